@@ -9,13 +9,21 @@ One "step" = one log_prob pass of the hot path over one resident batch of synthe
 GPU, default 1024).  Tiles are independent, so N ranks each own a shard (weak scaling); the only collective is
 the all-reduce (RCCL) of the summed log-likelihood, once per step.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line: only what the headline needs.
+  --full              also measures, in the same process, what the headline does not need: the other two
+                      arithmetics on the same batch with their accuracy against the headline's, the fp64-oracle
+                      check, config A and the secondary workloads (N=1) and the CPU baseline (N=1).
+  --dump-outputs DIR  after the timed steps, writes what the last timed step computed: DIR/log_prob.npy (float32,
+                      one value per tile, all ranks' shards in rank order) and DIR/log_prob_total.npy (float64, the
+                      all-reduced sum).  The inputs are seeded, so two builds can be compared output for output.
+
 Extra objects on the line
   roofline      dominant kernel = k_net_f32 at level 0 (32x32x4 tensors, 77 % of the FLOPs): algorithmic FLOP per
                 launch (conv1+conv2+conv3 of the coupling network at 2 FLOP/MAC) divided by
                 its average duration from HIP events recorded on the launch stream inside the timed region,
                 against the fp32-input MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md:42).
-  cpu_baseline  the CPU oracle (torch-CPU restatement, oracle/glowref_torch.py -- a port, not TensorFlow) timed
-                on this host's cores on a bounded sample of the same workload (rank 0, N=1 only).
+  cpu_baseline  (--full) the CPU oracle (torch-CPU restatement, oracle/glowref_torch.py -- a port, not TensorFlow)
+                timed on this host's cores on a bounded sample of the same workload (rank 0, N=1 only).
 """
 import argparse
 import json
@@ -437,6 +445,19 @@ def self_launch(args):
     return r.returncode
 
 
+def dump_outputs(path, lp, total, rank, world, dist):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- log_prob of every tile (all ranks' shards,
+    in rank order) and the all-reduced fp64 sum -- as <path>/log_prob.npy (float32) and <path>/log_prob_total.npy (float64)."""
+    shards = [lp.cpu().numpy()]
+    if dist is not None:
+        shards = [None] * world
+        dist.all_gather_object(shards, lp.cpu().numpy())
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "log_prob.npy"), np.concatenate(shards).astype(np.float32))
+        np.save(os.path.join(path, "log_prob_total.npy"), total.cpu().numpy().astype(np.float64))
+
+
 def git_head():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], capture_output=True, text=True, timeout=10).stdout.strip() or None
@@ -474,11 +495,18 @@ def main():
     ap.add_argument("--basis-train-steps", type=int, default=100, help="--workload basis: training steps per sigma level (3x at the first)")
     ap.add_argument("--basis-T", type=int, default=100, help="--workload basis: Langevin steps per sigma level before the timed region")
     ap.add_argument("--basis-crop", type=int, default=0, help="--workload basis: use only the first N mel bins of the 96x64 tiles (64: the 64x64 geometry of config B)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the log_prob_grad / train / basis sub-objects of the N=1 default run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-shapes", action="store_true", help="skip the config-A line inside the N=1 default run")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need (other arithmetics, accuracy checks, "
+                                                        "config A, secondary workloads, CPU baseline); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (default workload only)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the log_prob_grad / train / basis sub-objects of the N=1 run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the fp64-oracle check and the cpu_baseline object")
+    ap.add_argument("--no-other-shapes", action="store_true", help="--full: skip the config-A line inside the N=1 run")
     ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of CPU work for the cpu_baseline sample")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "log_prob":
+        ap.error("--dump-outputs writes the outputs of the default workload (log_prob) only")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -583,6 +611,7 @@ def main():
         assert torch.isfinite(total).all(), "non-finite log-likelihood"
         assert eng.range_status() == (False, 0), "the range guard fired"
         res["lp_main"] = lp.clone()
+        res["total_main"] = total.clone()
         if with_others:
             # the other arithmetic on the same batch: exact fp32 beside the split path (or vice versa), same run
             other = "f32" if precision != "f32" else "f16x3"
@@ -684,10 +713,12 @@ def main():
                 "roofline": roofline_obj(cfg, "f16x2", pr2, res.get("co", False)) if full else None}
         return out
 
-    res = measure(cfg, args.precision, args.steps, args.warmup, True)
+    res = measure(cfg, args.precision, args.steps, args.warmup, args.full)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["lp_main"], res["total_main"], rank, world, dist)
     out = line(cfg, args.precision, res, args.steps, args.warmup, True) if rank == 0 else None
     # accuracy of the headline arithmetic against the fp64 CPU oracle on two tiles of the same batch (rank 0)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # (N > 1: the other ranks would idle at the barrier meanwhile)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # (N > 1: the other ranks would idle at the barrier meanwhile)
         from oracle import glowref as R
         xs = res["x"][:2].cpu().numpy().astype(np.float64)
         ref = R.log_prob(xs, R.cast_params(res["params"], np.float64), cfg.as_dict())
@@ -697,7 +728,7 @@ def main():
     del res
     torch.cuda.empty_cache()
     # the other north-star shape (32x32x1, K=16, L=2: BASELINE.json configs[1]) in the same run, as a sub-object of the ONE line
-    if world == 1 and cfg is CONFIG_B and not args.no_other_shapes:
+    if args.full and world == 1 and cfg is CONFIG_B and not args.no_other_shapes:
         ra = measure(CONFIG_A, args.precision, args.steps, args.warmup, True)
         la = line(CONFIG_A, args.precision, ra, args.steps, args.warmup, False)
         out["config_A_32x32_K16_L2"] = {k: la[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "gflop_per_pass",
@@ -713,7 +744,7 @@ def main():
     # the secondary workloads of the path (BASELINE config 5) as compact sub-objects of the ONE line, each a few
     # seconds: the input-gradient path at the headline batch, the training step at the reference's batch of 32, and the BASIS chain
     # on the reference's 30 real mixture tiles with two priors trained here (K = 32, a shortened three-level ladder)
-    if world == 1 and cfg is CONFIG_B and not args.no_secondary:
+    if args.full and world == 1 and cfg is CONFIG_B and not args.no_secondary:
         def guarded_sub(name, fn):     # a secondary workload that fails reports its error in its sub-object; the headline line still prints
             try:
                 out[name] = fn()
@@ -757,7 +788,7 @@ def main():
     if rank == 0:
         out["git_head"] = git_head()
         out.update(dist_info)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, params_main, args.cpu_budget)
         out["summary"] = summary_of(out)      # LAST and short: the driver's record keeps only the tail of the line
         print(json.dumps(out), flush=True)

@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 C=${1:-unknown}
 O=gpurun_out
 mkdir -p $O
-python bench.py > $O/r04_bench.json 2> $O/r04_bench.err
+python bench.py --full > $O/r04_bench.json 2> $O/r04_bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-shapes --no-secondary > $O/r04_bench_under_rocprof.json 2> $O/r04_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-shapes --no-secondary > $O/r04_bench_under_rocprof.json 2> $O/r04_prof.err
 cp $(find $O/r04_prof -name "*kernel_stats.csv" | head -1) $O/r04_kernel_stats.csv; rm -rf $O/r04_prof
 echo "kernel trace done"
 for p in f16x3 f32; do
@@ -31,10 +31,10 @@ cp $(find $O/r04_prof_small -name "*kernel_stats.csv" | head -1) $O/r04_grad30_k
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof_basis -- python3 bench.py --workload basis --basis-levels 3 --basis-train-steps 30 --basis-T 20 --steps 10 --warmup 2 > /dev/null 2>> $O/r04_prof.err
 cp $(find $O/r04_prof_basis -name "*kernel_stats.csv" | head -1) $O/r04_basis_kernel_stats.csv; rm -rf $O/r04_prof_basis
 echo "traces done"
-GLOWK_BENCH_REHEARSAL=1 python bench.py --gpus 2 --steps 3 --warmup 1 --batch 256 --no-secondary > $O/r04_bench_gpus2_rehearsal.json 2>> $O/r04_bench.err
-GLOWK_BENCH_FORCE_DIST=1 python bench.py --steps 3 --warmup 1 --batch 256 --no-secondary --no-cpu-baseline --no-other-shapes > $O/r04_bench_rccl_1rank.json 2>> $O/r04_bench.err
+GLOWK_BENCH_REHEARSAL=1 python bench.py --full --gpus 2 --steps 3 --warmup 1 --batch 256 --no-secondary > $O/r04_bench_gpus2_rehearsal.json 2>> $O/r04_bench.err
+GLOWK_BENCH_FORCE_DIST=1 python bench.py --full --steps 3 --warmup 1 --batch 256 --no-secondary --no-cpu-baseline --no-other-shapes > $O/r04_bench_rccl_1rank.json 2>> $O/r04_bench.err
 echo "rehearsal done"
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes --no-secondary"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes --no-secondary"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/r04_pmc_fetch -- $B > /dev/null 2>> $O/r04_prof.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/r04_pmc_write -- $B > /dev/null 2>> $O/r04_prof.err
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/r04_pmc_mfma -- $B > /dev/null 2>> $O/r04_prof.err

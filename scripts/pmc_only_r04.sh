@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 C=${1:-unknown}
 O=gpurun_out
 mkdir -p $O
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes --no-secondary"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes --no-secondary"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/r04_pmc_fetch -- $B > /dev/null 2>> $O/r04_prof.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/r04_pmc_write -- $B > /dev/null 2>> $O/r04_prof.err
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/r04_pmc_mfma -- $B > /dev/null 2>> $O/r04_prof.err

@@ -41,7 +41,7 @@ def main():
         fcsv, wcsv, commit, out = sys.argv[2:6]
         f, w = per_kernel(fcsv), per_kernel(wcsv)
         res = {"build": commit, "tiles_per_launch": 1024,
-               "recipe": "two rocprofv3 --kernel-trace --pmc passes of `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes` "
+               "recipe": "two rocprofv3 --kernel-trace --pmc passes of `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-shapes` "
                          "(FETCH_SIZE; WRITE_SIZE), per-launch averages; bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 (gfx950 correction, MI355X_MICROARCH.md)",
                "hbm_bytes_per_level0_launch": {}, "kernels": {}}
         for k in sorted(set(f) | set(w)):

@@ -212,3 +212,18 @@ def test_bench_launches_its_own_ranks(monkeypatch, repo_root, capsys):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "WORLD_SIZE" in str(e.value.code)
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--workload", "train", "--dump-outputs", "d"]])
+def test_bench_rejects_bad_arguments_before_the_gpu(monkeypatch, argv, capsys):
+    """No timed step, or an output dump of a workload whose outputs it does not write: an argument error, before anything
+    touches the GPU."""
+    import importlib
+    import sys
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench.torch.cuda, "set_device", lambda *a: pytest.fail("touched the GPU"))
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    err = capsys.readouterr().err
+    assert e.value.code == 2 and ("--steps" in err or "--dump-outputs" in err)
