@@ -108,6 +108,10 @@ SYMBOLS = {
     "glowk_basis_mix": (_i, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_random": (_i, [_vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _i, _i, ctypes.c_uint64, _vp]),
     "glowk_add_noise": (_i, [_vp, _vp, ctypes.c_size_t, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _i, ctypes.c_uint64, _vp]),
+    "glowk_mel_filterbank": (_i, [_fp]),
+    "glowk_mel_frontend": (_i, [_vp, _i, _i, ctypes.c_float, _vp, _vp, _vp]),
+    "glowk_mel_to_power": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "glowk_masked_istft": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

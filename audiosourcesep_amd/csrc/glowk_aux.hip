@@ -1,6 +1,11 @@
-// glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint)
+// glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
+// the audio front end and mel inversion (glowk_audio.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
+#include "glowk_audio.h"
+
+#include <initializer_list>
+#include <mutex>
 
 using namespace glowk_eng;
 
@@ -93,5 +98,255 @@ uint32_t glowk_crc32c(const void* host_data, size_t n) {
   return c ^ 0xFFFFFFFFu;
 }
 
+
+// ---- audio: device constants (glowk_audio.h AudioConsts), built once on the host in fp64, uploaded once per device --------------
+namespace glowk_eng {
+struct AudioHost {
+  std::vector<float> tab, win, mel_w, bin_w, pinv, dense;   // dense: W [96][1025] (glowk_mel_filterbank)
+  std::vector<int> mel_lo, mel_len, mel_off, bin_mel;
+  float step = 0.0f;
+  std::string err;
+  AudioHost();
+};
+
+// Slaney mel scale (librosa hz_to_mel / mel_to_hz, htk=False): linear below 1 kHz (200/3 Hz per mel), logarithmic above
+static double hz_to_mel(double f) {
+  const double logstep = std::log(6.4) / 27.0;
+  return f >= 1000.0 ? 15.0 + std::log(f / 1000.0) / logstep : f / (200.0 / 3.0);
+}
+static double mel_to_hz(double m) {
+  const double logstep = std::log(6.4) / 27.0;
+  return m >= 15.0 ? 1000.0 * std::exp(logstep * (m - 15.0)) : (200.0 / 3.0) * m;
+}
+
+AudioHost::AudioHost() {
+  using namespace glowk_audio;
+  const double pi = 3.14159265358979323846;
+  tab.resize(NFFT);
+  win.resize(NFFT);
+  for (int m = 0; m < NFFT; ++m) {             // exact at the quarter turns, so DC / Nyquist columns carry no stray sine
+    tab[m] = (m % 512 == 0) ? (float)(m == 0 ? 1 : m == 1024 ? -1 : 0) : (float)std::cos(2.0 * pi * m / NFFT);
+    win[m] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * m / NFFT));   // scipy.signal.get_window('hann', 2048, fftbins=True)
+  }
+  // librosa.filters.mel(sr=16000, n_fft=2048, n_mels=96, fmin=125, fmax=7600), Slaney area normalisation
+  const double mmin = hz_to_mel(125.0), mmax = hz_to_mel(7600.0);
+  std::vector<double> mel_f(NMEL + 2);
+  for (int i = 0; i < NMEL + 2; ++i) mel_f[i] = mel_to_hz(i == NMEL + 1 ? mmax : mmin + i * ((mmax - mmin) / (NMEL + 1)));
+  std::vector<double> W((size_t)NMEL * NBIN);
+  for (int i = 0; i < NMEL; ++i) {
+    const double d0 = mel_f[i + 1] - mel_f[i], d1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+    for (int k = 0; k < NBIN; ++k) {
+      const double f = k * (16000.0 / NFFT);
+      const double lower = -(mel_f[i] - f) / d0, upper = (mel_f[i + 2] - f) / d1;
+      W[(size_t)i * NBIN + k] = (double)(float)(std::max(0.0, std::min(lower, upper)) * enorm);
+    }
+  }
+  dense.assign(W.begin(), W.end());
+  mel_lo.resize(NMEL); mel_len.resize(NMEL); mel_off.resize(NMEL);
+  bin_mel.assign(2 * NBIN, 0); bin_w.assign(2 * NBIN, 0.0f);
+  std::vector<int> cover(NBIN, 0);
+  for (int i = 0; i < NMEL; ++i) {
+    int lo = -1, hi = -1;
+    for (int k = 0; k < NBIN; ++k)
+      if (W[(size_t)i * NBIN + k] != 0.0) { if (lo < 0) lo = k; hi = k; }
+    if (lo < 0) { err = "mel filterbank: an empty filter"; return; }
+    mel_lo[i] = lo; mel_len[i] = hi - lo + 1; mel_off[i] = (int)mel_w.size();
+    for (int k = lo; k <= hi; ++k) {
+      const float w = (float)W[(size_t)i * NBIN + k];
+      mel_w.push_back(w);
+      if (w == 0.0f) continue;
+      if (cover[k] == 2) { err = "mel filterbank: a bin in more than two filters"; return; }
+      bin_mel[2 * k + cover[k]] = i;
+      bin_w[2 * k + cover[k]] = w;
+      ++cover[k];
+    }
+  }
+  // G = W W^T (SPD, 96 x 96): step = 1 / lambda_max(G) by power iteration, W+ = W^T G^-1 by Cholesky
+  std::vector<double> G((size_t)NMEL * NMEL, 0.0);
+  for (int i = 0; i < NMEL; ++i)
+    for (int j = 0; j < NMEL; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < NBIN; ++k) s += W[(size_t)i * NBIN + k] * W[(size_t)j * NBIN + k];
+      G[(size_t)i * NMEL + j] = s;
+    }
+  std::vector<double> v(NMEL, 1.0), u(NMEL);
+  double lam = 0.0;
+  for (int it = 0; it < 5000; ++it) {
+    double nrm = 0.0;
+    for (int i = 0; i < NMEL; ++i) {
+      double s = 0.0;
+      for (int j = 0; j < NMEL; ++j) s += G[(size_t)i * NMEL + j] * v[j];
+      u[i] = s;
+      nrm += s * s;
+    }
+    nrm = std::sqrt(nrm);
+    lam = nrm;
+    for (int i = 0; i < NMEL; ++i) v[i] = u[i] / nrm;
+  }
+  step = (float)(1.0 / lam);
+  std::vector<double> Lc((size_t)NMEL * NMEL, 0.0);
+  for (int j = 0; j < NMEL; ++j) {
+    double d = G[(size_t)j * NMEL + j];
+    for (int k = 0; k < j; ++k) d -= Lc[(size_t)j * NMEL + k] * Lc[(size_t)j * NMEL + k];
+    if (!(d > 0.0)) { err = "mel filterbank: W W^T is not positive definite"; return; }
+    Lc[(size_t)j * NMEL + j] = std::sqrt(d);
+    for (int i = j + 1; i < NMEL; ++i) {
+      double s = G[(size_t)i * NMEL + j];
+      for (int k = 0; k < j; ++k) s -= Lc[(size_t)i * NMEL + k] * Lc[(size_t)j * NMEL + k];
+      Lc[(size_t)i * NMEL + j] = s / Lc[(size_t)j * NMEL + j];
+    }
+  }
+  pinv.assign((size_t)NBIN * NMEL, 0.0f);
+  std::vector<double> z(NMEL);
+  for (int k = 0; k < NBIN; ++k) {              // row k of W+ = G^-1 w_k (G symmetric), w_k = column k of W
+    if (!cover[k]) continue;                    // exactly zero outside every filter
+    for (int i = 0; i < NMEL; ++i) {
+      double s = W[(size_t)i * NBIN + k];
+      for (int j = 0; j < i; ++j) s -= Lc[(size_t)i * NMEL + j] * z[j];
+      z[i] = s / Lc[(size_t)i * NMEL + i];
+    }
+    for (int i = NMEL - 1; i >= 0; --i) {
+      double s = z[i];
+      for (int j = i + 1; j < NMEL; ++j) s -= Lc[(size_t)j * NMEL + i] * z[j];
+      z[i] = s / Lc[(size_t)i * NMEL + i];
+    }
+    for (int i = 0; i < NMEL; ++i) pinv[(size_t)k * NMEL + i] = (float)z[i];
+  }
+}
+
+static const AudioHost& audio_host() {
+  static const AudioHost host;                 // function-local static: built once, thread-safe by the language
+  return host;
+}
+
+// the device every pointer lives on; a host, unregistered or foreign-device pointer is refused (the kernels would fault on it)
+static int audio_device(std::initializer_list<const void*> ptrs, int* dev) {
+  *dev = -1;
+  for (const void* p : ptrs) {
+    if (!p) continue;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || !(a.type == hipMemoryTypeDevice || a.isManaged) || a.device < 0) {
+      (void)hipGetLastError();
+      return fail("audio: every tensor must be device memory");
+    }
+    if (*dev >= 0 && a.device != *dev) return fail("audio: the tensors are on different devices");
+    *dev = a.device;
+  }
+  return 0;
+}
+
+// one upload per device, kept for the life of the process (allocated under the caller's DeviceGuard)
+static int audio_consts(int dev, glowk_audio::AudioConsts* out) {
+  const AudioHost& host = audio_host();
+  static std::mutex mu;
+  static std::vector<std::pair<int, glowk_audio::AudioConsts>> cache;
+  if (!host.err.empty()) return fail(host.err);
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& e : cache)
+    if (e.first == dev) { *out = e.second; return 0; }
+  const size_t nf = host.tab.size() + host.win.size() + host.mel_w.size() + host.bin_w.size() + host.pinv.size();
+  const size_t ni = host.mel_lo.size() + host.mel_len.size() + host.mel_off.size() + host.bin_mel.size();
+  char* base = nullptr;
+  HIPCHK(hipMalloc(&base, (nf + ni) * 4));
+  std::vector<char> img((nf + ni) * 4);
+  size_t pos = 0;
+  auto put = [&](const void* src, size_t n) { std::memcpy(img.data() + pos, src, n * 4); const char* p = base + pos; pos += n * 4; return p; };
+  glowk_audio::AudioConsts c;
+  c.tab = (const float*)put(host.tab.data(), host.tab.size());
+  c.win = (const float*)put(host.win.data(), host.win.size());
+  c.mel_w = (const float*)put(host.mel_w.data(), host.mel_w.size());
+  c.bin_w = (const float*)put(host.bin_w.data(), host.bin_w.size());
+  c.pinv = (const float*)put(host.pinv.data(), host.pinv.size());
+  c.mel_lo = (const int*)put(host.mel_lo.data(), host.mel_lo.size());
+  c.mel_len = (const int*)put(host.mel_len.data(), host.mel_len.size());
+  c.mel_off = (const int*)put(host.mel_off.data(), host.mel_off.size());
+  c.bin_mel = (const int*)put(host.bin_mel.data(), host.bin_mel.size());
+  c.step = host.step;
+  hipError_t e = hipMemcpy(base, img.data(), img.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(base);
+    return fail(std::string("audio constants upload: ") + hipGetErrorString(e));
+  }
+  cache.emplace_back(dev, c);
+  *out = c;
+  return 0;
+}
+}  // namespace glowk_eng
+
+int glowk_mel_filterbank(float* host_out) {
+  if (!host_out) return fail("null buffer");
+  const AudioHost& host = audio_host();
+  if (!host.err.empty()) return fail(host.err);
+  std::memcpy(host_out, host.dense.data(), host.dense.size() * sizeof(float));
+  return 0;
+}
+
+int glowk_mel_frontend(const float* audio_dev, int N, int n_samples, float top_db, float* mel_db_dev, float* stft_dev, void* stream) {
+  using namespace glowk_audio;
+  if (!audio_dev || !mel_db_dev) return fail("null tensor");
+  if (N < 0 || N > (1 << 20)) return fail("mel_frontend: N must be in [0, 2^20]");
+  if (n_samples <= PAD || n_samples >= MAX_FRAMES * HOP)
+    return fail("mel_frontend: n_samples must be in (1024, 65536): reflect padding needs more than 1024 samples, the tile at most 128 frames");
+  if (!(std::fabs(top_db) < 1e30f)) return fail("mel_frontend: top_db must be finite");
+  if (N == 0) return 0;
+  int dev;
+  if (int rc = audio_device({audio_dev, mel_db_dev, stft_dev}, &dev)) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  const int F = 1 + n_samples / HOP, ftiles = (F + 31) / 32;
+  hipStream_t s = (hipStream_t)stream;
+  float* power = nullptr;                      // |X|^2 scratch, only when the caller does not take the complex STFT (k_mel_db squares X)
+  if (!stft_dev) HIPCHK(hipMallocAsync((void**)&power, (size_t)N * NBIN * F * sizeof(float), s));
+  hipLaunchKernelGGL(k_stft, dim3((unsigned)(N * ftiles), (NBIN + 127) / 128), dim3(256), 0, s, audio_dev, n_samples, F, ftiles, c, power, stft_dev);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mel_db, dim3((unsigned)N), dim3(256), NMEL * F * sizeof(float), s, (const float*)power,
+                       (const float2*)stft_dev, F, top_db, c, mel_db_dev);
+    e = hipGetLastError();
+  }
+  if (power) (void)hipFreeAsync(power, s);
+  if (e != hipSuccess) return fail(std::string("launch k_stft / k_mel_db: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int glowk_mel_to_power(const float* mel_db_dev, int N, int frames, int iters, float* power_dev, void* stream) {
+  using namespace glowk_audio;
+  if (!mel_db_dev || !power_dev) return fail("null tensor");
+  if (N < 0 || N > (1 << 20)) return fail("mel_to_power: N must be in [0, 2^20]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail("mel_to_power: frames must be in [1, 128]");
+  if (iters < 0 || iters > 100000) return fail("mel_to_power: iters must be in [0, 100000]");
+  if (N == 0) return 0;
+  int dev;
+  if (int rc = audio_device({mel_db_dev, power_dev}, &dev)) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  const int total = N * frames;
+  hipLaunchKernelGGL(k_nnls, dim3((unsigned)((total + NNLS_G - 1) / NNLS_G)), dim3(256), 0, (hipStream_t)stream, mel_db_dev, frames, total, iters, c,
+                     power_dev);
+  LAUNCHCHK("k_nnls");
+  return 0;
+}
+
+int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev, int N, int frames, int wiener, float* audio_dev, void* stream) {
+  using namespace glowk_audio;
+  if (!power_dev || !stft_mix_dev || !audio_dev) return fail("null tensor");
+  if (S < 1 || S > 16) return fail("masked_istft: S must be in [1, 16]");
+  if (wiener && S < 2) return fail("masked_istft: the Wiener filter needs S >= 2 sources");
+  if (N < 0 || N > (1 << 20)) return fail("masked_istft: N must be in [0, 2^20]");
+  if (frames < 2 || frames > MAX_FRAMES) return fail("masked_istft: frames must be in [2, 128]");
+  if (N == 0) return 0;
+  int dev;
+  if (int rc = audio_device({power_dev, stft_mix_dev, audio_dev}, &dev)) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  const int htiles = (frames - 1 + 31) / 32;
+  hipLaunchKernelGGL(k_istft, dim3((unsigned)(S * N * htiles), HOP / 128), dim3(256), 0, (hipStream_t)stream, power_dev, S, stft_mix_dev, N, frames,
+                     htiles, wiener ? 1 : 0, c, audio_dev);
+  LAUNCHCHK("k_istft");
+  return 0;
+}
 
 }  // extern "C"

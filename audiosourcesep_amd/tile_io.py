@@ -3,7 +3,8 @@
 * TFRecord files written by ``datasets/preprocessing.py:197-271``: one ``tf.train.Example`` per tensor with features
   ``'array'`` (float_list, the flattened values) and ``'shape'`` (int64_list).  ``read_tfrecord`` / ``write_tfrecord``
   implement the TFRecord framing (length, masked CRC-32C, payload, masked CRC-32C) and the two protobuf messages by hand.
-* mel front-end constants of ``datasets/wav_to_spec.py:84-98`` and the 2.04 s tiling of ``run_basis_sep.py:346-351``.
+* mel front-end constants of ``datasets/wav_to_spec.py:84-98`` and the 2.04 s tiling of ``run_basis_sep.py:346-351``; the front end
+  itself (wav -> tiles) and the inversion (tiles -> wav) are ``audio.py`` (HIP kernels in ``csrc/glowk_audio.h``).
 Host-side only; feeds ``[N, 96, 64, 1]`` float32 dB tiles to the engine.
 """
 import struct

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 400
+#define GLOWK_VERSION 410
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -297,6 +297,29 @@ int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int whi
  * noise-conditioned training step (train_noisy_glow.py:31, X + tf.random.normal(X.shape) * noise).  out_dev may equal x_dev. */
 int glowk_add_noise(const float* x_dev, float* out_dev, size_t n, float sigma, uint64_t seed, uint64_t step, int which, uint64_t offset,
                     void* stream);
+
+/* --- audio: mel front end and mel-to-audio inversion (datasets/data_loader.py:146-164, melspec_inversion_basis.py:42-93) ----- */
+/* Handle-free; the constants of the reference's front end are compiled in: 16 kHz, n_fft 2048, hop 512, periodic Hann, 96 Slaney
+ * mels over 125..7600 Hz (librosa.filters.mel defaults), dB clipped to [-100, 20].  Spectra are [.., 1025, F] with the frame
+ * fastest; a complex spectrum is re/im interleaved (torch.complex64).  The first call on a device uploads its constants there.
+ * Every tensor must be device memory on one device (a host pointer is refused); the caller owns the shapes.
+ */
+/* the front end's mel filterbank W [96][1025] (float32, row-major) as the kernels use it, into a host buffer; no device call */
+int glowk_mel_filterbank(float* host_out);
+/* audio [N, n_samples] 16 kHz -> mel_db [N, 96, F], F = 1 + n_samples/512 (librosa.stft center=True, reflect padding,
+ * |X|^2, mel, power_to_db, np.clip); stft_dev (nullable) [N, 1025, F] complex, re/im interleaved; top_db <= 0: no per-extract
+ * floor, else L = max(L, max over the extract of L - top_db) before the clip.  1024 < n_samples < 65536 (F <= 128).  Without
+ * stft_dev the call takes an [N, 1025, F] float scratch from the stream-ordered allocator for |X|^2. */
+int glowk_mel_frontend(const float* audio_dev, int N, int n_samples, float top_db, float* mel_db_dev, float* stft_dev, void* stream);
+/* mel_db [N, 96, F] -> linear power [N, 1025, F]: 10^(L/10), then per frame the NNLS of librosa.feature.inverse.mel_to_stft
+ * by FISTA (projected gradient with Nesterov momentum, step 1/|W|_2^2) from max(0, W+ b), `iters` iterations (0..100000);
+ * F in [1, 128]. */
+int glowk_mel_to_power(const float* mel_db_dev, int N, int frames, int iters, float* power_dev, void* stream);
+/* power [S, N, 1025, F] + mixture STFT [N, 1025, F] -> audio [S, N, (F-1)*512] (librosa.istft, center=True): wiener == 0 reuses
+ * the mixture's phase, sqrt(x) X / |X| (phase 1 where X == 0); wiener != 0 needs S >= 2 and filters x_i / (sum_j x_j + 1e-10) X.
+ * S in [1, 16], F in [2, 128]. */
+int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev, int N, int frames, int wiener, float* audio_dev,
+                       void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
