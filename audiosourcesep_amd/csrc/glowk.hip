@@ -23,17 +23,11 @@ int num_cus() {
   }
   return n;
 }
-bool h3_shape16() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("GLOWK_H3_SHAPE"); v = (e && atoi(e) == 32) ? 0 : 1; }
-  return v == 1;
-}
 void launch_fail(const std::string& m) { fail(m); }
-unsigned long long* g_dbg_stamps = nullptr;    // glowk_debug_stamps
 static EnvSwitches read_env() {
   auto on = [](const char* n) { return getenv(n) != nullptr; };
-  return EnvSwitches{on("GLOWK_HALF_OFF"), on("GLOWK_HALF_FORCE"), on("GLOWK_FAM16_SMALL"), on("GLOWK_BWD_LIGHT_4"), on("GLOWK_COUPLE_PER_SAMPLE"),
-                     on("GLOWK_COUPLE_4"), on("GLOWK_NO_FUSE"), on("GLOWK_WGRAD_PLAIN"), on("GLOWK_WGRAD_128"), on("GLOWK_CO_OFF"), on("GLOWK_Q_OFF"), on("GLOWK_CO_SPLIT_OFF"), on("GLOWK_CO_TRAIN_OFF"), on("GLOWK_WGRAD_16_OFF"), on("GLOWK_CO8_OFF"), on("GLOWK_CO_MID_OFF")};
+  return EnvSwitches{on("GLOWK_BWD_LIGHT_4"), on("GLOWK_NO_FUSE"), on("GLOWK_WGRAD_PLAIN"), on("GLOWK_CO_OFF"), on("GLOWK_Q_OFF"), on("GLOWK_CO_TRAIN_OFF"),
+                     on("GLOWK_TRAIN_RECOMPUTE"), on("GLOWK_TRAIN_PERSTEP"), on("GLOWK_PG_JOIN")};
 }
 static EnvSwitches g_env = read_env();
 const EnvSwitches& env() { return g_env; }
@@ -132,13 +126,13 @@ struct FlatLd { double* slot; int stride, base; };
 
 int launch_couple(int c, const CoupleArgs& a, int N, hipStream_t s, const FlatLd* fl = nullptr, bool* flat_used = nullptr) {
   const int hw = a.h * a.w;
-  if (N < 2 * num_cus() && hw % 64 == 0 && (!a.logdet || (fl && fl->slot)) && !glowk_detail::env().couple_per_sample) {
+  if (N < 2 * num_cus() && hw % 64 == 0 && (!a.logdet || (fl && fl->slot))) {
     // few samples: a flat grid over the pixels instead of one workgroup per sample (30 tiles: 30 workgroups on 256 CUs); sixteen
     // lanes per pixel where the level is deep (c >= 8) and small
     CoupleArgs b = a;
     b.logdet = nullptr;
     double* slots = a.logdet ? fl->slot : (double*)nullptr;
-    const bool wide = c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus() && !glowk_detail::env().couple_4;
+    const bool wide = c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus();
     if (wide) { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
     else { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 4>), dim3((a.Q + 63) / 64), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
     LAUNCHCHK("k_couple_flat");
@@ -343,7 +337,7 @@ NetArgs net_args(glowk_handle* h, const Level& lv, const StepDev& sd, const floa
   a.bnorm = 1.0f;
   a.fuse = 0; a.co = glowk_detail::env().co_off ? 0 : 1; a.fz_osave = nullptr; a.fz_b3 = nullptr; a.fz_A = nullptr; a.fz_b = nullptr; a.fz_out = nullptr; a.fz_out_stride = 0; a.fz_out_off = 0; a.fz_inverse = 0;
   a.fz_edge = nullptr; a.fz_ldpart = nullptr;
-  a.dbg = glowk_detail::g_dbg_stamps;
+  a.pad = nullptr;
   a.xmax_out = h->d_probe ? h->d_probe + ((&lv - h->levels.data()) * h->cfg.K + (&sd - lv.dev.data())) : nullptr;
   return a;
 }
@@ -651,17 +645,6 @@ extern "C" {
 
 int glowk_version(void) { return GLOWK_VERSION; }
 void glowk_reload_env(void) { glowk_detail::reload_env(); }
-
-int glowk_debug_stamps(unsigned long long* out, int n) {
-  if (n < 0 || n > 64 || (n && !out)) return fail("glowk_debug_stamps: n must be in [0, 64]");
-  if (!glowk_detail::g_dbg_stamps) {
-    HIPCHK(hipMalloc(&glowk_detail::g_dbg_stamps, 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(glowk_detail::g_dbg_stamps, 0, 64 * sizeof(unsigned long long)));
-  }
-  HIPCHK(hipDeviceSynchronize());
-  if (n) HIPCHK(hipMemcpy(out, glowk_detail::g_dbg_stamps, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return 0;
-}
 const char* glowk_last_error(void) { return g_err.c_str(); }
 
 int glowk_create(const glowk_config* cfg, int device, glowk_handle** out) {
@@ -1046,7 +1029,7 @@ int glowk_range_probe_end(glowk_handle* h, float* fwd_ratio, float* bwd_ratio, v
       if (sd.xlim_f > 0.f) rf = std::max(rf, v[i] / sd.xlim_f);
       // (the backward kernels normalise their inputs per pixel: what can fail is the STATIC requirement 2 * 2^-4 <= xlim_b;
       //  reported as that ratio -- the recorded gradient magnitudes v[LK + i] no longer matter for the range)
-      if (sd.xlim_b > 0.f && v[LK + i] > 0.f) rb = std::max(rb, getenv("GLOWK_PROBE_RAW_BWD") ? v[LK + i] / sd.xlim_b : 0.125f / sd.xlim_b);   // (raw: the training sweep's uniformly scaled inputs)
+      if (sd.xlim_b > 0.f && v[LK + i] > 0.f) rb = std::max(rb, 0.125f / sd.xlim_b);
     }
   if (fwd_ratio) *fwd_ratio = rf;
   if (bwd_ratio) *bwd_ratio = rb;

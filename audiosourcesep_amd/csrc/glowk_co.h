@@ -73,9 +73,7 @@ struct RingC {
 
 // end of an op without a unit to wait for: this wave's LDS reads have retired (a DMA into the slot they read may follow the barrier)
 __device__ __forceinline__ void co_bar() {
-#ifndef GLOWK_EXP_CONOLGKM
   __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0) alone
-#endif
   h3_barrier();
 }
 
@@ -84,15 +82,8 @@ __device__ __forceinline__ void co_bar() {
 // LDS read still in flight when the wave passed the barrier after which another wave's DMA refills the slot)
 template <int N>
 __device__ __forceinline__ void co_end() {
-#ifdef GLOWK_EXP_CONOLGKM
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));   // vmcnt(N); expcnt / lgkmcnt: no wait
-#else
   __builtin_amdgcn_s_waitcnt((N & 15) | 0x0070 | ((N >> 4) << 14));   // vmcnt(N) and lgkmcnt(0)
-#endif
   h3_barrier();
-#ifdef GLOWK_EXP_COSLEEP   // (diagnostic build: a pause between the publishing barrier and the first read of the published unit)
-  __builtin_amdgcn_s_sleep(GLOWK_EXP_COSLEEP);
-#endif
 }
 // ... with `more` extra operations (the op's stores: a saving launch's ReLU mask) allowed to stay in flight, decided per wave at run time
 template <int N>
@@ -125,10 +116,6 @@ __device__ __forceinline__ void co_Y(const float4* slot, const h8 (&bh)[2], cons
     d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
     d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
   };
-#ifdef GLOWK_EXP_COPRIO    // (A/B build: a wave in its matrix ops outranks its SIMD partner -- the other workgroup's wave, possibly in the VALU-heavy X op:
-                           //  62.42 -> 62.74 ms per 1024-tile log_prob, +0.5 %: not kept)
-  __builtin_amdgcn_s_setprio(GLOWK_EXP_COPRIO);
-#endif
   load(A[0], 0);
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) {
@@ -136,9 +123,6 @@ __device__ __forceinline__ void co_Y(const float4* slot, const h8 (&bh)[2], cons
     if (gi + 1 < NG) load(A[(gi + 1) & 1], gi + 1);
     if constexpr (H == 1) {
       const int piece = gi * 4 + w4;
-#ifdef GLOWK_EXP_COHALFDMA   // (diagnostic build, wrong results: every other unit piece is not fetched -- is the L2 -> LDS path what bounds the form?)
-      if (gi & 1)
-#endif
       glds16(reinterpret_cast<const float4*>(ub + (size_t)piece * 1024 + voff), dst + piece * 64);
       asm volatile("; dma site %0" ::"n"(TAG * 16 + gi));
     } else if (gi == 0) {
@@ -162,9 +146,6 @@ __device__ __forceinline__ void co_Y(const float4* slot, const h8 (&bh)[2], cons
     acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
-#ifdef GLOWK_EXP_COPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Z: conv3 unit z of a pass = NFH tiles (16 rows x one hidden block) in (hidden block, row block) order.  Two passes in one workgroup:
@@ -208,15 +189,9 @@ __device__ __forceinline__ void co_Z(const NetArgs& a, const H3Ctx& hc, const Co
       unsigned mask = 0, bits = 0;
       if (G::BWD) mask = hc.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];        // mask1: the ReLU after conv1
       if constexpr (G::STORE)
-#ifdef GLOWK_EXP_TILEDST
-        bits = h3s_act_pair<MODE7, true>(acc2[2 * fo][0], acc2[2 * fo + 1][0], acc2[2 * fo][1], acc2[2 * fo + 1][1], a.sc2, mask, bh, bl,
-                                         uniform_fptr(a.st2 + ((size_t)blockIdx.x * NF * 32 + (size_t)(PASS * NFH + fo) * 32 * GLOWK_EXP_TILEDST) * 128),
-                                         ((unsigned)(4 * kq) * 128u + (unsigned)(q[0] & 127)) * 4u, 128u * 4u);
-#else
         bits = h3s_act_pair<MODE7, true>(acc2[2 * fo][0], acc2[2 * fo + 1][0], acc2[2 * fo][1], acc2[2 * fo + 1][1], a.sc2, mask, bh, bl,
                                          uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q), ((unsigned)(4 * kq) * (unsigned)a.Q + (unsigned)q[0]) * 4u,
                                          (unsigned)a.Q * 4u);
-#endif
       else {
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) bits |= h3s_act<MODE7, false>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf]) << (8 * hf);
@@ -241,9 +216,6 @@ __device__ __forceinline__ void co_Z(const NetArgs& a, const H3Ctx& hc, const Co
           const float val = (LAST && G::MERGE) ? part + keep[ml][hf][r] : part;
           if constexpr (G::FUSE) {
             if (m < M3) pl[m * CO_PSTR + (int)(threadIdx.x >> 6) * 32 + 16 * hf + (lane & 15)] = val;
-#ifdef GLOWK_EXP_COCHECK
-            keep[ml][hf][r] = val;      // (diagnostic build: the kernel re-reads what it wrote)
-#endif
           } else {
             float* Pp = a.P + ((SOLO || !G::MERGE) ? (size_t)PASS * a.pstride : (size_t)0);
             if (m < M3 && qok[hf]) Pp[(size_t)m * a.Q + q[hf]] = val;
@@ -290,48 +262,21 @@ __device__ __forceinline__ void co_pass(const NetArgs& a, const H3Ctx& hc, const
   for (int i0 = 0; i0 < NF; i0 += 2) {
     // ---- hidden block i0 (conv1 operands in K0).  Its second unit (-> M1): the prologue's in a first pass' block 0; with two conv3 units
     //      a second pass' block 0 finds unit 1 requested by Z_0 and asks for unit 0 (-> M0) itself
-    if (i0 > 0 || (SECOND && !G::M0LAST)) {
-#ifdef GLOWK_EXP_COHALFDMA
-      stage4<G::UNITP / 2, 73>(G::main_unit(c.img, PASS, i0, 1), c.m1, c.w4, c.voff);
-#else
-      stage4<G::UNITP, 73>(G::main_unit(c.img, PASS, i0, 1), c.m1, c.w4, c.voff);
-#endif
-    }
+    if (i0 > 0 || (SECOND && !G::M0LAST)) stage4<G::UNITP, 73>(G::main_unit(c.img, PASS, i0, 1), c.m1, c.w4, c.voff);
     if constexpr (SECOND && G::M0LAST) {
       if (i0 == 0) stage4<G::UNITP, 77>(G::main_unit(c.img, PASS, 0, 0), c.m0, c.w4, c.voff);
     }
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 2);
     h3s_X<KIN, MOUT, NF, G::MODEX, 2, 0, PASS, G::STORE>(a, hc, i0, xh, xl, lane, bh, bl);
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 3);
     if (SECOND && G::M0LAST && i0 == 0) co_end<0>();            // (the unit this very op asked for)
-    else {
-#ifdef GLOWK_EXP_COHALFDMA
-      co_end_st<G::PPW / 2>(st);
-#else
-      co_end_st<G::PPW + XST>(st);                    // unit 2 i0 (M0) landed; this op's unit (and its stores) may still be in flight
-#endif
-    }
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 4);
+    else co_end_st<G::PPW + XST>(st);                   // unit 2 i0 (M0) landed; this op's unit (and its stores) may still be in flight
     co_Y<NFH, MODE7, 0, 1, S::K1P>(c.m0, bh, bl, acc2, lane, hc.k1img + (size_t)((i0 + 2) % NF) * S::K14, hc.k1s0, c.w4, c.voff);
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 5);
     co_end_st<G::K1PW + XST>(st);                       // unit 2 i0 + 1 (M1) landed (asked for before X's stores: they may stay in flight)
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 6);
     co_Y<NFH, MODE7, 1, 2, S::K1P>(c.m1, bh, bl, acc2, lane, G::main_unit(c.img, PASS, i0 + 1, 0), c.m0, c.w4, c.voff);
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 7);
     co_bar();                                           // (M1 free for the next X's unit)
-    if (PASS == 0 && i0 == 2) GLOWK_STAMP(a, 8);
     // ---- hidden block i0 + 1 (conv1 operands in K1)
-#ifdef GLOWK_EXP_COHALFDMA
-    stage4<G::UNITP / 2, 74>(G::main_unit(c.img, PASS, i0 + 1, 1), c.m1, c.w4, c.voff);
-#else
     stage4<G::UNITP, 74>(G::main_unit(c.img, PASS, i0 + 1, 1), c.m1, c.w4, c.voff);
-#endif
     h3s_X<KIN, MOUT, NF, G::MODEX, 2, 1, PASS, G::STORE>(a, hc, i0 + 1, xh, xl, lane, bh, bl);
-#ifdef GLOWK_EXP_COHALFDMA
-    co_end_st<G::PPW / 2>(st);
-#else
     co_end_st<G::PPW + XST>(st);
-#endif
     co_Y<NFH, MODE7, 0, 3, S::K1P>(c.m0, bh, bl, acc2, lane, hc.k1img + (size_t)((i0 + 3) % NF) * S::K14, hc.k1s1, c.w4, c.voff);
     co_end_st<G::K1PW + XST>(st);
     // (after the last block: conv3 unit 1 takes the place of "unit 2 NF")
@@ -340,7 +285,6 @@ __device__ __forceinline__ void co_pass(const NetArgs& a, const H3Ctx& hc, const
     co_bar();
   }
   f32x4 acc3[G::NMT][2];
-  GLOWK_STAMP(a, 9 + (PASS == 0 ? 0 : 1));                  // (9: pass 0's blocks done, 10: pass 1's)
   co_Z<KIN, MOUT, NF, MODE, PASS, SOLO, 0>(a, hc, c, epl, pl, acc2, acc3, bh, bl, q, qok, lane, kq, keep);
   co_Z<KIN, MOUT, NF, MODE, PASS, SOLO, 1>(a, hc, c, epl, pl, acc2, acc3, bh, bl, q, qok, lane, kq, keep);
   if constexpr (G::NMT >= 3) co_Z<KIN, MOUT, NF, MODE, PASS, SOLO, 2>(a, hc, c, epl, pl, acc2, acc3, bh, bl, q, qok, lane, kq, keep);
@@ -358,7 +302,6 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   static_assert(!(G::FUSE && SPLIT), "the fused coupling needs both passes in one workgroup");
 
   const int tid = threadIdx.x;
-  GLOWK_STAMP(a, 0);
   // (aligned 1024: the LDS layout is sorted by alignment first, so the DMA targets take the lowest addresses and the fused form's
   //  copy of P the highest)
   __shared__ __attribute__((aligned(1024))) float4 slotM0[G::UNIT4];
@@ -377,10 +320,6 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
     __shared__ float4 vstash_arr[CO_PX];
     plds = plds_arr; vstash = vstash_arr;
   }
-#ifdef GLOWK_EXP_COPAD     // (diagnostic build: extra LDS per workgroup -- does a failure follow the LDS footprint / the number of resident workgroups?)
-  __shared__ float copad[GLOWK_EXP_COPAD];
-  if (a.Q < 0) copad[tid] = 1.0f;
-#endif
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = lane & 15;
@@ -462,12 +401,8 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   // forward: the static bound; backward (normalised per pixel): only a non-finite gradient can leave the range
   if (((G::BWD && !G::STORE) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
   if (a.xmax_out) range_probe(a.xmax_out, xmax);
-#ifdef GLOWK_EXP_COPAD
-  if (a.Q < -1 && a.flag) *a.flag = (int)copad[tid ^ 1];
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  GLOWK_STAMP(a, 1);
 
   f32x4 keep[G::NMT][2];
   if constexpr (SPLIT) {
@@ -477,31 +412,8 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
     co_pass<KIN, MOUT, NF, MODE, 0, false>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
     co_pass<KIN, MOUT, NF, MODE, 1, false>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
   }
-  GLOWK_STAMP(a, 12);
   if constexpr (G::FUSE) {
     __syncthreads();       // every wave's LDS writes of P are complete and visible (lgkmcnt(0) + barrier)
-#ifdef GLOWK_EXP_COCHECK    // (diagnostic build: does the LDS copy of P still hold what this wave wrote?  A mismatch raises the range flag;
-                            //  the values are written again before the tail reads them)
-    {
-      bool bad = false;
-#pragma unroll
-      for (int ml = 0; ml < 3; ++ml)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = ml * 16 + 4 * kq + r;
-            if (m < MOUT) {
-              float* p = &plds[m * CO_PSTR + wave * 32 + 16 * hf + (lane & 15)];
-              if (__float_as_uint(*p) != __float_as_uint(keep[ml][hf][r])) bad = true;
-              *p = keep[ml][hf][r];
-            }
-          }
-      if (bad && a.flag) *a.flag = 1;
-      __syncthreads();
-    }
-#endif
     fused_couple<CO_PX, CO_PSTR>(a, plds, vstash, tid);
   }
-  GLOWK_STAMP(a, 13);
 }

@@ -22,6 +22,8 @@
 //     vmcnt is an in-order counter, each such load is serialised behind the whole DMA;
 //  3. fp32-input MFMA and the FP32 VALU share one datapath: VALU FMAs do not hide under v_mfma_f32_32x32x2_f32.
 #pragma once
+#include "glowk_act_scale.h"
+
 #include <hip/hip_runtime.h>
 #include <utility>
 #include <stdint.h>
@@ -75,22 +77,12 @@ struct NetArgs {
   // (before BatchNorm); backward: st1 = mask2 * conv3^T(g_o) (gradient wrt relu2's output), st2 = mask1 * (K2 g_a2) (wrt relu1's)
   float* st1;
   float* st2;
-  unsigned long long* dbg;   // diagnostic (glowk_debug_stamps), normally null: in-kernel time stamps of workgroup (0, 0)'s first lane
+  void* pad;             // always null: keeps the kernel arguments at 264 bytes (256 moves the hidden arguments and changes the code)
 };
-
-// time stamp i of the launch (constant 100 MHz counter), in builds with -DGLOWK_STAMPS (python -c "import __graft_entry__ as g;
-// g.build(tag='stamps', extra_flags=['-DGLOWK_STAMPS'])", then GLOWK_LIB=.../libglowk_stamps.so): the product kernels carry none
-#ifdef GLOWK_STAMPS
-#define GLOWK_STAMP(a, i) do { if ((a).dbg && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) (a).dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define GLOWK_STAMP(a, i) do { } while (0)
-#endif
 
 // cache modifier of the planar hidden stores: they are streamed (gigabytes per launch, read back by the weight-gradient GEMMs after the
 // level's sweep), so non-temporal -- measured -1.7 % on a 256-tile parameter-gradient sweep against "" on one box, neutral at 32 tiles
-#ifndef GLOWK_ST_MOD
 #define GLOWK_ST_MOD " nt"
-#endif
 // planar store of one 32 x 32 accumulator tile of a hidden block (16 registers per lane: rows 0-3, 8-11, 16-19, 24-27, + 4 for the
 // upper lane half) into a [F][Q] array.  The block base is wave-uniform (SGPR pair), the lane's part a running 32-bit byte
 // offset: global_store_dword voffset, data, saddr.  Written as asm because hipcc turns the C form into sixteen hoisted
@@ -479,12 +471,6 @@ __global__ __launch_bounds__(256, 1) void k_net_f32(NetArgs a) {
 // during the Z ops as soon as their slot is free; the last Z op of a pass requests the next pass's first chunks.
 // ------------------------------------------------------------------------------------------------------------------
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-// Activation scale before the fp16 split.  Overflow (a hidden activation above 65504 / scale) turns into inf/NaN, underflow only
-// costs the low bits of activations below ~6e-5 / scale * 2^11: 4 leaves |activation| < 16 376 with activations down to 0.03
-// fully split; log_prob accuracy measured identical for 1, 4 and 32 (scripts/act_scale_probe.py).
-#ifndef GLOWK_ACT_SCALE
-#define GLOWK_ACT_SCALE 4.0f
-#endif
 
 // KIN = input channels of the small 3x3 convolution (c/2 forward: conv1; c backward: conv3^T), MOUT = rows of the per-tap
 // output (18 ci forward: conv3; 9 ci backward: conv1^T), MODE as for k_net_f32.
@@ -588,14 +574,6 @@ __device__ __forceinline__ float pixel_norm(float m, float target, float& undo) 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo) {
-#ifdef GLOWK_SPLIT_SCALAR   // (A/B builds only, scripts/ab.py: round 1's element-wise form)
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    hi[j] = (_Float16)v[j];
-    lo[j] = (_Float16)(v[j] - (float)hi[j]);
-  }
-  return;
-#endif
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
     const f32x2 p = {v[j], v[j + 1]};
@@ -652,9 +630,7 @@ __device__ __forceinline__ void gather8(const float* base, int i, int j0, int h,
 // The waits are builtins so that the compiler's own wait-count bookkeeping sees them.
 __device__ __forceinline__ void h3_barrier() {
   asm volatile("" ::: "memory");
-#ifndef GLOWK_EXP_NOBARRIER   // (diagnostic build, racy on purpose: what do the phase barriers cost?)
   __builtin_amdgcn_s_barrier();
-#endif
   asm volatile("" ::: "memory");
 }
 __device__ __forceinline__ void h3_wait_barrier() {
@@ -704,9 +680,6 @@ __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned
         }
       }
     }
-#ifdef GLOWK_EXP_NOHST
-    do_st = false;
-#endif
     if ((MODE & 8) && do_st) {
       unsigned off = st_lane + (unsigned)(16 * s) * st_row;      // rows 8 (r >> 2) + (r & 3): registers 8 s .. 8 s + 7 = rows 16 s + {0..3, 8..11}
 #pragma unroll
@@ -744,13 +717,6 @@ template <int KIN, int MOUT, int NF, int MODE, int NP, int KP, int PASS>
 __device__ __forceinline__ void h3_X(const NetArgs& a, const H3Ctx& c, int fi, const h8 (&xh)[(RingH<KIN, MOUT, NF, MODE, NP>::KS)],
                                      const h8 (&xl)[(RingH<KIN, MOUT, NF, MODE, NP>::KS)], int lane, h8 (&bh)[2], h8 (&bl)[2]) {
   using G = RingH<KIN, MOUT, NF, MODE, NP>;
-#ifdef GLOWK_EXP_NOX   // (diagnostic build, wrong results: X does nothing -- what do conv1 and its epilogue cost a phase?)
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { bh[s][j] = (_Float16)0.0f; bl[s][j] = (_Float16)0.0f; }
-  return;
-#endif
   f32x16 h1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) h1[r] = 0.0f;
@@ -1105,9 +1071,6 @@ struct RingS {
   static constexpr int IMG_PASS4 = (NF + IMG_NCH) * IMG_MAIN4;
   static constexpr int SUBS = NP / 2;
   __device__ static const float4* main_chunk(const float4* img, int pass, int ch) {
-#ifdef GLOWK_EXP_SAMECHUNK   // (diagnostic build, wrong results: every weight DMA reads the same 32 KiB -- is the weight stream's L2 / HBM latency on the critical path?)
-    ch = 0;
-#endif
     return img + K1TOT4 + (size_t)(pass / SUBS) * IMG_PASS4 + (size_t)ch * IMG_MAIN4 + (size_t)(pass % SUBS) * MAIN4;
   }
   __device__ static const float4* out_chunk(const float4* img, int pass, int s) {   // conv3 chunk s of a pass (TPC tiles)
@@ -1122,15 +1085,11 @@ struct RingS {
   // time) pass 0 keeps its partial sums in 24 registers and pass 1 adds them before the only store.  (Diagnostic builds: the P
   // stores are ~10 % of the kernel's time -- skipping two thirds of them made a pass 7 % faster -- so half of them is worth having;
   // the consumer reads one partial buffer instead of two.)  Plain forward modes only: the saving pass keeps its two buffers.
-#ifdef GLOWK_NO_MERGE   // (A/B builds only, scripts/ab.py)
-  static constexpr bool MERGE = false;
-#else
   static constexpr bool MERGE = PXH == 2 && NP == 2 && NGRP == 1 && NMT <= 3 &&
                                 ((MODE & 7) == NET_FWD || (MODE & 7) == NET_FWD2 || ((MODE & 7) == NET_BWD && NMT <= 2) || ((MODE & 7) == NET_FWD_SAVE && FUSE));   // (the saving pass keeps no P
                                 // any more -- the coupling's pre-tanh inputs are what the backward pass reads -- so it can take the fused form too;
                                 // the 4-channel level's backward network (18 output rows: 16 registers) merges its two passes as well, the 8-channel
                                 // one (36 rows: 24 registers) spills 18 registers if it does)
-#endif
 };
 
 template <bool TWO = false>
@@ -1171,9 +1130,6 @@ __device__ __forceinline__ unsigned h3s_act(const f32x4& r0, const f32x4& r1, fl
   float v[8];
   const unsigned bits = h3s_act_vals<MODE>(r0, r1, sc, mask8, v);
   if constexpr (ST) {
-#ifdef GLOWK_EXP_NOHST      // (diagnostic build, wrong weight gradients: the hidden tensors are not stored -- what do the stores cost a training launch?)
-    do_st = false;
-#endif
     if (do_st) {
       const unsigned long long st_base = reinterpret_cast<unsigned long long>(st_blk);
 #pragma unroll
@@ -1202,7 +1158,6 @@ __device__ __forceinline__ unsigned h3s_act_pair(const f32x4& r00, const f32x4& 
   //  per wave and 8-byte wave store -- scripts/store_rate_probe.hip.  Issuing the stores two at a time between the conversions below
   //  changed nothing, docs/EXPERIMENTS.md round 4.)
   if constexpr (ST) {
-#ifndef GLOWK_EXP_NOHST
     const unsigned long long st_base = reinterpret_cast<unsigned long long>(st_blk);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -1210,7 +1165,6 @@ __device__ __forceinline__ unsigned h3s_act_pair(const f32x4& r00, const f32x4& 
       const f32x2 pr = {v0[j], v1[j]};
       asm volatile("global_store_dwordx2 %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(pr), "s"(st_base) : "memory");
     }
-#endif
   }
   split8(v0, bh[0], bl[0]);
   split8(v1, bh[1], bl[1]);
@@ -1258,15 +1212,8 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
     static_assert(G::PXH == 2, "pairs: two pixel halves per wave");
     const int stq = (int)c.wblk * 32 + 2 * (lane & 15);
     if constexpr ((MODE & 8) && PASS == 0)
-#ifdef GLOWK_EXP_TILEDST   // (diagnostic builds, wrong weight gradients: the stores of a workgroup land in ONE contiguous [F][128] block -- do the 1-MB row
-                           //  strides cost?  GLOWK_EXP_TILEDST = 0: every hidden block of a workgroup lands on the SAME 16 KB -- does the path behind L2?)
-      bits = h3s_act_pair<(MODE & 7), true>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl,
-                                            uniform_fptr(a.st1 + ((size_t)blockIdx.x * NF * 32 + (size_t)fi * 32 * GLOWK_EXP_TILEDST) * 128),
-                                            ((unsigned)(4 * (lane >> 4)) * 128u + (unsigned)(stq & 127)) * 4u, 128u * 4u);
-#else
       bits = h3s_act_pair<(MODE & 7), true>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q),
                                             ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u);
-#endif
     else bits = h3s_act_pair<(MODE & 7), false>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, nullptr, 0u, 0u);
   } else {
 #pragma unroll
@@ -1291,9 +1238,6 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
   const char* mb = uniform_ptr(main_src);
   constexpr int NG = G::NRB / 2;
   constexpr int PPG = G::MAINP / 4 / NG;            // DMA pieces per wave and group
-#ifdef GLOWK_EXP_YPRIO   // (A/B build: the wave in its matrix phase outranks its SIMD partner, which is in the VALU-heavy X phase)
-  __builtin_amdgcn_s_setprio(1);
-#endif
   h8 A[2][4];
   auto load = [&](h8 (&d)[4], int gi) {
     d[0] = buf[((2 * gi) * 2 + 0) * 64];            // row block 2gi hi, lo; row block 2gi+1 hi, lo
@@ -1305,11 +1249,7 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) {
     const int o0 = 2 * gi, o1 = 2 * gi + 1;
-#ifdef GLOWK_EXP_SAMEFRAG   // (diagnostic build, wrong results: every group reuses the first group's A fragments -- what do Y's LDS reads cost?)
-    if (gi == 0) load(A[1], 1);
-#else
     if (gi + 1 < NG) load(A[(gi + 1) & 1], gi + 1);
-#endif
     if (!g) {
       if (main_ok) {
 #pragma unroll
@@ -1340,9 +1280,6 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
     if constexpr (G::PXH == 2) acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
-#ifdef GLOWK_EXP_YPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Z: conv3 op z of a pass = half a chunk of A tiles (16 rows x one hidden block)
@@ -1405,9 +1342,6 @@ __device__ __forceinline__ void h3s_Z(const NetArgs& a, const H3Ctx& c, const fl
               if (m < M3) c.pl[m * FUSE_PSTR + (int)(threadIdx.x >> 6) * 32 + 16 * hf + (lane & 15)] = val + keep[ml][hf][r];
               continue;
             }
-#ifdef GLOWK_EXP_NOSTORE   // (diagnostic build, wrong results: only one row tile of P is written -- what do the P stores cost?)
-            if (mt == 0)
-#endif
             if (m < M3 && qok[hf]) Pp[(size_t)m * a.Q + q[hf]] = MERGE ? val + keep[ml][hf][r] : val;
           }
       }
@@ -1510,12 +1444,8 @@ __device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, 
   ot += a.fz_b3[2 + k];
   float lsum = 0.0f;
   // (the partner lane l ^ 32 holds the other channel pair of the SAME pixel: the two take identical branches)
-#ifdef GLOWK_EXP_VGLOBAL   // (diagnostic build: the tail reads the coupling input from global memory, not from the LDS stash)
-  const float4 v4 = qok ? *reinterpret_cast<const float4*>(a.vin + (size_t)q * 4) : float4{0.f, 0.f, 0.f, 0.f};
-#else
   const float4 v4 = vst[px];          // the pixel's four input channels, parked in LDS by the prologue (a global load here would be
                                       // a full memory latency on the workgroup's serial tail: nothing else runs on this CU)
-#endif
   const float vk = k ? v4.y : v4.x;
   const float log_s = tanhf(ols);
   const float sc = expf(log_s);
@@ -1681,9 +1611,6 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
   __syncthreads();
 
   f32x4 keep[G::G0N][2];     // pass 0's partial sums of P (RingS::MERGE; otherwise never touched and compiled away)
-#ifdef GLOWK_EXP_STATICPRIO   // (A/B build: the younger half of the workgroup -- group 1 -- outranks its SIMD partners for good)
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
   if (g) h3_barrier();
   if constexpr (SPLIT) {
     if (solo_pass == 0) h3s_pass<KIN, MOUT, NF, MODE, NP, 0, 0, true>(a, c, epl, xh, xl, g, q, qok, lane, kq, keep);

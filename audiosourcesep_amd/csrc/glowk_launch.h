@@ -17,29 +17,21 @@ void note_co();                         // ... and that it took the co-resident 
 void note_q();                          // ... or the small-grid form with all conv1 blocks first (glowk_q.h)
 void note_family(int family);           // which kernel family a (non-dry) launch took: 0 k_net_f32, 1 k_net_h3 (32x32x16), 2 k_net_h3s
                                         // (16x16x32), 3 its half-wave form, 4 the fused network + coupling kernel; glowk.hip
-bool h3_shape16();                      // GLOWK_H3_SHAPE=32 keeps the forward pass on the 32x32x16 kernel (A/B timing); glowk.hip
 void launch_fail(const std::string&);   // sets glowk_last_error(); glowk.hip
 
-// Diagnostic switches (A/B timing, parity tests of one launch form against another): environment variables, read ONCE -- when the
-// library is loaded and again by glowk_reload_env() -- not per launch (round-3 verdict: six getenv() scans per flow step sat on the
-// latency-bound path, ~1 200 per 30-tile gradient call).  glowk.hip owns the instance.
+// Switches (parity tests of one launch form against another): environment variables, read ONCE -- when the library is loaded and
+// again by glowk_reload_env() -- not per launch (round-3 verdict: six getenv() scans per flow step sat on the latency-bound path,
+// ~1 200 per 30-tile gradient call).  glowk.hip owns the instance.
 struct EnvSwitches {
-  bool half_off;            // GLOWK_HALF_OFF: never the half-wave form where another one exists
-  bool half_force;          // GLOWK_HALF_FORCE: the half-wave form of the plain forward network at every grid size
-  bool fam16_small;         // GLOWK_FAM16_SMALL: the 16x16x32 family of the gradient path at every grid size
   bool bwd_light_4;         // GLOWK_BWD_LIGHT_4: k_bwd_light with four lanes per pixel whatever the grid
-  bool couple_per_sample;   // GLOWK_COUPLE_PER_SAMPLE: k_couple (one workgroup per sample) instead of the flat grid
-  bool couple_4;            // GLOWK_COUPLE_4: k_couple_flat with four lanes per pixel whatever the level
   bool no_fuse;             // GLOWK_NO_FUSE: network + coupling as two kernels at the 4-channel level
   bool wgrad_plain;         // GLOWK_WGRAD_PLAIN: the weight-gradient GEMM's plain (not fenced) round
-  bool wgrad_128;           // GLOWK_WGRAD_128: 128 x 128 tiles in the exact weight-gradient GEMM
   bool co_off;              // GLOWK_CO_OFF: never the co-resident (two workgroups per CU) form of the forward network
   bool q_off;               // GLOWK_Q_OFF: never the all-conv1-first small-grid form (glowk_q.h)
-  bool co_split_off;        // GLOWK_CO_SPLIT_OFF: never the one-pass-per-workgroup (small-grid) form of k_net_h3c
-  bool co_train_off;        // GLOWK_CO_TRAIN_OFF: the training sweep stays on the 32x32x16 family (A/B timing)
-  bool wgrad_16_off;        // GLOWK_WGRAD_16_OFF: no 16-wave / 256 x 256 form of the split weight-gradient GEMM (A/B timing)
-  bool co8_off;             // GLOWK_CO8_OFF: no co-resident form at the 8-channel level (A/B timing)
-  bool co_mid_off;          // GLOWK_CO_MID_OFF: the co-resident form only on grids of >= 4 workgroups per CU (or <= 1: SPLIT), as first built
+  bool co_train_off;        // GLOWK_CO_TRAIN_OFF: the training sweep stays on the 32x32x16 family
+  bool train_recompute;     // GLOWK_TRAIN_RECOMPUTE: the training sweep recomputes each step's forward pass instead of keeping it
+  bool train_perstep;       // GLOWK_TRAIN_PERSTEP: one saving forward launch per step instead of the level's chain
+  bool pg_join;             // GLOWK_PG_JOIN: glowk_param_grad joins the caller's stream on the host first, as before the side stream
 };
 const EnvSwitches& env();
 
@@ -87,6 +79,7 @@ inline bool co_two_per_cu(Kernel kernel) {
 
 template <int KIN, int MOUT, int NF, int MODE>
 int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
+  static_assert(!(MODE & 8), "no storing launches here: the co-resident branch does not check Q % 128 (co_train does)");
   constexpr bool F2 = RingS<KIN, MOUT, NF, MODE, 2>::FITS, F4 = RingS<KIN, MOUT, NF, MODE, 4>::FITS;
   const int wgs = (a.Q + 255) / 256, cus = num_cus();
   if constexpr (F4) {
@@ -110,11 +103,11 @@ int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
     // level) or writing P once (1) --, on small grids (2 x Q/128 workgroups fit two to a CU) one pass per workgroup (2 partial P buffers)
     if constexpr (RingC<KIN, MOUT, NF, MODE>::FITS) {
       const int wgc = (a.Q + CO_PX - 1) / CO_PX;
-      const bool co_ok = a.co && !env().co_off && !(RingC<KIN, MOUT, NF, MODE>::NMT == 5 && env().co8_off);
+      const bool co_ok = a.co && !env().co_off;
       // (grids in between -- more 128-pixel workgroups than CUs, fewer than four per CU, e.g. BASIS' 30 mixture tiles at the reference's
       //  96 x 64: the eight-wave kernel would run one two-pass workgroup on 70 % of the CUs; this form runs its workgroups two to a CU in
-      //  one round up to 2 x CUs, two rounds up to 4 x CUs.  GLOWK_CO_MID_OFF: the round-4 rule "four per CU or none", for A/B timing)
-      if (co_ok && (wgc >= 4 * cus || (wgc > cus && !env().co_mid_off))) {
+      //  one round up to 2 x CUs, two rounds up to 4 x CUs)
+      if (co_ok && wgc > cus) {
         if constexpr (RingC<KIN, MOUT, NF, MODE | 16>::FITS) {
           // (the form only pays with TWO workgroups per CU -- 2 x 78.8 KB of LDS, 2 x 4 x 248 VGPRs: ask the runtime once per instance, and
           //  keep the eight-wave kernel where a driver / device leaves room for one)
@@ -128,7 +121,7 @@ int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
           return RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2;
         }
       }
-      if (co_ok && !env().co_split_off && split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
+      if (co_ok && split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
         if (!dry) { hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a); note_family(2); note_co(); }
         return 2;
       }
@@ -155,10 +148,7 @@ int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
 // workgroups at half the work per phase: chosen where the 256-pixel workgroups with their passes as workgroups of their own
 // still leave half the CUs idle (latency-bound grids: the deeper levels at the reference's batch sizes of 30 / 32 tiles), and for
 // shapes whose small-conv fragments only fit the registers at one half per wave (the 32-channel level's backward network: K = 288).
-inline bool half_wave_grid(const NetArgs& a) {
-  if (env().half_off) return false;                 // (A/B timing and diagnostics)
-  return 8 * ((a.Q + 255) / 256) <= num_cus();
-}
+inline bool half_wave_grid(const NetArgs& a) { return 8 * ((a.Q + 255) / 256) <= num_cus(); }
 
 template <int KIN, int MOUT, int NF, int MODE>
 int launch_h3s_half(const NetArgs& a, hipStream_t s, bool dry) {
@@ -207,13 +197,13 @@ constexpr bool half_train_only() {
 template <int CI, int NF>
 inline bool use_half_train(const NetArgs& a) {
   if constexpr (!half_train_ok<CI, NF>()) return false;
-  return a.fam16 && h3_shape16() && a.max_np >= 4 && (half_train_only<CI, NF>() || half_wave_grid(a));
+  return a.fam16 && a.max_np >= 4 && (half_train_only<CI, NF>() || half_wave_grid(a));
 }
 
 template <int CI, int NF>
 inline bool use_half(const NetArgs& a) {
   if constexpr (!half_ok<CI, NF>()) return false;
-  return a.fam16 && h3_shape16() && a.max_np >= 4 && (half_only<CI, NF>() || half_wave_grid(a));
+  return a.fam16 && a.max_np >= 4 && (half_only<CI, NF>() || half_wave_grid(a));
 }
 
 // a level's saving forward pass and its backward pass run in ONE kernel family (their ReLU-mask layouts differ): the
@@ -221,9 +211,9 @@ inline bool use_half(const NetArgs& a) {
 // for four partial buffers, which the save buffers may not have)
 // ... and only where the grid fills the chip (measured: +3.3 % at 1024 tiles, -2.5 % at 30, where the launches are split
 // into passes and latency-bound).  Both launches of a level see the same pixel count, so they decide alike.
-// (re-measured in round 3 with GLOWK_FAM16_SMALL=1 -- the 16x16x32 family at every grid size: 8.72 vs 8.72 ms for the gradient of 30
-//  tiles, within +-1 % at 8 ... 128 tiles: no reason to change the rule the fuzz runs validated)
-inline bool big_grid(const NetArgs& a) { return 2 * ((a.Q + 255) / 256) > num_cus() || env().fam16_small; }
+// (re-measured in round 3 with the 16x16x32 family at every grid size: 8.72 vs 8.72 ms for the gradient of 30 tiles, within +-1 % at
+//  8 ... 128 tiles: no reason to change the rule the fuzz runs validated)
+inline bool big_grid(const NetArgs& a) { return 2 * ((a.Q + 255) / 256) > num_cus(); }
 
 // ... or where both launches take the one-pass-per-workgroup co-resident form (k_net_h3c<..., SPLIT>: four-wave workgroups two to a CU
 // instead of one eight-wave pass-workgroup per CU): the same question for the saving and the backward launch of a level, same answer
@@ -231,7 +221,7 @@ template <int CI, int NF>
 inline bool co_split_grad(const NetArgs& a) {
   if constexpr (RingC<CI, 18 * CI, NF, NET_FWD_SAVE>::FITS && RingC<2 * CI, 9 * CI, NF, NET_BWD>::FITS) {
     const int wgc = (a.Q + CO_PX - 1) / CO_PX, cus = num_cus();
-    return a.co && !env().co_off && !env().co_split_off && a.fam16 && h3_shape16() && a.max_np >= 2 && 2 * ((a.Q + 255) / 256) <= cus && wgc <= cus &&
+    return a.co && !env().co_off && a.fam16 && a.max_np >= 2 && 2 * ((a.Q + 255) / 256) <= cus && wgc <= cus &&
            co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, NET_FWD_SAVE, true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, NET_BWD, true>);
   }
   return false;
@@ -239,17 +229,16 @@ inline bool co_split_grad(const NetArgs& a) {
 
 // The training sweep of a level in the co-resident form (k_net_h3c<..., MODE | 8>: the launches also store their hidden tensors): where
 // both the saving forward and the backward network have an instance, every workgroup is full (the kernels count their stores: Q % 128
-// == 0) and the grid is one of the two the form is built for -- >= 4 workgroups per CU with both passes in a workgroup, or <= 1 per CU
-// with a workgroup per pass.  Same question, same answer for the two launches of a level (their ReLU-mask layouts must agree).
+// == 0): more workgroups than CUs with both passes in a workgroup, otherwise a workgroup per pass.  Same question, same answer for
+// the two launches of a level (their ReLU-mask layouts must agree).
 template <int CI, int NF>
 inline bool co_train(const NetArgs& a) {
   if constexpr (RingC<CI, 18 * CI, NF, (NET_FWD_SAVE | 8)>::FITS && RingC<2 * CI, 9 * CI, NF, (NET_BWD | 8)>::FITS) {
     const int wgc = (a.Q + CO_PX - 1) / CO_PX, cus = num_cus();
-    if (!(a.co && !env().co_off && !env().co_train_off && a.fam16 && h3_shape16() && a.Q % CO_PX == 0 && a.max_np >= 2)) return false;
-    if (wgc >= 4 * cus || (wgc > cus && !env().co_mid_off))
+    if (!(a.co && !env().co_off && !env().co_train_off && a.fam16 && a.Q % CO_PX == 0 && a.max_np >= 2)) return false;
+    if (wgc > cus)
       return co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), false>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, (NET_BWD | 8), false>);
-    if (wgc <= cus && !env().co_split_off)
-      return co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, (NET_BWD | 8), true>);
+    return co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, (NET_BWD | 8), true>);
   }
   return false;
 }
@@ -301,22 +290,21 @@ int launch_net_t(const NetArgs& a, int mode, hipStream_t s, bool dry) {
       break;
     case 9:            if (!dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD_SAVE, true>), dim3(ntiles), dim3(256), 0, s, a); break;   // saving forward pass that keeps its hiddens
     case 3:   // f16x3 arithmetic: forward / forward with saves / backward; shapes without an instance run the exact fp32 kernel
-      // (GLOWK_HALF_FORCE=1: the half-wave form at every grid size -- two 128-pixel workgroups per CU; an experiment)
-      if (a.RSp && h3_shape16() && ((half_wave_grid(a) && !a.fuse) || env().half_force)) np = launch_h3s_half<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && a.RSp && h3_shape16()) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+      if (a.RSp && half_wave_grid(a) && !a.fuse) np = launch_h3s_half<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+      if (!np && a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
       if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
       if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD>), dim3(ntiles), dim3(256), 0, s, a);
       break;
     case 6:   // two-term forward (GLOWK_PREC_F16X2): 16x16x32 kernel only; without an instance, the three-term forms of case 3
-      if (a.RSp && h3_shape16()) np = launch_h3s<CI, 18 * CI, NF, NET_FWD2>(a, s, dry);
-      if (!np && a.RSp && h3_shape16()) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+      if (a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD2>(a, s, dry);
+      if (!np && a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
       if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
       if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD>), dim3(ntiles), dim3(256), 0, s, a);
       break;
     case 4:
       if (use_half<CI, NF>(a)) np = launch_h3s_half<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
       if constexpr (fam16_ok<CI, NF>()) {
-        if (!np && a.fam16 && h3_shape16() && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
+        if (!np && a.fam16 && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
       }
       if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
       if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD_SAVE>), dim3(ntiles), dim3(256), 0, s, a);
@@ -324,7 +312,7 @@ int launch_net_t(const NetArgs& a, int mode, hipStream_t s, bool dry) {
     case 5:
       if (use_half<CI, NF>(a)) np = launch_h3s_half<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
       if constexpr (fam16_ok<CI, NF>()) {
-        if (!np && a.fam16 && h3_shape16() && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
+        if (!np && a.fam16 && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
       }
       if (!np && a.RHp) np = launch_h3<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
       if (!np && !dry) hipLaunchKernelGGL((k_net_f32<2 * CI, 9 * CI, NF, NET_BWD>), dim3(ntiles), dim3(256), 0, s, a);

@@ -4,6 +4,7 @@
 // -fsanitize=thread (tests/test_pack_sanitizers.py).
 #pragma once
 #include "../../include/glowk.h"
+#include "glowk_act_scale.h"
 
 #include <algorithm>
 #include <atomic>
@@ -12,10 +13,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-
-#ifndef GLOWK_ACT_SCALE
-#define GLOWK_ACT_SCALE 4.0f   // activation scale before the fp16 split (glowk_kernels.h has the rationale)
-#endif
 
 #ifndef __HIP__
 struct float4;   // (device vector type; only pointers to it appear here -- a host-only build has no HIP headers)

@@ -14,7 +14,7 @@
 // ends with counted vmcnt + lgkmcnt(0) + raw barrier (glowk_co.h: the rule for DMA that spans barriers).  Same weight images, same
 // per-accumulator MFMA order as the half-wave form: results are bit for bit equal (tests/test_gpu_small_grid_form.py).
 //
-// What it measured (in-kernel stamps, glowk_debug_stamps / scripts/q_stamps.py, 30 tiles, level 1 forward): prologue 2.4 us, X halves
+// What it measured (in-kernel time stamps, 30 tiles, level 1 forward): prologue 2.4 us, X halves
 // 2.6 + 2.2, Y halves 5.7 + 5.6, Z 2.8 = 21.7 us in the kernel (half-wave form: ~26).  The Y halves do not move whatever the barrier
 // count or the MFMA order: 0.65 us per k-step is the LDS -- at one pixel half per wave every wave reads the whole 16-KiB chunk for its
 // 24 MFMAs, 128 KiB per k-step and CU against 768 MFMA cycles, i.e. 130 % of the LDS bandwidth (the half-wave form's known price).
@@ -226,23 +226,17 @@ __device__ __forceinline__ void q_pass(const NetArgs& a, const H3Ctx& c, const Q
       acc2[ob][0][r] = b;
       acc2[ob][1][r] = b;
     }
-  GLOWK_STAMP(a, 2);
   q_X_all<KIN, MOUT, NF, MODE, PASS, 0>(a, c, sl, xh, xl, g, lane, bfh, bfl, std::make_integer_sequence<int, G::NB / 2>());
-  GLOWK_STAMP(a, 3);
   q_Y_all<KIN, MOUT, NF, MODE, PASS, 0>(c, sl, bfh, bfl, acc2, g, lane, std::make_integer_sequence<int, NF / 4>());
-  GLOWK_STAMP(a, 6);
   q_X_all<KIN, MOUT, NF, MODE, PASS, G::NB / 2>(a, c, sl, xh, xl, g, lane, bfh, bfl, std::make_integer_sequence<int, G::NB / 2>());
   if constexpr (G::BWD) {                    // mask2 is done with: the same buffer takes mask1 (read by the Z ops, many barriers from here)
     if (!g) stage4<NF, 86>(reinterpret_cast<const float4*>(a.mask1 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(sl.mk), c.w4, c.voff);
   }
-  GLOWK_STAMP(a, 7);
   q_Y_all<KIN, MOUT, NF, MODE, PASS, NF / 4>(c, sl, bfh, bfl, acc2, g, lane, std::make_integer_sequence<int, NF / 4>());
-  GLOWK_STAMP(a, 4);
   f32x4 acc3[S::G0N][2];
   f32x4 keep[S::G0N][2];                     // (never touched: a solo pass writes its own partial P)
   h8 bh[2], bl[2];
   h3s_tail<KIN, MOUT, NF, MODE | 32, 4, 0, PASS, true>(a, c, epl, acc2, acc3, bh, bl, g, q, qok, lane, kq, keep, std::make_integer_sequence<int, 2 * S::NCH>());
-  GLOWK_STAMP(a, 5);
 }
 
 // grid (workgroups of 128 pixels, 4 passes); each workgroup runs ONE pass
@@ -267,7 +261,6 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
   __shared__ __attribute__((aligned(1024))) unsigned short mkl[G::MASKB / 2 + 8];
 
   const int tid = threadIdx.x;
-  GLOWK_STAMP(a, 0);
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2;
@@ -349,7 +342,6 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
   if (a.xmax_out) range_probe(a.xmax_out, xmax);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  GLOWK_STAMP(a, 1);
 
   if (pass == 0) q_pass<KIN, MOUT, NF, MODE, 0>(a, c, sl, epl, xh, xl, g, q, qok, lane, kq);
   else if (pass == 1) q_pass<KIN, MOUT, NF, MODE, 1>(a, c, sl, epl, xh, xl, g, q, qok, lane, kq);

@@ -252,9 +252,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN >= 8 ? 1 : 2) void k_wgrad_h3
   const bool full = VEC && m0 + TM <= a.M && n0 + TN <= a.N && ((k_end - k_begin) & 31) == 0;
   auto load4 = [&](auto full_tag, const float* base, int row, int rows, long k) -> float4 {
     float4 v = {0.f, 0.f, 0.f, 0.f};
-#ifdef WGRAD_EXP_NOLOAD  // (diagnostic build: no global loads)
-    return v;
-#endif
     if constexpr (decltype(full_tag)::value) {
       v = *reinterpret_cast<const float4*>(base + (size_t)row * a.K + k);
     } else if constexpr (VEC) {   // unconditional load from a clamped address, then select (no branch around the load)
@@ -281,14 +278,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN >= 8 ? 1 : 2) void k_wgrad_h3
   typedef _Float16 h4v __attribute__((ext_vector_type(4)));
   auto put = [&](auto unit_tag, const float4& v, float sc, _Float16* hi, _Float16* lo, int row) {
     constexpr bool UNIT = decltype(unit_tag)::value;    // scale 1: no multiply
-#ifdef WGRAD_EXP_NOSTAGE // (diagnostic build: no LDS writes at all -- fragment reads, MFMAs and barriers alone)
-    return;
-#endif
-#ifdef WGRAD_EXP_NOCVT   // (diagnostic build, wrong numbers on purpose: what does the conversion cost?  same bytes through the same path)
-    *reinterpret_cast<float2*>(hi + row * LDH + lk) = make_float2(v.x, v.y);
-    *reinterpret_cast<float2*>(lo + row * LDH + lk) = make_float2(v.z, v.w);
-    return;
-#endif
     const f32x2 p0 = {UNIT ? v.x : v.x * sc, UNIT ? v.y : v.y * sc}, p1 = {UNIT ? v.z : v.z * sc, UNIT ? v.w : v.w * sc};
     const h2v h0 = __builtin_convertvector(p0, h2v), h1 = __builtin_convertvector(p1, h2v);
     const f32x2 d0 = p0 - __builtin_convertvector(h0, f32x2), d1 = p1 - __builtin_convertvector(h1, f32x2);

@@ -2,7 +2,6 @@
 // the device-side refresh of the kernel images -- glowk_param_vector_size / glowk_param_offset / glowk_param_grad / glowk_apply_gradients
 // (train_glow.py:29-44, train_utils.py:23-41).  The sweep itself (run_forward / run_backward) lives in glowk.hip.
 #include "glowk_engine.h"
-#include <chrono>
 #include "glowk_train.h"
 
 using namespace glowk_eng;
@@ -110,7 +109,7 @@ int ensure_train(glowk_handle* h, int N) {
         per_tile += 2 * F * (size_t)h->levels[lvl].h * h->levels[lvl].w;
       }
     size_t free_b = 0, tot_b = 0;
-    if (hipMemGetInfo(&free_b, &tot_b) == hipSuccess && per_tile * N * 4 <= free_b / 4 && !getenv("GLOWK_TRAIN_RECOMPUTE")) {
+    if (hipMemGetInfo(&free_b, &tot_b) == hipSuccess && per_tile * N * 4 <= free_b / 4 && !glowk_detail::env().train_recompute) {
       HIPCHK(hipMalloc(&h->trKeep, per_tile * N * 4));
       h->trKeepN = N;
     }
@@ -118,7 +117,7 @@ int ensure_train(glowk_handle* h, int N) {
   // a level at a time (trNB = K): M1 / M2, g_o, g_v and the im2col arrays of all K steps of the largest level -- with R1 / R2 kept and
   // a third of what is then free; GLOWK_TRAIN_PERSTEP=1 forces the step-by-step path (both are tested)
   h->trNB = 1;
-  if (h->trKeep && K > 1 && !getenv("GLOWK_TRAIN_PERSTEP")) {
+  if (h->trKeep && K > 1 && !glowk_detail::env().train_perstep) {
     bool uniform = true;
     for (const Level& lv : h->levels) uniform = uniform && level_uniform(lv);
     const size_t extra = (K * (2 * F * qmax + xcol + gcol + 2 * gv)) * 4;
@@ -150,15 +149,14 @@ int ensure_train(glowk_handle* h, int N) {
 // the split GEMM, by a k_rowsum pass after the exact one.
 int launch_wgrad(glowk_handle* h, bool split, const float* A, ptrdiff_t bsA, int M, const float* B, ptrdiff_t bsB, int N, int K, int nb, float sa, float sb,
                  float* C, size_t csC, bool b_sums, hipStream_t s) {
-  const bool big = split ? N >= 256 : (M >= 256 && N >= 256 && glowk_detail::env().wgrad_128);   // (fp32: 128 x 128 tiles measured 5 % slower than 64 x 64)
-  const bool big8 = split && big && M % 256 == 0;   // 8 waves, 256 x 128: a quarter less staging per MFMA (254 -> 290 TFLOP/s on the level-0 conv2 batch)
+  const bool big = split && N >= 256;                  // (fp32: 64 x 64 tiles; 128 x 128 measured 5 % slower)
+  const bool big8 = big && M % 256 == 0;   // 8 waves, 256 x 128: a quarter less staging per MFMA (254 -> 290 TFLOP/s on the level-0 conv2 batch)
   // 16 waves, 256 x 256 (square shapes: the conv2 gradient): 2/3 of the 8-wave form's staged bytes per MFMA -- staging is what bounds these
   // GEMMs --, 128 registers per wave (one k-step's fragments at a time): 332 -> 373 TFLOP/s on the level-0 batch of a 256-tile step
-  const bool big16 = big8 && N % 256 == 0 && (K & 3) == 0 && !glowk_detail::env().wgrad_16_off;
-  const int TM = big8 ? 256 : split ? 128 : big ? 128 : 64, TN = big16 ? 256 : split ? (big ? 128 : 64) : TM;
+  const bool big16 = big8 && N % 256 == 0 && (K & 3) == 0;
+  const int TM = big8 ? 256 : split ? 128 : 64, TN = big16 ? 256 : big ? 128 : 64;
   const int tm = (M + TM - 1) / TM, tn = (N + TN - 1) / TN, tiles = tm * tn;
-  static const int wg_env = getenv("GLOWK_WGRAD_WGS") ? atoi(getenv("GLOWK_WGRAD_WGS")) : 0;   // workgroups per CU the split aims at
-  const int wg_per_cu = wg_env > 0 ? wg_env : big8 ? 1 : 2;                                       // (what fits a CU: 1 of the 8-wave form)
+  const int wg_per_cu = big8 ? 1 : 2;                  // workgroups per CU the split aims at (what fits a CU: 1 of the 8-wave form)
   int S = std::max(1, std::min((wg_per_cu * num_cus() + tiles * nb - 1) / (tiles * nb), (K + 255) / 256));
   const bool in_gemm = b_sums && split;
   const size_t n = (size_t)(M + (in_gemm ? 1 : 0)) * N;
@@ -187,9 +185,7 @@ int launch_wgrad(glowk_handle* h, bool split, const float* A, ptrdiff_t bsA, int
     a.A = A; a.B = B; a.M = M; a.N = N; a.a_ones = 0; a.K = K; a.kslice = kslice; a.Cpart = out; a.S = S; a.tm = tm; a.tn = tn; a.bsA = bsA; a.bsB = bsB;
     a.csz = csz;
     const dim3 grid((unsigned)(tiles * S * nb));
-    if (big && vec) hipLaunchKernelGGL((k_wgrad_nt<2, true>), grid, dim3(256), 0, s, a);
-    else if (big) hipLaunchKernelGGL((k_wgrad_nt<2, false>), grid, dim3(256), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((k_wgrad_nt<1, true>), grid, dim3(256), 0, s, a);
+    if (vec) hipLaunchKernelGGL((k_wgrad_nt<1, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_wgrad_nt<1, false>), grid, dim3(256), 0, s, a);
     LAUNCHCHK("k_wgrad_nt");
   }
@@ -221,8 +217,7 @@ int train_network_grads(glowk_handle* h, TrainCtx* tc, int lvl, int k0, int nb, 
   LAUNCHCHK("k_im2col_planar");
   // (2) the three GEMMs over the pixel dimension.  A split sweep left R / M in the units its kernels split them in; the im2col
   //     arrays take the scale of those kernels' own gathers.  Row F of C3 = the row sums of Gcol, row F of C2 = sum_q M2.
-  static const bool gemm_f32 = getenv("GLOWK_WGRAD_F32") != nullptr;   // (A/B: the exact GEMMs under a split sweep)
-  const bool sg = tc->split && !gemm_f32;
+  const bool sg = tc->split;
   const float act = sg ? GLOWK_ACT_SCALE : 1.0f;
   if (int rc = launch_wgrad(h, sg, R2, r_bs, F, h->trGcol, (ptrdiff_t)gs, N3, Q, nb, 1.0f, act, h->trC3, c3s, true, s)) return rc;
   if (int rc = launch_wgrad(h, sg, R1, r_bs, F, M2, m_bs, F, Q, nb, 1.0f, 1.0f, h->trC2, c2s, true, s)) return rc;
@@ -493,7 +488,7 @@ static int param_grad_impl(glowk_handle* h, const float* x_dev, int N, float sca
   if (int rc = ensure_train(h, N)) return rc;
   // The sweep runs in the handle's arithmetic where the split kernels have training instances for every level (32x32x16 family,
   // forward and backward images) and the hiddens are kept by the forward pass; otherwise on the exact fp32 kernels.
-  bool split = allow_split && prec != GLOWK_PREC_F32 && h->trKeep && N <= h->trKeepN && !getenv("GLOWK_TRAIN_F32");
+  bool split = allow_split && prec != GLOWK_PREC_F32 && h->trKeep && N <= h->trKeepN;
   for (const Level& lv : h->levels) {
     if (!split) break;
     const StepDev& sd = lv.dev[0];
@@ -545,14 +540,12 @@ static int param_grad_impl(glowk_handle* h, const float* x_dev, int N, float sca
   // on the side stream (they land in the heads of the step blocks, which no kernel of the sweep writes after the initial memset), and
   // the caller's stream waits for that upload: no host join of the caller's stream at all
   hipStream_t side = h->tr_side;
-  const bool host_times = getenv("GLOWK_HOST_TIMES") != nullptr;      // (diagnostic: what does the host's share of a training step take?)
-  if (getenv("GLOWK_PG_JOIN")) HIPCHK(hipStreamSynchronize(s));       // (A/B timing: the host joins the caller's stream first, as it did before the side stream)
+  if (glowk_detail::env().pg_join) HIPCHK(hipStreamSynchronize(s));   // (A/B: the host joins the caller's stream first, as it did before the side stream)
   HIPCHK(hipStreamWaitEvent(side, h->tr_ev_sums, 0));
   HIPCHK(hipMemcpyAsync(h->h_sums, h->trAffSum, steps * AFF_NOUT_MAX * 8, hipMemcpyDeviceToHost, side));
   if (split) HIPCHK(hipMemcpyAsync(h->h_flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost, side));
   HIPCHK(hipMemcpyAsync(h->h_gmax, h->tr_gmax, sizeof(float) * 64, hipMemcpyDeviceToHost, side));
   HIPCHK(hipStreamSynchronize(side));
-  const auto ht0 = std::chrono::steady_clock::now();
   if (split && h->h_flag[0]) {       // the range guard of the split arithmetic fired somewhere in the sweep: its gradients are not usable
     h->h_flag[0] = 0;
     HIPCHK(hipMemsetAsync(h->d_flag, 0, sizeof(int), side));
@@ -591,8 +584,6 @@ static int param_grad_impl(glowk_handle* h, const float* x_dev, int N, float sca
   }
   HIPCHK(hipEventRecord(h->tr_ev_up, side));
   HIPCHK(hipStreamWaitEvent(s, h->tr_ev_up, 0));
-  if (host_times) fprintf(stderr, "glowk_param_grad: host share (chain rule of %zu steps + uploads) %.0f us\n", steps,
-                          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count());
   return 0;
 }
 
@@ -700,13 +691,10 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
       stale16 = true;
     }
   }
-  const bool host_times = getenv("GLOWK_HOST_TIMES") != nullptr;
-  double fold_us = 0.0;
   for (int lvl = 0; lvl < L; ++lvl) {
     Level& lv = h->levels[lvl];
     hipStream_t ls = h->tr_streams[lvl];
     HIPCHK(hipEventSynchronize(h->tr_events[1 + L + lvl]));      // the small tensors are down
-    const auto ht0 = std::chrono::steady_clock::now();
     const StepLayout SL = step_layout(lv.c, F);
     const TrainOff t = train_off(lv.c, F);
     float* img0 = h->arena + lv.dev[0].arena_off;
@@ -728,7 +716,6 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
       h->ld_step[(size_t)lvl * cfg.K + k] = ldc;
       std::memcpy(blocks + (size_t)k * tail, tmp.data() + SL.Afwd, tail * 4);
     }
-    fold_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count();
     HIPCHK(hipMemcpy2DAsync(img0 + SL.Afwd, SL.total * 4, blocks, tail * 4, tail * 4, cfg.K, hipMemcpyHostToDevice, ls));
     HIPCHK(hipEventRecord(h->tr_events[1 + lvl], ls));
     HIPCHK(hipStreamWaitEvent(s, h->tr_events[1 + lvl], 0));     // whatever the caller's stream runs next sees the refreshed images
@@ -746,7 +733,6 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
       if (SL.slotHB || SL.slotSB) { d.scb1 = q8[3]; d.scb2 = q8[4]; d.scb3 = q8[5]; d.xlim_b = q8[7]; }
     }
   }
-  if (host_times) fprintf(stderr, "glowk_apply_gradients: host fold of ActNorm + 1x1 (all levels) %.0f us\n", fold_us);
   h->ld_const = 0.0;
   for (double v : h->ld_step) h->ld_const += v;
   if (cfg.learntop) {

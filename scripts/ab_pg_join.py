@@ -19,12 +19,14 @@ for n in (32, 256):
         for join in (1, 0):
             if join: os.environ["GLOWK_PG_JOIN"] = "1"
             else: os.environ.pop("GLOWK_PG_JOIN", None)
+            _lib.load().glowk_reload_env()
             for _ in range(2): step()
             torch.cuda.synchronize(); t0 = time.perf_counter()
             for _ in range(10 if n == 32 else 4): step()
             torch.cuda.synchronize()
             res[join].append((time.perf_counter() - t0) / (10 if n == 32 else 4) * 1e3)
     os.environ.pop("GLOWK_PG_JOIN", None)
+    _lib.load().glowk_reload_env()
     a, b = sorted(res[1]), sorted(res[0])
     print("tiles %4d: step with the host join %.3f ms (min %.3f)   chain rule beside the GEMMs %.3f ms (min %.3f)   %+.1f %%" % (n, a[1], a[0], b[1], b[0], 100 * (b[1] / a[1] - 1)), flush=True)
     eng.close()

@@ -233,8 +233,8 @@ def test_input_gradient_f16x3_full_width():
         d = np.abs(g.cpu().numpy() - g_ref) / scale
         errs[prec] = float(d.max())
         # Either arithmetic may decide a ReLU whose pre-activation is within rounding of zero differently from fp64: one such flip
-        # moves a few dozen gradient entries around ONE pixel neighbourhood of ONE tile by ~1e-3 of the maximum (scripts/
-        # grad_flip_probe.py: seeds 11-16 of this very shape -- most agree to 6e-7, fp32 flips in tile 2 at seed 11, the split
+        # moves a few dozen gradient entries around ONE pixel neighbourhood of ONE tile by ~1e-3 of the maximum (probed
+        # on seeds 11-16 of this very shape -- most agree to 6e-7, fp32 flips in tile 2 at seed 11, the split
         # kernels in tile 1).  Everything outside such a neighbourhood is fp32-class; anything systematic is not tolerated.
         big = np.argwhere(d > 2e-4)
         if len(big):

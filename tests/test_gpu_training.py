@@ -137,22 +137,28 @@ def test_step_by_step_and_recompute_paths_agree_with_the_level_batches(prec, mon
     x = synthetic_mel_tiles(n, cfg, seed=23)
     scale = -1.0 / n
     flats = {}
-    for mode in ("batch", "GLOWK_TRAIN_PERSTEP", "GLOWK_TRAIN_RECOMPUTE"):
-        if mode != "batch":
-            monkeypatch.setenv(mode, "1")
-        eng, params = calibrated_engine(cfg, device=0, init_tiles=8)
-        if prec == "f16x3":
-            eng.set_precision(_lib.PREC_F16X3)
-            eng.set_range_policy("error")
-        lp, got, flat = engine_grads(eng, params, x, scale)
-        flats[mode] = flat.astype(np.float64)
-        if mode == "batch":
-            lp_ref, ref = oracle_param_grads(x, params, cfg, scale)
-        for k, r in ref.items():
-            np.testing.assert_allclose(got[k], r, atol=2e-4 * max(np.abs(r).max(), 1e-12), rtol=2e-3, err_msg="%s %s" % (mode, k))
-        eng.close()
-        if mode != "batch":
-            monkeypatch.delenv(mode)
+    try:
+        for mode in ("batch", "GLOWK_TRAIN_PERSTEP", "GLOWK_TRAIN_RECOMPUTE"):
+            if mode != "batch":
+                monkeypatch.setenv(mode, "1")
+                _lib.load().glowk_reload_env()       # (the engine reads its switches when the library loads)
+            eng, params = calibrated_engine(cfg, device=0, init_tiles=8)
+            if prec == "f16x3":
+                eng.set_precision(_lib.PREC_F16X3)
+                eng.set_range_policy("error")
+            lp, got, flat = engine_grads(eng, params, x, scale)
+            flats[mode] = flat.astype(np.float64)
+            if mode == "batch":
+                lp_ref, ref = oracle_param_grads(x, params, cfg, scale)
+            for k, r in ref.items():
+                np.testing.assert_allclose(got[k], r, atol=2e-4 * max(np.abs(r).max(), 1e-12), rtol=2e-3, err_msg="%s %s" % (mode, k))
+            eng.close()
+            if mode != "batch":
+                monkeypatch.delenv(mode)
+                _lib.load().glowk_reload_env()
+    finally:
+        monkeypatch.undo()
+        _lib.load().glowk_reload_env()
     ref_norm = np.linalg.norm(flats["batch"])
     for mode in ("GLOWK_TRAIN_PERSTEP", "GLOWK_TRAIN_RECOMPUTE"):
         assert np.linalg.norm(flats[mode] - flats["batch"]) < 2e-6 * ref_norm, mode
@@ -398,29 +404,33 @@ def test_training_steps_without_a_host_join_equal_joined_ones(prec, monkeypatch)
     cfg = GlowConfig(H=32, W=32, C=1, L=3, K=3, F=256)
     x = dev(synthetic_mel_tiles(24, cfg, seed=41))
     out = {}
-    for joined in (False, True):
-        if joined:
-            monkeypatch.setenv("GLOWK_PG_JOIN", "1")
-        else:
-            monkeypatch.delenv("GLOWK_PG_JOIN", raising=False)
-        eng, _ = calibrated_engine(cfg, device=0, init_tiles=16)
-        if prec == "f16x3":
-            eng.set_precision(_lib.PREC_F16X3)
-        g = torch.zeros(eng.param_vector_size, device="cuda")
-        lps = []
-        for it in range(8):
-            lp, _ = eng.param_grad(x, -1.0 / 24.0, g)
+    try:
+        for joined in (False, True):
             if joined:
-                torch.cuda.synchronize()
-            lps.append(lp)
-            eng.apply_gradients(g, optimizer="adamax", lr=1e-3)
-            if joined:
-                torch.cuda.synchronize()
-        final = eng.log_prob(x)
-        torch.cuda.synchronize()
-        out[joined] = (torch.stack(lps).cpu(), final.cpu(), {k: np.asarray(v) for k, v in GlowFlow(eng).state_dict().items()}, g.cpu())
-        eng.close()
-    monkeypatch.undo()
+                monkeypatch.setenv("GLOWK_PG_JOIN", "1")
+            else:
+                monkeypatch.delenv("GLOWK_PG_JOIN", raising=False)
+            _lib.load().glowk_reload_env()           # (the engine reads its switches when the library loads)
+            eng, _ = calibrated_engine(cfg, device=0, init_tiles=16)
+            if prec == "f16x3":
+                eng.set_precision(_lib.PREC_F16X3)
+            g = torch.zeros(eng.param_vector_size, device="cuda")
+            lps = []
+            for it in range(8):
+                lp, _ = eng.param_grad(x, -1.0 / 24.0, g)
+                if joined:
+                    torch.cuda.synchronize()
+                lps.append(lp)
+                eng.apply_gradients(g, optimizer="adamax", lr=1e-3)
+                if joined:
+                    torch.cuda.synchronize()
+            final = eng.log_prob(x)
+            torch.cuda.synchronize()
+            out[joined] = (torch.stack(lps).cpu(), final.cpu(), {k: np.asarray(v) for k, v in GlowFlow(eng).state_dict().items()}, g.cpu())
+            eng.close()
+    finally:
+        monkeypatch.undo()
+        _lib.load().glowk_reload_env()
     a, b = out[False], out[True]
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[3], b[3])
     assert a[2].keys() == b[2].keys()
