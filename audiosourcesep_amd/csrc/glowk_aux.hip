@@ -1,8 +1,9 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
-// the audio front end and mel inversion (glowk_audio.h)
+// the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
+#include "glowk_bsseval.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -220,16 +221,16 @@ static const AudioHost& audio_host() {
 }
 
 // the device every pointer lives on; a host, unregistered or foreign-device pointer is refused (the kernels would fault on it)
-static int audio_device(std::initializer_list<const void*> ptrs, int* dev) {
+static int audio_device(std::initializer_list<const void*> ptrs, int* dev, const char* what = "audio") {
   *dev = -1;
   for (const void* p : ptrs) {
     if (!p) continue;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess || !(a.type == hipMemoryTypeDevice || a.isManaged) || a.device < 0) {
       (void)hipGetLastError();
-      return fail("audio: every tensor must be device memory");
+      return fail(std::string(what) + ": every tensor must be device memory");
     }
-    if (*dev >= 0 && a.device != *dev) return fail("audio: the tensors are on different devices");
+    if (*dev >= 0 && a.device != *dev) return fail(std::string(what) + ": the tensors are on different devices");
     *dev = a.device;
   }
   return 0;
@@ -346,6 +347,120 @@ int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev,
   hipLaunchKernelGGL(k_istft, dim3((unsigned)(S * N * htiles), HOP / 128), dim3(256), 0, (hipStream_t)stream, power_dev, S, stft_mix_dev, N, frames,
                      htiles, wiener ? 1 : 0, c, audio_dev);
   LAUNCHCHK("k_istft");
+  return 0;
+}
+
+// ---- BSS Eval v4 (glowk_bsseval.h) ------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t BSS_SCRATCH_CAP = (size_t)256 << 20;   // partial sums of one launch group
+constexpr size_t BSS_CHOL_CAP = (size_t)2 << 30;        // Cholesky workspaces in flight (8 MB per system at M = 1024)
+}
+
+int glowk_bss_xcorr(const double* sig_dev, int nsig, int64_t nsampl, const int64_t* win_dev, int nwin, int64_t max_len, const int* pairs_dev,
+                    int npairs, int filters_len, double* corr_dev, void* stream) {
+  using namespace glowk_bss;
+  if (!sig_dev || !win_dev || !pairs_dev || !corr_dev) return fail("null tensor");
+  if (nsig < 1 || nsampl < 1 || nsampl > ((int64_t)1 << 40)) return fail("bss_xcorr: nsig and nsampl must be positive");
+  if (filters_len < 1 || filters_len > LMAX) return fail("bss_xcorr: filters_len must be in [1, 512]");
+  if (npairs < 1 || npairs > 65535) return fail("bss_xcorr: npairs must be in [1, 65535]");
+  if (nwin < 0 || max_len < 0 || max_len > nsampl) return fail("bss_xcorr: nwin >= 0 and max_len in [0, nsampl] required");
+  if (nwin == 0) return 0;
+  int dev;
+  if (int rc = audio_device({sig_dev, win_dev, pairs_dev, corr_dev}, &dev, "bss_xcorr")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nsub = std::max<int64_t>(1, (max_len + XC_SUB - 1) / XC_SUB);
+  const int per = (int)((nsub + 1023) / 1024), nblk = (int)((nsub + per - 1) / per);
+  const size_t per_win = (size_t)npairs * nblk * filters_len * sizeof(double);
+  const int group = (int)std::max<size_t>(1, std::min<size_t>({BSS_SCRATCH_CAP / per_win, (size_t)nwin, (size_t)65535}));
+  double* part = nullptr;
+  HIPCHK(hipMallocAsync((void**)&part, group * per_win, s));
+  hipError_t e = hipSuccess;
+  for (int w0 = 0; w0 < nwin && e == hipSuccess; w0 += group) {
+    const int g = std::min(group, nwin - w0);
+    XcorrArgs a;
+    a.sig = sig_dev; a.nsig = nsig; a.nsampl = nsampl; a.win = win_dev + 2 * (int64_t)w0; a.pairs = pairs_dev; a.npairs = npairs;
+    a.L = filters_len; a.per = per; a.nblk = nblk; a.part = part;
+    hipLaunchKernelGGL(k_bss_xcorr, dim3(nblk, npairs, g), dim3(XC_THREADS), 0, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) break;
+    const int64_t n = (int64_t)g * npairs * filters_len;
+    hipLaunchKernelGGL(k_bss_xcorr_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)part, n, filters_len, nblk,
+                       corr_dev + (int64_t)w0 * npairs * filters_len);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(part, s);
+  if (e != hipSuccess) return fail(std::string("launch k_bss_xcorr: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int glowk_bss_solve(const double* corr_dev, int nwin, int npairs, int nref, int filters_len, int nchan_sys, const int* sys_dev, int nsys,
+                    double* coef_dev, int* status_dev, void* stream) {
+  using namespace glowk_bss;
+  if (!corr_dev || !sys_dev || !coef_dev || !status_dev) return fail("null tensor");
+  if (filters_len < 1 || filters_len > LMAX) return fail("bss_solve: filters_len must be in [1, 512]");
+  if (nref < 1 || nchan_sys < 1 || nchan_sys > nref) return fail("bss_solve: need 1 <= nchan_sys <= nref");
+  if ((int64_t)nchan_sys * filters_len > MMAX) return fail("bss_solve: nchan_sys * filters_len must be <= 2048");
+  if (nwin < 1 || (int64_t)npairs < 2 * (int64_t)nref * nref) return fail("bss_solve: nwin >= 1 and npairs >= 2 nref^2 required");
+  if (nsys < 0) return fail("bss_solve: nsys must be >= 0");
+  if (nsys == 0) return 0;
+  int dev;
+  if (int rc = audio_device({corr_dev, sys_dev, coef_dev, status_dev}, &dev, "bss_solve")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t s = (hipStream_t)stream;
+  const int M = nchan_sys * filters_len;
+  const size_t per_sys = (size_t)M * M * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(BSS_CHOL_CAP / per_sys, (size_t)nsys));
+  double* A = nullptr;
+  HIPCHK(hipMallocAsync((void**)&A, chunk * per_sys, s));
+  hipError_t e = hipSuccess;
+  for (int k0 = 0; k0 < nsys && e == hipSuccess; k0 += chunk) {
+    CholArgs a;
+    a.corr = corr_dev; a.nwin = nwin; a.npairs = npairs; a.P = nref; a.L = filters_len; a.np = nchan_sys; a.sys = sys_dev; a.sys0 = k0;
+    a.A = A; a.X = coef_dev; a.status = status_dev;
+    hipLaunchKernelGGL(k_bss_chol, dim3(std::min(chunk, nsys - k0)), dim3(CH_THREADS), 0, s, a);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(A, s);
+  if (e != hipSuccess) return fail(std::string("launch k_bss_chol: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int glowk_bss_project(const double* sig_dev, int64_t nsampl, int nsrc, int nchan, int filters_len, const int64_t* items_dev, int nitems,
+                      int64_t max_len, const double* coef_c_dev, int nsys_c, const double* coef_j_dev, int nsys_j, double* energy_dev,
+                      void* stream) {
+  using namespace glowk_bss;
+  if (!sig_dev || !items_dev || !coef_c_dev || !coef_j_dev || !energy_dev) return fail("null tensor");
+  if (nsampl < 1 || nsampl > ((int64_t)1 << 40)) return fail("bss_project: nsampl must be positive");
+  if (filters_len < 1 || filters_len > LMAX) return fail("bss_project: filters_len must be in [1, 512]");
+  if (nsrc < 1 || nchan < 1 || (int64_t)nsrc * nchan * filters_len > MMAX) return fail("bss_project: nsrc * nchan * filters_len must be <= 2048");
+  if (nitems < 0 || nsys_c < 1 || nsys_j < 1 || max_len < 0 || max_len > nsampl) return fail("bss_project: bad item / system counts or max_len");
+  if (nitems == 0) return 0;
+  int dev;
+  if (int rc = audio_device({sig_dev, items_dev, coef_c_dev, coef_j_dev, energy_dev}, &dev, "bss_project")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nchunk = (max_len + filters_len - 1 + PJ_OUT - 1) / PJ_OUT;
+  if (nchunk > (1 << 24)) return fail("bss_project: window too long");
+  const size_t per_item = (size_t)nchunk * NENERGY * sizeof(double);
+  const int group = (int)std::max<size_t>(1, std::min<size_t>({BSS_SCRATCH_CAP / per_item, (size_t)nitems, (size_t)(((int64_t)1 << 30) / nchunk)}));
+  double* part = nullptr;
+  HIPCHK(hipMallocAsync((void**)&part, group * per_item, s));
+  hipError_t e = hipSuccess;
+  for (int i0 = 0; i0 < nitems && e == hipSuccess; i0 += group) {
+    const int g = std::min(group, nitems - i0);
+    ProjArgs a;
+    a.sig = sig_dev; a.nsampl = nsampl; a.nsrc = nsrc; a.nchan = nchan; a.L = filters_len; a.items = items_dev + 6 * (int64_t)i0; a.nitems = g;
+    a.nchunk = (int)nchunk; a.coefC = coef_c_dev; a.nsysC = nsys_c; a.coefJ = coef_j_dev; a.nsysJ = nsys_j; a.part = part;
+    hipLaunchKernelGGL(k_bss_project, dim3((unsigned)(g * nchunk)), dim3(PJ_THREADS), 0, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(k_bss_energy_sum, dim3((unsigned)((g * NENERGY + 255) / 256)), dim3(256), 0, s, (const double*)part, g, (int)nchunk,
+                       energy_dev + (int64_t)i0 * NENERGY);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(part, s);
+  if (e != hipSuccess) return fail(std::string("launch k_bss_project: ") + hipGetErrorString(e));
   return 0;
 }
 
