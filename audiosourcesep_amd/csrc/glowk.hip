@@ -32,17 +32,9 @@ static EnvSwitches read_env() {
 static EnvSwitches g_env = read_env();
 const EnvSwitches& env() { return g_env; }
 void reload_env() { g_env = read_env(); }
-thread_local int g_family = 0;
-thread_local bool g_co = false, g_q = false;
-void note_family(int family) { g_family = family; g_co = false; g_q = false; }
-void note_co() { g_co = true; }
-void note_q() { g_q = true; }
 // instantiated in glowk_net_inst.hip, one translation unit per (CI, NF)
-#define GLOWK_EXTERN_NET(CI_, NF_) extern template int launch_net_t<CI_, NF_>(const NetArgs&, int, hipStream_t, bool);
-GLOWK_EXTERN_NET(2, 16) GLOWK_EXTERN_NET(4, 16) GLOWK_EXTERN_NET(8, 16) GLOWK_EXTERN_NET(16, 16)
-GLOWK_EXTERN_NET(2, 12) GLOWK_EXTERN_NET(4, 12) GLOWK_EXTERN_NET(8, 12) GLOWK_EXTERN_NET(16, 12)
-GLOWK_EXTERN_NET(2, 8) GLOWK_EXTERN_NET(4, 8) GLOWK_EXTERN_NET(8, 8) GLOWK_EXTERN_NET(16, 8)
-GLOWK_EXTERN_NET(2, 4) GLOWK_EXTERN_NET(4, 4) GLOWK_EXTERN_NET(8, 4) GLOWK_EXTERN_NET(16, 4)
+#define GLOWK_EXTERN_NET(CI_, NF_) extern template NetLaunch launch_net_t<CI_, NF_>(const NetArgs&, NetCall, hipStream_t, bool);
+GLOWK_NET_SHAPES(GLOWK_EXTERN_NET)
 #undef GLOWK_EXTERN_NET
 }  // namespace glowk_detail
 
@@ -50,9 +42,13 @@ namespace glowk_eng {
 using glowk_detail::num_cus;
 using glowk_detail::launch_net_t;
 
-// launch_net mode of the plain forward network for the handle's precision (glowk_launch.h: 0 exact fp32, 3 three-term split,
-// 6 two-term split)
-int fwd_mode(const glowk_handle* h) { return h->precision == GLOWK_PREC_F16X3 ? 3 : h->precision == GLOWK_PREC_F16X2 ? 6 : NET_FWD; }
+// The network launch of direction dir in the handle's arithmetic: exact fp32 in GLOWK_PREC_F32 or where the step has no split image
+// for it (split = false); otherwise the three-term split, but for the plain forward network of GLOWK_PREC_F16X2 (the only two-term
+// launch).  store: a training launch that also stores its hiddens.
+NetCall net_call(const glowk_handle* h, int dir, bool store, bool split) {
+  if (h->precision == GLOWK_PREC_F32 || !split) return NetCall{dir, NET_EXACT, store};
+  return NetCall{dir, h->precision == GLOWK_PREC_F16X2 && dir == NET_FWD && !store ? NET_SPLIT2 : NET_SPLIT3, store};
+}
 
 // the light kernels raise the sticky range flag only for calls in a split arithmetic (in exact fp32 a non-finite value is the
 // reference's own result, and the fp32 re-run of the FALLBACK policy must not re-arm it)
@@ -67,42 +63,37 @@ float bwd_norm_target(float xlim_b) {
   return std::ldexp(1.0f, std::min(e - 1, 10));
 }
 
-int launch_net_raw(int c, int F, const NetArgs& a, int mode, hipStream_t s, bool dry) {
-  glowk_detail::g_family = 0;     // (the fp32 kernels do not announce themselves)
-  glowk_detail::g_co = false;
-  glowk_detail::g_q = false;
-#define NETCASE(CI_, NF_) if (c == 2 * CI_ && F == 32 * NF_) return launch_net_t<CI_, NF_>(a, mode, s, dry);
-  NETCASE(2, 16) NETCASE(4, 16) NETCASE(8, 16) NETCASE(16, 16)
-  NETCASE(2, 12) NETCASE(4, 12) NETCASE(8, 12) NETCASE(16, 12)
-  NETCASE(2, 8) NETCASE(4, 8) NETCASE(8, 8) NETCASE(16, 8)
-  NETCASE(2, 4) NETCASE(4, 4) NETCASE(8, 4) NETCASE(16, 4)
+NetLaunch launch_net_raw(int c, int F, const NetArgs& a, NetCall call, hipStream_t s, bool dry) {
+#define NETCASE(CI_, NF_) if (c == 2 * CI_ && F == 32 * NF_) return launch_net_t<CI_, NF_>(a, call, s, dry);
+  GLOWK_NET_SHAPES(NETCASE)
 #undef NETCASE
-  fail("unsupported (channels, n_filters) combination: c=" + std::to_string(c) + " F=" + std::to_string(F));
-  return -1;
+  return glowk_detail::net_failed("unsupported (channels, n_filters) combination: c=" + std::to_string(c) + " F=" + std::to_string(F));
 }
 
-// np_out: number of partial P buffers the launch wrote (P + p * pstride), for the consumer
-int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipStream_t s, int mode = NET_FWD, int* np_out = nullptr) {
-  if (!h->profiling) {
-    const int np = launch_net_raw(c, F, a, mode, s);
-    if (np >= 0) { ++h->family_launches[glowk_detail::g_family]; if (glowk_detail::g_co) ++h->family_launches[5]; if (glowk_detail::g_q) ++h->family_launches[6]; }
-    if (np_out) *np_out = np;
-    return np < 0 ? 1 : 0;
+// out: what the launch took (NetLaunch::np partial P buffers, for the consumer).  Counts the launch into glowk_kernel_families; the
+// calls of launch_net_raw alone (the recompute launch of the training sweep, dry queries) are not counted.
+int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipStream_t s, NetCall call, NetLaunch* out = nullptr) {
+  if (h->profiling) {
+    while (h->ev_pool.size() < h->ev_used + 2) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreate(&e));
+      h->ev_pool.push_back(e);
+    }
+    HIPCHK(hipEventRecord(h->ev_pool[h->ev_used], s));
   }
-  while (h->ev_pool.size() < h->ev_used + 2) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    h->ev_pool.push_back(e);
+  const NetLaunch r = launch_net_raw(c, F, a, call, s);
+  if (!r.failed) {
+    ++h->family_launches[r.family];
+    if (r.co) ++h->family_launches[FAM_CO];
+    if (r.q) ++h->family_launches[FAM_Q];
   }
-  hipEvent_t e0 = h->ev_pool[h->ev_used], e1 = h->ev_pool[h->ev_used + 1];
-  HIPCHK(hipEventRecord(e0, s));
-  const int np = launch_net_raw(c, F, a, mode, s);
-  if (np >= 0) { ++h->family_launches[glowk_detail::g_family]; if (glowk_detail::g_co) ++h->family_launches[5]; if (glowk_detail::g_q) ++h->family_launches[6]; }
-  HIPCHK(hipEventRecord(e1, s));
-  h->ev_used += 2;
-  h->ev_level.push_back(level);
-  if (np_out) *np_out = np;
-  return np < 0 ? 1 : 0;
+  if (h->profiling) {
+    HIPCHK(hipEventRecord(h->ev_pool[h->ev_used + 1], s));
+    h->ev_used += 2;
+    h->ev_level.push_back(level);
+  }
+  if (out) *out = r;
+  return r.failed ? 1 : 0;
 }
 
 
@@ -150,9 +141,10 @@ int launch_couple(int c, const CoupleArgs& a, int N, hipStream_t s, const FlatLd
 }
 
 // One flow step's coupling network + coupling.  Plain forward direction of the split arithmetics at the 4-channel level with a grid
-// that fills the chip: ONE kernel (k_net_h3s<..., MODE | 16>: the per-tap conv3 outputs never leave the workgroup) plus
+// that fills the chip: ONE kernel (k_net_h3s<..., MODE | NET_FUSE>: the per-tap conv3 outputs never leave the workgroup) plus
 // k_couple_edge for the pixel rows whose 3 x 3 neighbourhood straddles two workgroups and the per-sample log-det; otherwise k_net
-// (P to HBM) + k_couple.  na: the network launch (na.P / pstride as for launch_net); ca: the coupling as k_couple takes it.
+// (P to HBM) + k_couple.  na: the network launch (na.P / pstride as for launch_net); ca: the coupling as k_couple takes it, but for
+// P / np / pstride, which the network launch decides.
 bool fuse_geometry_ok(int h, int w, int pxw = 256) {     // pxw: pixels per workgroup of the fused kernel
   const int hw = h * w;
   if (w < 4 || w > FUSE_EW || (w & (w - 1)) || pxw % w) return false;
@@ -160,11 +152,12 @@ bool fuse_geometry_ok(int h, int w, int pxw = 256) {     // pxw: pixels per work
   return hw >= 32 && hw < pxw && (hw & (hw - 1)) == 0;
 }
 
-int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArgs ca, int N, hipStream_t s, int mode, const FlatLd* fl = nullptr,
+int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArgs ca, int N, hipStream_t s, NetCall call, const FlatLd* fl = nullptr,
                    bool* flat_used = nullptr) {
   const bool no_fuse = glowk_detail::env().no_fuse;            // (A/B timing and the fused-vs-unfused parity test, which calls glowk_reload_env)
+  const bool fusable = call.arith != NET_EXACT && call.dir != NET_BWD && !call.store;   // the split forward networks, saving or not
   const int hw = ca.h * ca.w;
-  if (!no_fuse && c == 4 && (mode == 3 || mode == 6 || mode == 4) && na.RSp && ca.vin && !ca.log_s_out && ca.out && na.in_stride == 4 &&
+  if (!no_fuse && c == 4 && fusable && na.RSp && ca.vin && !ca.log_s_out && ca.out && na.in_stride == 4 &&
       ca.out_stride % 4 == 0 && ca.out_off % 4 == 0 && fuse_geometry_ok(ca.h, ca.w) && na.P == h->bufP) {
     // (scratch sized for the co-resident form's 128-pixel workgroups when it may be taken: twice the edge slots)
     const size_t pxw = (na.co && fuse_geometry_ok(ca.h, ca.w, CO_PX)) ? CO_PX : 256;
@@ -181,14 +174,14 @@ int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArg
       na.fz_ldpart = ca.logdet ? reinterpret_cast<double*>(h->bufP + edge_floats) : nullptr;
     }
   }
-  int np = 1;
-  if (int rc = launch_net(h, lvl, c, F, na, s, mode, &np)) return rc;
-  if (np != 100 && np != 101) {
-    ca.P = na.P; ca.np = np; ca.pstride = na.pstride;
+  NetLaunch r;
+  if (int rc = launch_net(h, lvl, c, F, na, s, call, &r)) return rc;
+  if (!r.fused_px) {
+    ca.P = na.P; ca.np = r.np; ca.pstride = na.pstride;
     return launch_couple(c, ca, N, s, fl, flat_used);
   }
   ++h->fused_steps;
-  const int pxw = np == 101 ? CO_PX : 256;
+  const int pxw = r.fused_px;
   if (hw > pxw || ca.logdet) {
     EdgeArgs ea;
     ea.vin = ca.vin; ea.edge = na.fz_edge; ea.ldpart = na.fz_ldpart; ea.A = ca.A; ea.b = ca.b; ea.out = ca.out; ea.out_stride = ca.out_stride;
@@ -369,6 +362,8 @@ int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_
   float* oth = h->bufB;
   // small batches: the coupling kernels run on a flat pixel grid and leave their log-det shares in per-workgroup slots (k_couple_flat)
   const int nslots = ld_slots_per_sample(h);
+  // (the plain forward direction and the saving pass of the split arithmetics: network + coupling may run as one kernel, net_and_couple)
+  const NetCall call = net_call(h, save ? NET_FWD_SAVE : NET_FWD, keep_hidden);
   const bool flat_ok = N < 2 * num_cus() && h->bufLdSlot;
   bool flat_used = false;
   int slot_base = 0;
@@ -392,19 +387,12 @@ int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_
         na.mask1 = h->saveM + h->offM[sidx];
         na.mask2 = na.mask1 + blocks * NF * 64;
       }
-      int np = 1;   // the f16x3 kernels leave P as np partial sums (one per pass over the hidden width)
-      if (keep_hidden) {   // training, exact fp32: this launch also leaves relu(conv1 + b1), relu(conv2 + b2) planar for the weight gradients
+      if (keep_hidden) {   // training: this launch also leaves relu(conv1 + b1), relu(conv2 + b2) planar for the weight gradients
         na.st1 = h->trKeep + h->trKeepOff[sidx] * (size_t)N;
         na.st2 = na.st1 + (size_t)cfg.F * Q;
       }
-      // the plain forward direction and the saving pass of the split arithmetics: network + coupling may run as one kernel
-      const bool plain = !keep_hidden && (!save || h->precision != GLOWK_PREC_F32);
-      const int plain_mode = save ? 4 : fwd_mode(h);
-      if (!plain) {
-        if (int rc = launch_net(h, lvl, lv.c, cfg.F, na, s, keep_hidden ? (h->precision == GLOWK_PREC_F32 ? 9 : 10) : NET_FWD_SAVE, &np)) return rc;
-      }
       CoupleArgs ca;
-      ca.vin = cur; ca.P = na.P; ca.np = np; ca.pstride = na.pstride; ca.b3 = sd.b3; ca.logdet = h->bufLd; ca.log_s_out = nullptr; ca.t_out = nullptr;
+      ca.vin = cur; ca.b3 = sd.b3; ca.logdet = h->bufLd; ca.log_s_out = nullptr; ca.t_out = nullptr;
       ca.o_save = save ? h->saveP + h->offP[sidx] : nullptr;
       ca.Q = (int)Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
       float* next = save && k > 0 ? h->saveV + h->offV[sidx + 1] : oth;
@@ -418,8 +406,7 @@ int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_
       }
       const FlatLd fl{flat_ok ? h->bufLdSlot : nullptr, nslots, slot_base};
       slot_base += (lv.h * lv.w + 15) / 16;
-      if (plain) { if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, na, ca, N, s, plain_mode, &fl, &flat_used)) return rc; }
-      else if (int rc = launch_couple(lv.c, ca, N, s, &fl, &flat_used)) return rc;
+      if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, na, ca, N, s, call, &fl, &flat_used)) return rc;
       if (k > 0) {
         if (save) cur = next; else std::swap(cur, oth);
       } else if (lvl < L - 1) {
@@ -498,8 +485,8 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
       na.K1p = sd.K3bp; na.R0p = sd.RBp; na.P = Pg;
       na.mask1 = h->saveM + h->offM[sidx];
       na.mask2 = na.mask1 + blocks * NF * 64;
-      const bool h3b = (tc ? tc->split : h->precision != GLOWK_PREC_F32) && (sd.RHBp || sd.RSBp);   // (c = 32: 16x16x32 image only)
-      if (h3b) {
+      const NetCall call = net_call(h, NET_BWD, tc != nullptr, sd.RHBp || sd.RSBp);   // (c = 32: 16x16x32 image only)
+      if (call.arith != NET_EXACT) {
         na.RHp = sd.RHBp; na.RSp = sd.RSBp; na.eph = nullptr; na.sc1 = sd.scb1; na.sc2 = sd.scb2; na.sc3 = sd.scb3; na.xlim = sd.xlim_b;
         // the backward network is linear, so the kernels normalise every pixel's gradient vector to [T, 2T) (a power of two, exact;
         // glowk_kernels.h: pixel_norm): T = the largest power of two for which the host's worst-case bound (xlim_b: L1 norms of the
@@ -513,7 +500,9 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
       }
       if (na.xmax_out) na.xmax_out += (size_t)cfg.L * cfg.K;     // (range probe: the backward launches' half)
       if (tc) { na.st1 = h->trM2 + (size_t)k * m_slot; na.st2 = h->trM1 + (size_t)k * m_slot; }
-      if (int rc = launch_net(h, lvl, lv.c, cfg.F, na, s, tc ? (tc->split ? 11 : 8) : h3b ? 5 : NET_BWD, &npg)) return rc;
+      NetLaunch r;
+      if (int rc = launch_net(h, lvl, lv.c, cfg.F, na, s, call, &r)) return rc;
+      npg = r.np;
       if (tc && !level_batch) {
         // R1 / R2: kept by the saving forward pass, or recomputed now from the saved input (the P output of that launch goes to a
         // scratch partial of bufP)
@@ -522,7 +511,7 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
         else {
           NetArgs nf = net_args(h, lv, sd, h->saveV + h->offV[sidx], lv.c, lv.c / 2, N);
           nf.P = h->bufP + 2 * h->pstride; nf.st1 = h->trR1; nf.st2 = h->trR1 + (size_t)cfg.F * Q;
-          if (launch_net_raw(lv.c, cfg.F, nf, 7, s) < 0) return 1;
+          if (launch_net_raw(lv.c, cfg.F, nf, net_call(h, NET_FWD, true), s).failed) return 1;   // (exact fp32: a split sweep keeps its hiddens)
         }
         if (int rc = train_network_grads(h, tc, lvl, k, 1, h->saveV + h->offV[sidx], 0, go_k, 0, R1, 0, h->trM1, h->trM2, 0, N, s, bfac)) return rc;
       }
@@ -586,7 +575,7 @@ int run_inverse(glowk_handle* h, const float* z, int N, float* x, hipStream_t s)
       ca.vin = cur; ca.P = h->bufP; ca.np = 1; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr; ca.o_save = nullptr;
       ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
       ca.A = sd.Ainv; ca.b = sd.binv; ca.out = oth; ca.out_stride = lv.c; ca.out_off = 0;
-      if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, net_args(h, lv, sd, cur, lv.c, lv.c / 2, N), ca, N, s, fwd_mode(h))) return rc;
+      if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, net_args(h, lv, sd, cur, lv.c, lv.c / 2, N), ca, N, s, net_call(h, NET_FWD))) return rc;
       std::swap(cur, oth);
     }
   }
@@ -856,7 +845,7 @@ int run_step_inplace(glowk_handle* h, int lvl, int k, float* cur, float* tmp, in
   CDISPATCH(lv.c, hipLaunchKernelGGL((k_affine<CC>), dim3((Q + 255) / 256), dim3(256), 0, s, (const float*)cur, Q, sd.Afwd, sd.bfwd, tmp));
   LAUNCHCHK("k_affine");
   NetArgs na = net_args(h, lv, sd, tmp, lv.c, lv.c / 2, Nl);
-  if (int rc = launch_net(h, lvl, lv.c, h->cfg.F, na, s)) return rc;
+  if (int rc = launch_net(h, lvl, lv.c, h->cfg.F, na, s, NetCall{NET_FWD, NET_EXACT})) return rc;
   CoupleArgs ca;
   ca.o_save = nullptr;
   ca.vin = tmp; ca.P = h->bufP; ca.np = 1; ca.pstride = 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
@@ -1178,7 +1167,7 @@ int64_t glowk_fused_steps(const glowk_handle* h) { return h ? h->fused_steps : -
 
 int glowk_kernel_families(const glowk_handle* h, int64_t* out7) {
   if (!h || !out7) return fail("null argument");
-  for (int i = 0; i < 7; ++i) out7[i] = h->family_launches[i];
+  for (int i = 0; i < FAM_COUNT; ++i) out7[i] = h->family_launches[i];
   return 0;
 }
 
@@ -1266,8 +1255,8 @@ int glowk_step_forward(glowk_handle* h, int level, int step, const float* u_dev,
   return guarded(h, s, [&]() -> int {
     CDISPATCH(lv.c, hipLaunchKernelGGL((k_affine<CC>), dim3((Q + 255) / 256), dim3(256), 0, s, u_dev, Q, sd.Afwd, sd.bfwd, h->bufA));
     LAUNCHCHK("k_affine");
-    int np = 1;
-    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, h->bufA, lv.c, lv.c / 2, N), s, fwd_mode(h), &np)) return rc;
+    NetLaunch r;
+    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, h->bufA, lv.c, lv.c / 2, N), s, net_call(h, NET_FWD), &r)) return rc;
     if (logdet_dev) {
       // logdet accumulator starts at the step's constant h*w*(sum log_scale + sum log_S)
       std::vector<double> init(N, h->ld_step[(size_t)level * h->cfg.K + step]);
@@ -1276,7 +1265,7 @@ int glowk_step_forward(glowk_handle* h, int level, int step, const float* u_dev,
     }
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = h->bufA; ca.P = h->bufP; ca.np = np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
+    ca.vin = h->bufA; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
     ca.out = y_dev; ca.out_stride = lv.c; ca.out_off = 0;
     ca.logdet = logdet_dev ? h->bufLd : nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
     ca.Q = Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
@@ -1300,11 +1289,11 @@ int glowk_step_inverse(glowk_handle* h, int level, int step, const float* y_dev,
   const Level& lv = h->levels[level];
   const StepDev& sd = lv.dev[step];
   return guarded(h, s, [&]() -> int {
-    int np = 1;
-    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, y_dev, lv.c, lv.c / 2, N), s, fwd_mode(h), &np)) return rc;
+    NetLaunch r;
+    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, y_dev, lv.c, lv.c / 2, N), s, net_call(h, NET_FWD), &r)) return rc;
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = y_dev; ca.P = h->bufP; ca.np = np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = sd.Ainv; ca.b = sd.binv;
+    ca.vin = y_dev; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = sd.Ainv; ca.b = sd.binv;
     ca.out = u_dev; ca.out_stride = lv.c; ca.out_off = 0;
     ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
     ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
@@ -1322,11 +1311,11 @@ int glowk_coupling_net(glowk_handle* h, int level, int step, const float* xb_dev
   const Level& lv = h->levels[level];
   const StepDev& sd = lv.dev[step];
   return guarded(h, s, [&]() -> int {
-    int np = 1;
-    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, xb_dev, lv.c / 2, 0, N), s, fwd_mode(h), &np)) return rc;
+    NetLaunch r;
+    if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, xb_dev, lv.c / 2, 0, N), s, net_call(h, NET_FWD), &r)) return rc;
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = nullptr; ca.P = h->bufP; ca.np = np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
+    ca.vin = nullptr; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
     ca.out = nullptr; ca.out_stride = 0; ca.out_off = 0;
     ca.logdet = nullptr; ca.log_s_out = log_s_dev; ca.t_out = t_dev;
     ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);

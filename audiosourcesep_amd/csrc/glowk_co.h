@@ -22,12 +22,12 @@
 // wave has landed" is exactly what each op boundary needs (4 pieces per wave and unit, 1 per conv1 block); the barrier publishes it.
 // The slots are distinct static __shared__ objects with static roles (glowk_kernels.h, rule 1): M0 always holds the first halves.
 //
-// Modes (MODE & 7): the plain forward network (NET_FWD, NET_FWD2), the forward network of the gradient path (NET_FWD_SAVE: ReLU masks
+// Directions (net_dir<MODE>): the plain forward network (NET_FWD, NET_FWD2), the forward network of the gradient path (NET_FWD_SAVE: ReLU masks
 // stored from X and Z) and the backward network (NET_BWD, 4-channel level: 18 output rows = two conv3 units; the forward pass's masks
 // of the workgroup's four 32-pixel blocks in LDS; every pixel's gradient normalised by a power of two) -- the mask layout is that of the
-// eight-wave 16x16x32 kernels (one entry per 32-pixel block of a wave), so either form can follow the other.  MODE | 16: the coupling
+// eight-wave 16x16x32 kernels (one entry per 32-pixel block of a wave), so either form can follow the other.  MODE | NET_FUSE: the coupling
 // fused in (forward modes).  SPLIT: grid.y = 2 and every workgroup runs ONE pass (small grids: 2 x Q/128 workgroups of four waves,
-// two to a CU; each pass leaves its own partial P).  MODE | 8 (NET_FWD_SAVE, NET_BWD): the training sweep's launches, which also store
+// two to a CU; each pass leaves its own partial P).  MODE | NET_STORE (NET_FWD_SAVE, NET_BWD): the training sweep's launches, which also store
 // their hidden tensors planar (NetArgs::st1 / st2) -- lane n of a wave then holds the ADJACENT pixels 2 n, 2 n + 1 (not n, 16 + n), so
 // that the values leave as 8-byte pairs, one full 128-byte line per hidden row and instruction; the stores are counted into the op-end
 // waits (they stay in flight across a barrier), which is why the host takes the form only where every wave is full (Q % 128 == 0).
@@ -39,15 +39,15 @@ constexpr int CO_PSTR = 132;        // fused coupling: floats per LDS row of P (
 
 template <int KIN, int MOUT, int NF, int MODE>
 struct RingC {
-  static constexpr int MODE7 = MODE & 7;
+  static constexpr int MODE7 = net_dir<MODE>;
   using S = RingS<KIN, MOUT, NF, MODE7, 2>;            // per-wave tiling, weight image, epilogue constants: those of the two-pass form
-  static constexpr bool FUSE = (MODE & 16) != 0;
+  static constexpr bool FUSE = (MODE & NET_FUSE) != 0;
   static constexpr bool SAVE = MODE7 == NET_FWD_SAVE, BWD = MODE7 == NET_BWD;
   static constexpr bool MERGE = S::NMT <= 3;           // two passes in one workgroup: pass 0's sums of P stay in registers, P is written once
                                                        // (five row blocks, the 8-channel level: 40 registers the kernel does not have -- two partial buffers)
   static constexpr bool M0LAST = S::NMT % 3 == 2;      // the pass's last conv3 unit sits in M0 (units cycle D, M0, M1): the next pass asks for its unit 0 itself
-  static constexpr bool STORE = (MODE & 8) != 0;       // training: the launch also leaves its hidden tensors planar (NetArgs::st1 / st2)
-  static constexpr int MODEX = MODE & 15;              // what h3s_X sees: the mode and the store bit
+  static constexpr bool STORE = (MODE & NET_STORE) != 0;   // training: the launch also leaves its hidden tensors planar (NetArgs::st1 / st2)
+  static constexpr int MODEX = net_dir<MODE> | (MODE & NET_STORE);   // what h3s_X sees: the mode and the store bit
   static constexpr int NFH = S::NFH, NRB = S::NRB, NMT = S::NMT, KS = S::KS;
   static constexpr int UNITP = S::MAINP / 2;            // 1-KiB pieces per unit
   static constexpr int UNIT4 = S::MAIN4 / 2;            // float4 per unit
@@ -58,7 +58,7 @@ struct RingC {
   static constexpr int MASKN = BWD ? 2 * 4 * NF * 64 : 0;   // backward: LDS copy of the masks [mask1 | mask2][wave][hidden block][lane], entries
   static constexpr size_t LDS_BYTES = (size_t)3 * UNIT4 * 16 + (size_t)2 * S::K14 * 16 + (size_t)EPN * 4 + (size_t)MASKN * 2 +
                                       (FUSE ? (size_t)36 * CO_PSTR * 4 + CO_PX * 16 : 0);
-  static constexpr bool FITS = (MODE7 == NET_FWD || MODE7 == NET_FWD2 || SAVE || BWD) && !(MODE & 32) && (!STORE || ((SAVE || BWD) && !FUSE)) && S::NGRP == 1 && (NMT == 2 || NMT == 3 || (NMT == 5 && !STORE && !BWD)) &&
+  static constexpr bool FITS = (MODE7 == NET_FWD || MODE7 == NET_FWD2 || SAVE || BWD) && !(MODE & NET_HALF) && (!STORE || ((SAVE || BWD) && !FUSE)) && S::NGRP == 1 && (NMT == 2 || NMT == 3 || (NMT == 5 && !STORE && !BWD)) &&
                                (!FUSE || (MOUT == 36 && !BWD)) && KS <= 3 && NF % 4 == 0 && NFH >= 2 && NFH % 2 == 0 && UNITP % 4 == 0 && PPW == NG &&
                                2 * LDS_BYTES <= 160 * 1024 + 1;   // (diagnostic paddings aside)
   // training: vector-memory stores an op issues per wave (8 pairs of values per activated hidden block from X and from Z; a saving launch adds

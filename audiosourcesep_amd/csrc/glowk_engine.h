@@ -63,7 +63,7 @@ struct glowk_handle {
   int precision = GLOWK_PREC_F32;
   int range_policy = GLOWK_RANGE_ERROR;
   int64_t range_fallbacks = 0;
-  int64_t family_launches[7] = {0, 0, 0, 0, 0, 0, 0};   // coupling-network launches by kernel family (glowk_launch.h: note_family)
+  int64_t family_launches[FAM_COUNT] = {};   // coupling-network launches by kernel family (glowk_launch.h: NetFamily; launch_net)
   int64_t fused_steps = 0;      // flow steps that ran as ONE network + coupling kernel (net_and_couple)
   int* d_flag = nullptr;        // sticky range flag (device), written by k_couple / k_bwd_light
   int* h_flag = nullptr;        // pinned host word it is read back into
@@ -155,7 +155,7 @@ namespace glowk_eng {
 struct TrainCtx {
   float* grad;     // [tr_n] flat gradient vector (device, caller owned)
   float scale;     // every gradient is scale * d sum_n log_prob / d theta
-  bool split;      // the sweep runs the fp16-split kernels (k_net_h3, MODE | 8): planar arrays in scaled units (StepGradArgs::scaled)
+  bool split;      // the sweep runs the fp16-split kernels (k_net_h3, MODE | NET_STORE): planar arrays in scaled units (StepGradArgs::scaled)
   hipEvent_t sums_ready = nullptr;   // recorded on the sweep's stream once every ActNorm / 1x1 sum (and the range flag, the gradient maxima) is final
 };
 
@@ -163,7 +163,8 @@ struct TrainCtx {
 int check_ready(glowk_handle* h, int N);
 int ensure_save(glowk_handle* h, int N);
 NetArgs net_args(glowk_handle* h, const Level& lv, const StepDev& sd, const float* vin, int in_stride, int in_off, int N);
-int launch_net_raw(int c, int F, const NetArgs& a, int mode, hipStream_t s, bool dry = false);
+NetCall net_call(const glowk_handle* h, int dir, bool store = false, bool split = true);
+NetLaunch launch_net_raw(int c, int F, const NetArgs& a, NetCall call, hipStream_t s, bool dry = false);
 int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_t s, bool save = false, bool keep_hidden = false);
 int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* dx, hipStream_t s, TrainCtx* tc = nullptr);
 int launch_prior(glowk_handle* h, const float* z, int N, float* logp_dev, hipStream_t s);     // k_prior: log N(z) + the accumulated log-det

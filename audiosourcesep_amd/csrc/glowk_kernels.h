@@ -58,9 +58,9 @@ struct NetArgs {
   float bnorm;           // split kernels, backward network (linear in its input): every pixel's gathered gradient vector is scaled by the
                          // power of two that brings its largest magnitude into [bnorm, 2 bnorm) before the split, and the pixel's outputs
                          // are scaled back (exact): no gradient magnitude can leave the fp16 range, small pixels keep all their bits
-  // ---- coupling fused into k_net_h3s<..., MODE | 16> (fused_couple): what k_couple would have been given
-  int fuse;              // host side: ask the launch policy for the fused instance (it answers 100 instead of a number of partials;
-                         // 101: the co-resident form of it, 128-pixel workgroups -- k_couple_edge is told, EdgeArgs::pxw)
+  // ---- coupling fused into k_net_h3s<..., MODE | NET_FUSE> (fused_couple): what k_couple would have been given
+  int fuse;              // host side: ask the launch policy for the fused instance (its answer names the fused form and its pixels
+                         // per workgroup, NetLaunch::fused_px: 128 for the co-resident form -- k_couple_edge is told, EdgeArgs::pxw)
   int co;                // host side: the co-resident form (glowk_co.h) may be taken where it has an instance
   const float* fz_b3;    // [C] conv3 bias
   const float* fz_A;     // post affine [C][C] or null (forward: the NEXT step's ActNorm + 1x1; inverse: this step's inverse 1x1 + ActNorm)
@@ -181,6 +181,13 @@ __device__ __forceinline__ void stage_range(const float4* __restrict__ src, floa
 enum { NET_FWD = 0, NET_FWD_SAVE = 1, NET_BWD = 2,
        NET_FWD2 = 3 };   // k_net_h3s only: plain forward with TWO split terms per product (activations rounded to fp16 once,
                          // weights still hi + lo): ~1e-5-class log_prob instead of fp32-class, 2/3 of the MFMAs
+// The MODE argument of the split kernels is the direction above plus these flags (the values are part of every instance's name)
+constexpr int NET_STORE = 8;    // training: the launch also stores its hidden tensors planar (NetArgs::st1 / st2)
+constexpr int NET_FUSE = 16;    // the coupling fused into the network kernel (fused_couple): plain forward directions
+constexpr int NET_HALF = 32;    // k_net_h3s with ONE 16-pixel half per wave: 128-pixel workgroups, four passes
+template <int MODE>
+constexpr int net_dir = MODE & 7;   // the direction of a MODE: NET_FWD, NET_FWD_SAVE, NET_BWD or NET_FWD2.  (A variable, not a
+                                    // function: a call in a kernel's run-time condition is not folded up front and changes the code.)
 
 // select word j of a small register array with a wave-uniform index (v_cndmask chain; no dynamic register indexing)
 template <int N>
@@ -478,7 +485,7 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 // need the registers, and for small grids, where each pass becomes a workgroup of its own).
 template <int KIN, int MOUT, int NF, int MODE, int NP>
 struct RingH {
-  static constexpr bool BWD = (MODE & 7) == NET_BWD;
+  static constexpr bool BWD = net_dir<MODE> == NET_BWD;
   static constexpr int NFH = NF / NP;                             // accumulator tiles (hidden 32-blocks) per pass
   static constexpr int K1 = 9 * KIN;
   static constexpr int KROWS = K1 + (BWD ? 0 : 1);                // forward: a spare k row carries conv1's bias
@@ -656,7 +663,7 @@ struct H3Ctx {                      // wave-uniform pointers of the kernel (LDS 
 
 // activation epilogue of 16 accumulator values: forward max(acc * sc, 0) (+ the ReLU decisions as bits), backward
 // acc * sc where the forward pass's ReLU was open
-// (MODE & 8: training -- the 16 activation values, in the scaled units they are split in, also go to a planar [F][Q] array:
+// (MODE & NET_STORE: training -- the 16 activation values, in the scaled units they are split in, also go to a planar [F][Q] array:
 //  st_blk = wave-uniform base of the hidden block's 32 rows, st_lane = this lane's byte offset, st_row = bytes per row)
 template <int MODE>
 __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned mask, h8 (&bh)[2], h8 (&bl)[2], bool do_st = false,
@@ -673,18 +680,18 @@ __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned
       const float t[2] = {t2.x, t2.y};
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        if ((MODE & 7) == NET_BWD) v[j + e] = __int_as_float(__float_as_int(t[e]) & __builtin_amdgcn_sbfe((int)mask, r + e, 1));   // bit ? t : 0
+        if (net_dir<MODE> == NET_BWD) v[j + e] = __int_as_float(__float_as_int(t[e]) & __builtin_amdgcn_sbfe((int)mask, r + e, 1));   // bit ? t : 0
         else {
           v[j + e] = fmaxf(t[e], 0.0f);
-          if ((MODE & 7) == NET_FWD_SAVE) bits |= (acc[r + e] > 0.0f ? 1u : 0u) << (r + e);
+          if (net_dir<MODE> == NET_FWD_SAVE) bits |= (acc[r + e] > 0.0f ? 1u : 0u) << (r + e);
         }
       }
     }
-    if ((MODE & 8) && do_st) {
+    if ((MODE & NET_STORE) && do_st) {
       unsigned off = st_lane + (unsigned)(16 * s) * st_row;      // rows 8 (r >> 2) + (r & 3): registers 8 s .. 8 s + 7 = rows 16 s + {0..3, 8..11}
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float sv = (MODE & 7) == NET_BWD ? v[j] * stu : v[j];      // backward: back in the pixel's own units (NetArgs::bnorm)
+        const float sv = net_dir<MODE> == NET_BWD ? v[j] * stu : v[j];      // backward: back in the pixel's own units (NetArgs::bnorm)
         asm volatile("global_store_dword %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(sv), "s"(st_base) : "memory");
         off += (j == 3 ? 5u : 1u) * st_row;
       }
@@ -695,12 +702,12 @@ __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned
 }
 
 // end of an X phase.  In pass 0 a saving launch stores the ReLU mask of the hidden block from here (1 store per wave) and a training
-// launch (MODE & 8) the block itself (16 planar stores): the wave's YOUNGEST memory operations -- everything the phase has to wait
+// launch (MODE & NET_STORE) the block itself (16 planar stores): the wave's YOUNGEST memory operations -- everything the phase has to wait
 // for (the DMA requested during the previous Y) is older, and vmcnt counts in issue order, so the stores stay in flight instead of
 // exposing their write latency at every one of the 16 X phases
 template <int MODE, int PASS, int NSTV>
 __device__ __forceinline__ void h3_x_end(const H3Ctx& c) {
-  constexpr int NST = ((MODE & 8) ? NSTV : 0) + (((MODE & 7) == NET_FWD_SAVE) ? 1 : 0);   // (NSTV: value stores of a training launch per X phase)
+  constexpr int NST = ((MODE & NET_STORE) ? NSTV : 0) + ((net_dir<MODE> == NET_FWD_SAVE) ? 1 : 0);   // (NSTV: value stores of a training launch per X phase)
   if constexpr (NST != 0 && PASS == 0) {
     if (c.wok) {      // (a wave without a valid pixel issues no store: its youngest operations are the DMA)
       __builtin_amdgcn_s_waitcnt((NST & 15) | 0x0F70 | ((NST >> 4) << 14));   // vmcnt(NST)
@@ -722,7 +729,7 @@ __device__ __forceinline__ void h3_X(const NetArgs& a, const H3Ctx& c, int fi, c
   for (int r = 0; r < 16; ++r) h1[r] = 0.0f;
   const h8* k1 = reinterpret_cast<const h8*>(KP ? c.k1s1 : c.k1s0) + lane;   // [s][hi|lo][64]
   unsigned mask = 0;
-  if ((MODE & 7) == NET_BWD) mask = c.mkl[((size_t)(8 + (threadIdx.x >> 6)) * NF + fi) * 64 + lane];  // mask2: the ReLU after conv2
+  if (net_dir<MODE> == NET_BWD) mask = c.mkl[((size_t)(8 + (threadIdx.x >> 6)) * NF + fi) * 64 + lane];  // mask2: the ReLU after conv2
   if constexpr (G::KS <= 3) {       // all operand reads in flight before the first MFMA
     h8 kf[2 * G::KS];
 #pragma unroll
@@ -735,10 +742,10 @@ __device__ __forceinline__ void h3_X(const NetArgs& a, const H3Ctx& c, int fi, c
     for (int s = 0; s < G::KS; ++s) h1 = mfma3(k1[(2 * s + 0) * 64], k1[(2 * s + 1) * 64], xh[s], xl[s], h1);
   }
   const int stq = (int)c.wblk * 32 + (lane & 31);
-  const unsigned bits = h3_act<MODE>(h1, a.sc1, mask, bh, bl, (MODE & 8) && PASS == 0 && stq < a.Q,
-                                     (MODE & 8) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
+  const unsigned bits = h3_act<MODE>(h1, a.sc1, mask, bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+                                     (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                      ((unsigned)(4 * (lane >> 5)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u, c.ub[0]);
-  if ((MODE & 7) == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
+  if (net_dir<MODE> == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
 }
 
 // Y: main contraction's contribution of one hidden block to this pass's NFH accumulator tiles (chunk in `slot`).  The wave
@@ -821,11 +828,11 @@ __device__ __forceinline__ void h3_Z(const NetArgs& a, const H3Ctx& c, const flo
     const int ml = first_group ? mt : mt - G::G0N;     // this row tile's accumulator within its group
     if (ml == 0) {
       unsigned mask = 0;
-      if ((MODE & 7) == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
-      const unsigned bits = h3_act<MODE>(acc2[fo], a.sc2, mask, bh, bl, (MODE & 8) && qok,
-                                         (MODE & 8) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
+      if (net_dir<MODE> == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
+      const unsigned bits = h3_act<MODE>(acc2[fo], a.sc2, mask, bh, bl, (MODE & NET_STORE) && qok,
+                                         (MODE & NET_STORE) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
                                          ((unsigned)(4 * hh) * (unsigned)a.Q + (unsigned)q) * 4u, (unsigned)a.Q * 4u, c.ub[0]);
-      if ((MODE & 7) == NET_FWD_SAVE && first_group && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
+      if (net_dir<MODE> == NET_FWD_SAVE && first_group && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
     }
     if (fo == 0) {
 #pragma unroll
@@ -837,7 +844,7 @@ __device__ __forceinline__ void h3_Z(const NetArgs& a, const H3Ctx& c, const flo
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = mt * 32 + mfma_row(r, hh);
-        if (m < M3 && qok) Pp[(size_t)m * a.Q + q] = (MODE & 7) == NET_BWD ? acc3[ml][r] * (a.sc3 * c.ub[0])
+        if (m < M3 && qok) Pp[(size_t)m * a.Q + q] = net_dir<MODE> == NET_BWD ? acc3[ml][r] * (a.sc3 * c.ub[0])
                                                      : PASS == 0 ? fmaf(acc3[ml][r], a.sc3, pb[m]) : acc3[ml][r] * a.sc3;
       }
     }
@@ -865,7 +872,7 @@ __device__ __forceinline__ void h3_pass(const NetArgs& a, const H3Ctx& c, const 
 #pragma unroll
   for (int fo = 0; fo < NFH; ++fo)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc2[fo][r] = (MODE & 7) == NET_BWD ? 0.0f : epl[f2base + fo * 32 + mfma_row(r, hh)];   // conv2 bias (scaled)
+    for (int r = 0; r < 16; ++r) acc2[fo][r] = net_dir<MODE> == NET_BWD ? 0.0f : epl[f2base + fo * 32 + mfma_row(r, hh)];   // conv2 bias (scaled)
 
   h8 bh[2], bl[2];
 #pragma nounroll
@@ -909,7 +916,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
   using G = RingH<KIN, MOUT, NF, MODE, NP>;
   constexpr int K1 = G::K1;
   constexpr int KS = G::KS;
-  constexpr int SGN = ((MODE & 7) == NET_BWD) ? -1 : 1;   // backward gathers at q - d(tap)
+  constexpr int SGN = (net_dir<MODE> == NET_BWD) ? -1 : 1;   // backward gathers at q - d(tap)
   static_assert(G::FITS, "shape");
 
   __shared__ float4 slotA[G::MAIN4];
@@ -945,12 +952,12 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
   if (!g) {
     stage4<G::MAINP, 60>(G::main_chunk(c.img, solo_pass, 0), slotA, c.w4, c.voff);       // main chunk 0
     stage4<G::MAINP, 61>(G::out_chunk(c.img, solo_pass, 0), slotD, c.w4, c.voff);        // first output chunk
-    if ((MODE & 7) == NET_BWD)   // the forward pass's ReLU decisions of this workgroup's 8 column blocks: [mask1 | mask2][wave][block][lane]
+    if (net_dir<MODE> == NET_BWD)   // the forward pass's ReLU decisions of this workgroup's 8 column blocks: [mask1 | mask2][wave][block][lane]
       stage4<NF, 64>(reinterpret_cast<const float4*>(a.mask1 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(mkl), c.w4, c.voff);
   } else {
     stage4<G::K1P, 62>(c.k1img, k1slot0, c.w4, c.voff);                                   // small-conv operands of blocks 0, 1
     stage4<G::K1P, 63>(c.k1img + G::K14, k1slot1, c.w4, c.voff);
-    if ((MODE & 7) == NET_BWD)
+    if (net_dir<MODE> == NET_BWD)
       stage4<NF, 65>(reinterpret_cast<const float4*>(a.mask2 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(mkl + 8 * NF * 64), c.w4, c.voff);
   }
   // im2col fragments of this lane's pixel: k-step s holds k = 16 s + 8 hh + j (natural order), scaled and split
@@ -962,7 +969,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
     const int rem = qq % hw;
     const int i = rem / a.w, j0 = rem % a.w;
     const float* base = a.vin + (long)qq * a.in_stride + a.in_off;
-    if constexpr ((MODE & 7) == NET_BWD) {
+    if constexpr (net_dir<MODE> == NET_BWD) {
       // the backward network is linear: normalise the pixel's gradient vector (its two lanes hh = 0, 1 hold it) by a power of two
       float v[KS][8];
 #pragma unroll
@@ -971,9 +978,9 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
         xmax = range8(xmax, v[s]);
       }
       xmax = nan_max(xmax, __shfl_xor(xmax, 32, 64));
-      // (training, MODE & 8: the hiddens this launch stores feed GEMMs over ALL pixels, so one scale has to serve the whole
+      // (training, MODE & NET_STORE: the hiddens this launch stores feed GEMMs over ALL pixels, so one scale has to serve the whole
       //  launch -- the producer pre-scaled g_o by a host-chosen power of two, BwdArgs::go_scale, and the static bound xlim checks it)
-      const float fac = (MODE & 8) ? 1.0f : pixel_norm(xmax, a.bnorm, c.ub[0]);
+      const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(xmax, a.bnorm, c.ub[0]);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
 #pragma unroll
@@ -990,11 +997,11 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
       }
     }
   }
-  if ((MODE & 7) != NET_BWD)
+  if (net_dir<MODE> != NET_BWD)
     for (int i = tid; i < G::EPN; i += 512) epl[i] = a.eph[i];
   // forward: beyond this input magnitude the host cannot rule out an fp16 overflow; backward (normalised per pixel): only a
   // non-finite gradient can
-  if ((((MODE & 7) == NET_BWD && !(MODE & 8)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
+  if (((net_dir<MODE> == NET_BWD && !(MODE & NET_STORE)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
   if (a.xmax_out) range_probe(a.xmax_out, xmax);           // (diagnostic runs only: how far below the limit do the inputs stay?)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                                         // constants and the first chunks visible to every wave
@@ -1030,12 +1037,12 @@ constexpr int FUSE_PSTR = 260;     // fused coupling: floats per LDS row of P: 4
                                    // quarters (kq) of a 16 x 16 accumulator tile store to disjoint banks
 constexpr int FUSE_EW = 64;        // pixels per row slot of the edge buffer
 
-// KIN / MOUT / MODE / NP as for RingH; MODE | 16: the coupling fused into the kernel (fused_couple)
+// KIN / MOUT / MODE / NP as for RingH; MODE | NET_FUSE: the coupling fused into the kernel (fused_couple)
 template <int KIN, int MOUT, int NF, int MODE, int NP>
 struct RingS {
-  static constexpr bool BWD = (MODE & 7) == NET_BWD;
-  static constexpr bool FUSE = (MODE & 16) != 0;                   // coupling fused into the kernel (see fused_couple); plain forward modes only
-  static constexpr int PXH = (MODE & 32) ? 1 : 2;                  // 16-pixel halves per wave.  MODE | 32: ONE half -- a workgroup of 128 pixels with
+  static constexpr bool BWD = net_dir<MODE> == NET_BWD;
+  static constexpr bool FUSE = (MODE & NET_FUSE) != 0;            // coupling fused into the kernel (see fused_couple); plain forward modes only
+  static constexpr int PXH = (MODE & NET_HALF) ? 1 : 2;           // 16-pixel halves per wave.  MODE | NET_HALF: ONE half -- a workgroup of 128 pixels with
                                                                    // half the MFMAs and half the epilogue work per phase: for grids that leave CUs
                                                                    // idle (latency per launch is what counts there) and for shapes whose small-conv
                                                                    // fragments (KS k-steps x PXH halves x 2 registers x 4) need the room
@@ -1086,7 +1093,7 @@ struct RingS {
   // stores are ~10 % of the kernel's time -- skipping two thirds of them made a pass 7 % faster -- so half of them is worth having;
   // the consumer reads one partial buffer instead of two.)  Plain forward modes only: the saving pass keeps its two buffers.
   static constexpr bool MERGE = PXH == 2 && NP == 2 && NGRP == 1 && NMT <= 3 &&
-                                ((MODE & 7) == NET_FWD || (MODE & 7) == NET_FWD2 || ((MODE & 7) == NET_BWD && NMT <= 2) || ((MODE & 7) == NET_FWD_SAVE && FUSE));   // (the saving pass keeps no P
+                                (net_dir<MODE> == NET_FWD || net_dir<MODE> == NET_FWD2 || (net_dir<MODE> == NET_BWD && NMT <= 2) || (net_dir<MODE> == NET_FWD_SAVE && FUSE));   // (the saving pass keeps no P
                                 // any more -- the coupling's pre-tanh inputs are what the backward pass reads -- so it can take the fused form too;
                                 // the 4-channel level's backward network (18 output rows: 16 registers) merges its two passes as well, the 8-channel
                                 // one (36 rows: 24 registers) spills 18 registers if it does)
@@ -1178,7 +1185,7 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
                                       const h8 (&xl)[(RingS<KIN, MOUT, NF, MODE, NP>::KS)][2], int lane, h8 (&bh)[2], h8 (&bl)[2]) {
   using G = RingS<KIN, MOUT, NF, MODE, NP>;
   unsigned mask = 0;
-  if ((MODE & 7) == NET_BWD) mask = c.mkl[c.mk2off + ((size_t)(threadIdx.x >> 6) * NF + fi) * 64 + lane];   // mask2: the ReLU after conv2
+  if (net_dir<MODE> == NET_BWD) mask = c.mkl[c.mk2off + ((size_t)(threadIdx.x >> 6) * NF + fi) * 64 + lane];   // mask2: the ReLU after conv2
   f32x4 h1[2][2];   // [row block][pixel half]
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -1196,7 +1203,7 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int hf = 0; hf < G::PXH; ++hf)
-          h1[rb][hf] = mfma3s<(MODE & 7) == NET_FWD2>(kf[(s * 2 + rb) * 2 + 0], kf[(s * 2 + rb) * 2 + 1], xh[s][hf], xl[s][hf], h1[rb][hf]);
+          h1[rb][hf] = mfma3s<net_dir<MODE> == NET_FWD2>(kf[(s * 2 + rb) * 2 + 0], kf[(s * 2 + rb) * 2 + 1], xh[s][hf], xl[s][hf], h1[rb][hf]);
   } else {
 #pragma unroll
     for (int s = 0; s < G::KS; ++s)
@@ -1204,27 +1211,27 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
       for (int rb = 0; rb < 2; ++rb) {
         const h8 ah = k1[((s * 2 + rb) * 2 + 0) * 64], al = k1[((s * 2 + rb) * 2 + 1) * 64];
 #pragma unroll
-        for (int hf = 0; hf < G::PXH; ++hf) h1[rb][hf] = mfma3s<(MODE & 7) == NET_FWD2>(ah, al, xh[s][hf], xl[s][hf], h1[rb][hf]);
+        for (int hf = 0; hf < G::PXH; ++hf) h1[rb][hf] = mfma3s<net_dir<MODE> == NET_FWD2>(ah, al, xh[s][hf], xl[s][hf], h1[rb][hf]);
       }
   }
   unsigned bits = 0;
   if constexpr (PAIR) {      // (every wave full: the host's condition for the form)
     static_assert(G::PXH == 2, "pairs: two pixel halves per wave");
     const int stq = (int)c.wblk * 32 + 2 * (lane & 15);
-    if constexpr ((MODE & 8) && PASS == 0)
-      bits = h3s_act_pair<(MODE & 7), true>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q),
+    if constexpr ((MODE & NET_STORE) && PASS == 0)
+      bits = h3s_act_pair<net_dir<MODE>, true>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q),
                                             ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u);
-    else bits = h3s_act_pair<(MODE & 7), false>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, nullptr, 0u, 0u);
+    else bits = h3s_act_pair<net_dir<MODE>, false>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, nullptr, 0u, 0u);
   } else {
 #pragma unroll
     for (int hf = 0; hf < G::PXH; ++hf) {
       const int stq = (int)c.wblk * (16 * G::PXH) + 16 * hf + (lane & 15);
-      bits |= h3s_act<(MODE & 7), (MODE & 8) != 0>(h1[0][hf], h1[1][hf], a.sc1, mask >> (8 * hf), bh[hf], bl[hf], (MODE & 8) && PASS == 0 && stq < a.Q,
-                                                   (MODE & 8) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
+      bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0>(h1[0][hf], h1[1][hf], a.sc1, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+                                                   (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                                    ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u) << (8 * hf);
     }
   }
-  if ((MODE & 7) == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
+  if (net_dir<MODE> == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
 }
 
 // Y: conv2 contribution of one hidden block (one k-step of 32) to the pass's NRB x 2 accumulator tiles; same pipelining and
@@ -1268,7 +1275,7 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
     if constexpr (G::PXH == 2) acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
     acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
     if constexpr (G::PXH == 2) acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
-    if ((MODE & 7) != NET_FWD2) {
+    if (net_dir<MODE> != NET_FWD2) {
       acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
       if constexpr (G::PXH == 2) acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
       acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], acc2[o1][0], 0, 0, 0);
@@ -1314,28 +1321,28 @@ __device__ __forceinline__ void h3s_Z(const NetArgs& a, const H3Ctx& c, const fl
       const int ml = mt % 6;                             // this row block's accumulator within its group
       if (ml == 0) {
         unsigned mask = 0, bits = 0;
-        if ((MODE & 7) == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
+        if (net_dir<MODE> == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
 #pragma unroll
         for (int hf = 0; hf < G::PXH; ++hf)
-          bits |= h3s_act<(MODE & 7), (MODE & 8) != 0>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf], (MODE & 8) && qok[hf],
-                                                       (MODE & 8) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
+          bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && qok[hf],
+                                                       (MODE & NET_STORE) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
                                                        ((unsigned)(4 * kq) * (unsigned)a.Q + (unsigned)q[hf]) * 4u, (unsigned)a.Q * 4u) << (8 * hf);
-        if ((MODE & 7) == NET_FWD_SAVE && t < NFH * G::G0N && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
+        if (net_dir<MODE> == NET_FWD_SAVE && t < NFH * G::G0N && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
       }
       if (fo == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { acc3[ml][0][r] = 0.0f; acc3[ml][1][r] = 0.0f; }
       }
       const h8 ah = buf[(tp * 2 + 0) * 64], al = buf[(tp * 2 + 1) * 64];
-      acc3[ml][0] = mfma3s<(MODE & 7) == NET_FWD2>(ah, al, bh[0], bl[0], acc3[ml][0]);
-      if constexpr (G::PXH == 2) acc3[ml][1] = mfma3s<(MODE & 7) == NET_FWD2>(ah, al, bh[1], bl[1], acc3[ml][1]);
+      acc3[ml][0] = mfma3s<net_dir<MODE> == NET_FWD2>(ah, al, bh[0], bl[0], acc3[ml][0]);
+      if constexpr (G::PXH == 2) acc3[ml][1] = mfma3s<net_dir<MODE> == NET_FWD2>(ah, al, bh[1], bl[1], acc3[ml][1]);
       if (fo == NFH - 1) {
 #pragma unroll
         for (int hf = 0; hf < G::PXH; ++hf)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int m = mt * 16 + 4 * kq + r;
-            const float val = (MODE & 7) == NET_BWD ? acc3[ml][hf][r] * (a.sc3 * c.ub[hf])
+            const float val = net_dir<MODE> == NET_BWD ? acc3[ml][hf][r] * (a.sc3 * c.ub[hf])
                               : PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[m]) : acc3[ml][hf][r] * a.sc3;
             if (MERGE && PASS == 0) { keep[ml][hf][r] = val; continue; }     // pass 1 adds it and stores once
             if constexpr (G::FUSE) {      // the per-tap outputs stay in the workgroup: LDS row m, pixel = wave * 32 + 16 hf + lane % 16
@@ -1370,7 +1377,7 @@ __device__ __forceinline__ void h3s_pass(const NetArgs& a, const H3Ctx& c, const
   for (int ob = 0; ob < NRB; ++ob)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float b = (MODE & 7) == NET_BWD ? 0.0f : epl[f2base + ob * 16 + 4 * kq + r];   // conv2 bias (scaled)
+      const float b = net_dir<MODE> == NET_BWD ? 0.0f : epl[f2base + ob * 16 + 4 * kq + r];   // conv2 bias (scaled)
       acc2[ob][0][r] = b;
       acc2[ob][1][r] = b;
     }
@@ -1504,7 +1511,7 @@ template <int KIN, int MOUT, int NF, int MODE, int NP, bool SPLIT>
 __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
   using G = RingS<KIN, MOUT, NF, MODE, NP>;
   constexpr int KS = G::KS;
-  constexpr int SGN = ((MODE & 7) == NET_BWD) ? -1 : 1;   // backward gathers at q - d(tap)
+  constexpr int SGN = (net_dir<MODE> == NET_BWD) ? -1 : 1;   // backward gathers at q - d(tap)
   static_assert(G::FITS, "shape");
 
   __shared__ float4 slotA[G::MAIN4];
@@ -1517,7 +1524,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
   __shared__ float plds[G::FUSE ? 36 * FUSE_PSTR : 1];   // fused coupling: the workgroup's per-tap outputs
   __shared__ float4 vstash[G::FUSE ? 256 : 1];           // ... and its pixels' four input channels (coupling input)
   static_assert(!G::FUSE || (G::MERGE && !SPLIT && MOUT == 36), "the fused coupling needs both passes in one workgroup and a 4-channel level");
-  static_assert(!(MODE & 8) || G::PXH == 1, "hidden stores (training): half-wave form only -- with two pixel halves a wave whose second half lies "
+  static_assert(!(MODE & NET_STORE) || G::PXH == 1, "hidden stores (training): half-wave form only -- with two pixel halves a wave whose second half lies "
                                             "beyond Q would issue fewer stores than h3_x_end's counted wait assumes");
 
   const int tid = threadIdx.x;
@@ -1547,12 +1554,12 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
   if (!g) {
     stage4<G::MAINP, 60>(G::main_chunk(c.img, solo_pass, 0), slotA, c.w4, c.voff);
     stage4<G::MAINP, 61>(G::out_chunk(c.img, solo_pass, 0), slotD, c.w4, c.voff);
-    if ((MODE & 7) == NET_BWD)   // the forward pass's ReLU decisions of this workgroup's 8 column blocks: [mask1 | mask2][wave][block][lane]
+    if (net_dir<MODE> == NET_BWD)   // the forward pass's ReLU decisions of this workgroup's 8 column blocks: [mask1 | mask2][wave][block][lane]
       stage4<NF, 64>(reinterpret_cast<const float4*>(a.mask1 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(mkl), c.w4, c.voff);
   } else {
     stage4<G::K1P, 62>(c.k1img, k1slot0, c.w4, c.voff);
     stage4<G::K1P, 63>(c.k1img + G::K14, k1slot1, c.w4, c.voff);
-    if ((MODE & 7) == NET_BWD)
+    if (net_dir<MODE> == NET_BWD)
       stage4<NF, 65>(reinterpret_cast<const float4*>(a.mask2 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(mkl + 8 * NF * 64), c.w4, c.voff);
   }
   // im2col fragments of this lane's two pixels: k-step s holds k = 32 s + 8 kq + j (natural order), scaled and split
@@ -1566,7 +1573,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
       const int rem = qq % hw;
       const int i = rem / a.w, j0 = rem % a.w;
       const float* base = a.vin + (long)qq * a.in_stride + a.in_off;
-      if constexpr ((MODE & 7) == NET_BWD) {
+      if constexpr (net_dir<MODE> == NET_BWD) {
         // linear network: the pixel's gradient vector (held by its four lanes kq = 0..3) is normalised by a power of two
         float v[KS][8];
         float pm = 0.0f;
@@ -1578,7 +1585,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
         pm = nan_max(pm, __shfl_xor(pm, 16, 64));
         pm = nan_max(pm, __shfl_xor(pm, 32, 64));
         xmax = nan_max(xmax, pm);
-        const float fac = (MODE & 8) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[hf]);     // (training: one scale per launch, BwdArgs::go_scale)
+        const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[hf]);     // (training: one scale per launch, BwdArgs::go_scale)
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
 #pragma unroll
@@ -1602,10 +1609,10 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
       vstash[tid] = qv < a.Q ? *reinterpret_cast<const float4*>(a.vin + (size_t)qv * 4) : float4{0.f, 0.f, 0.f, 0.f};
     }
   }
-  if ((MODE & 7) != NET_BWD)
+  if (net_dir<MODE> != NET_BWD)
     for (int i = tid; i < G::EPN; i += 512) epl[i] = a.eph[i];   // RingS::EPN <= RingH::EPN, same content
   // forward: the static bound; backward (normalised per pixel): only a non-finite gradient can leave the range
-  if ((((MODE & 7) == NET_BWD && !(MODE & 8)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
+  if (((net_dir<MODE> == NET_BWD && !(MODE & NET_STORE)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
   if (a.xmax_out) range_probe(a.xmax_out, xmax);           // (diagnostic runs only: how far below the limit do the inputs stay?)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();

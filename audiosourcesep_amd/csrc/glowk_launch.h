@@ -10,13 +10,36 @@
 #include <cstdlib>
 #include <string>
 
+// The 16 level shapes (CI, NF) with a launch_net_t instance: CI = c / 2 of a level, NF = n_filters / 32 (512, 384, 256, 128).
+// __graft_entry__.NET_SHAPES builds one glowk_net_inst.hip object per shape; a shape missing there fails the link.
+#define GLOWK_NET_SHAPES(X) X(2, 16) X(4, 16) X(8, 16) X(16, 16) X(2, 12) X(4, 12) X(8, 12) X(16, 12) \
+                            X(2, 8) X(4, 8) X(8, 8) X(16, 8) X(2, 4) X(4, 4) X(8, 4) X(16, 4)
+
+// A launch request.  dir: NET_FWD (plain forward network), NET_FWD_SAVE (the gradient path's forward network, which saves the ReLU
+// masks) or NET_BWD (the backward network).  arith: the exact fp32 kernel (k_net_f32) or the fp16 hi + lo split kernels, three terms
+// per product or two (the two-term form exists for the plain forward network only).  store: training -- the launch also stores its
+// hidden tensors planar (NetArgs::st1 / st2), in exact fp32 in any direction, in the three-term split for NET_FWD_SAVE / NET_BWD.
+enum NetArith { NET_EXACT, NET_SPLIT3, NET_SPLIT2 };
+struct NetCall { int dir; NetArith arith; bool store = false; };
+
+// The counters of glowk_kernel_families, in the order include/glowk.h documents
+enum NetFamily { FAM_F32, FAM_H3, FAM_H3S, FAM_H3S_HALF, FAM_FUSED, FAM_CO, FAM_Q, FAM_COUNT };
+
+// What a launch took.  A dry call answers the same without launching (the consumers of P need the answer before the launch).
+struct NetLaunch {
+  int np = 0;               // partial P buffers written (P + p * pstride); 0: this form was not taken -- or the coupling was fused
+  int family = FAM_F32;     // the kernel family that ran (FAM_F32 .. FAM_FUSED)
+  bool co = false;          // ... in its co-resident form (k_net_h3c, glowk_co.h: four-wave / 128-pixel workgroups, two to a CU)
+  bool q = false;           // ... in its small-grid form with all conv1 blocks first (k_net_h3q, glowk_q.h)
+  int fused_px = 0;         // > 0: the coupling ran inside the kernel (fused_couple), in workgroups of this many pixels: no P was
+                            // written, the step's output is in place but for the rows k_couple_edge finishes
+  bool failed = false;      // launch_fail() has set glowk_last_error()
+  explicit operator bool() const { return np > 0 || fused_px > 0; }   // a form was taken
+};
+
 namespace glowk_detail {
 
 int num_cus();                          // compute units of the current device (queried once); glowk.hip
-void note_co();                         // ... and that it took the co-resident form (after note_family)
-void note_q();                          // ... or the small-grid form with all conv1 blocks first (glowk_q.h)
-void note_family(int family);           // which kernel family a (non-dry) launch took: 0 k_net_f32, 1 k_net_h3 (32x32x16), 2 k_net_h3s
-                                        // (16x16x32), 3 its half-wave form, 4 the fused network + coupling kernel; glowk.hip
 void launch_fail(const std::string&);   // sets glowk_last_error(); glowk.hip
 
 // Switches (parity tests of one launch form against another): environment variables, read ONCE -- when the library is loaded and
@@ -35,12 +58,27 @@ struct EnvSwitches {
 };
 const EnvSwitches& env();
 
+// kernel shape of a direction at a level: the forward networks map CI channels to 18 CI outputs (9 taps x log s, t), the backward
+// network 2 CI gradient channels back to 9 CI
+template <int CI, int DIR>
+struct NetShape {
+  static constexpr int KIN = DIR == NET_BWD ? 2 * CI : CI;
+  static constexpr int MOUT = DIR == NET_BWD ? 9 * CI : 18 * CI;
+};
+
+// the exact fp32 kernel (the fallback of every split request whose shape has no instance)
+template <int CI, int NF, int DIR, bool STORE>
+NetLaunch launch_f32(const NetArgs& a, hipStream_t s, bool dry) {
+  using Sh = NetShape<CI, DIR>;
+  if (!dry) hipLaunchKernelGGL((k_net_f32<Sh::KIN, Sh::MOUT, NF, DIR, STORE>), dim3((a.Q + 127) / 128), dim3(256), 0, s, a);
+  return {1, FAM_F32};
+}
+
 // k_net_h3 / k_net_h3s launch forms.  NP = passes over the hidden width (2, or 4 where the shape needs the registers);
 // when NP workgroups per 256 pixels still fit the CUs in one round the passes become workgroups of their own (SPLIT):
-// 1/NP of the latency per launch.  Returns the number of partial P buffers the launch writes (= NP), 0 if no instance fits.
-// dry: decide only (the consumers of P need the same answer).
+// 1/NP of the latency per launch.  np = NP partial P buffers; not taken if no instance fits.
 template <int KIN, int MOUT, int NF, int MODE>
-int launch_h3(const NetArgs& a, hipStream_t s, bool dry) {
+NetLaunch launch_h3(const NetArgs& a, hipStream_t s, bool dry) {
   constexpr bool F2 = RingH<KIN, MOUT, NF, MODE, 2>::FITS, F4 = RingH<KIN, MOUT, NF, MODE, 4>::FITS;
   const int wgs = (a.Q + 255) / 256, cus = num_cus();
   if constexpr (F4) {
@@ -49,20 +87,18 @@ int launch_h3(const NetArgs& a, hipStream_t s, bool dry) {
       if (!dry) {
         if (split) hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
         else hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-        note_family(1);
       }
-      return 4;
+      return {4, FAM_H3};
     }
   }
   if constexpr (F2) {
     if (!dry) {
       if (2 * wgs <= cus) hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 2, true>), dim3(wgs, 2), dim3(512), 0, s, a);
       else hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
-      note_family(1);
     }
-    return 2;
+    return {2, FAM_H3};
   }
-  return 0;
+  return {};
 }
 
 // does the runtime place two workgroups of this co-resident instance on a CU?  (asked once per instance: one device type per process)
@@ -78,8 +114,8 @@ inline bool co_two_per_cu(Kernel kernel) {
 }
 
 template <int KIN, int MOUT, int NF, int MODE>
-int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
-  static_assert(!(MODE & 8), "no storing launches here: the co-resident branch does not check Q % 128 (co_train does)");
+NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
+  static_assert(!(MODE & NET_STORE), "no storing launches here: the co-resident branch does not check Q % 128 (launch_co_train does)");
   constexpr bool F2 = RingS<KIN, MOUT, NF, MODE, 2>::FITS, F4 = RingS<KIN, MOUT, NF, MODE, 4>::FITS;
   const int wgs = (a.Q + 255) / 256, cus = num_cus();
   if constexpr (F4) {
@@ -88,19 +124,17 @@ int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
       if (!dry) {
         if (split) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
         else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-        note_family(2);
       }
-      return 4;
+      return {4, FAM_H3S};
     }
   }
   if constexpr (F2) {
     const bool split = 2 * wgs <= cus;
     // the coupling fused into the kernel (glowk_kernels.h: fused_couple) where the caller asks for it (NetArgs::fuse: plain forward
-    // direction, geometry checked by the host), the level has four channels and both passes run in one workgroup: answers 100 =
-    // "no P was written, the step's output is in place (but for the rows k_couple_edge finishes)"
+    // direction, geometry checked by the host), the level has four channels and both passes run in one workgroup
     // the co-resident form (glowk_co.h: four-wave / 128-pixel workgroups, two to a CU), where the caller allows it (NetArgs::co) and it
-    // has an instance: on grids that fill the chip with it both passes in one workgroup -- fused (101: forward modes at the 4-channel
-    // level) or writing P once (1) --, on small grids (2 x Q/128 workgroups fit two to a CU) one pass per workgroup (2 partial P buffers)
+    // has an instance: on grids that fill the chip with it both passes in one workgroup -- fused (forward modes at the 4-channel
+    // level) or writing P once --, on small grids (2 x Q/128 workgroups fit two to a CU) one pass per workgroup (2 partial P buffers)
     if constexpr (RingC<KIN, MOUT, NF, MODE>::FITS) {
       const int wgc = (a.Q + CO_PX - 1) / CO_PX;
       const bool co_ok = a.co && !env().co_off;
@@ -108,75 +142,73 @@ int launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
       //  96 x 64: the eight-wave kernel would run one two-pass workgroup on 70 % of the CUs; this form runs its workgroups two to a CU in
       //  one round up to 2 x CUs, two rounds up to 4 x CUs)
       if (co_ok && wgc > cus) {
-        if constexpr (RingC<KIN, MOUT, NF, MODE | 16>::FITS) {
+        if constexpr (RingC<KIN, MOUT, NF, MODE | NET_FUSE>::FITS) {
           // (the form only pays with TWO workgroups per CU -- 2 x 78.8 KB of LDS, 2 x 4 x 248 VGPRs: ask the runtime once per instance, and
           //  keep the eight-wave kernel where a driver / device leaves room for one)
-          if (a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | 16, false>)) {
-            if (!dry) { hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | 16, false>), dim3(wgc), dim3(256), 0, s, a); note_family(4); note_co(); }
-            return 101;
+          if (a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>)) {
+            if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>), dim3(wgc), dim3(256), 0, s, a);
+            return {0, FAM_FUSED, true, false, CO_PX};
           }
         }
         if (!a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, false>)) {
-          if (!dry) { hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, false>), dim3(wgc), dim3(256), 0, s, a); note_family(2); note_co(); }
-          return RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2;
+          if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, false>), dim3(wgc), dim3(256), 0, s, a);
+          return {RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2, FAM_H3S, true};
         }
       }
       if (co_ok && split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
-        if (!dry) { hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a); note_family(2); note_co(); }
-        return 2;
+        if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
+        return {2, FAM_H3S, true};
       }
     }
     if constexpr ((MODE == NET_FWD || MODE == NET_FWD2 || MODE == NET_FWD_SAVE) && MOUT == 36) {
-      if constexpr (RingS<KIN, MOUT, NF, MODE | 16, 2>::FITS && RingS<KIN, MOUT, NF, MODE | 16, 2>::MERGE) {
+      if constexpr (RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::FITS && RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::MERGE) {
         if (a.fuse && !split) {
-          if (!dry) { hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | 16, 2, false>), dim3(wgs), dim3(512), 0, s, a); note_family(4); }
-          return 100;
+          if (!dry) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_FUSE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
+          return {0, FAM_FUSED, false, false, 256};
         }
       }
     }
     if (!dry) {
       if (split) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 2, true>), dim3(wgs, 2), dim3(512), 0, s, a);
       else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
-      note_family(2);
     }
-    return (!split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2;     // (merged: the two passes' sums leave the kernel as one buffer)
+    return {(!split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2, FAM_H3S};   // (merged: the two passes' sums leave the kernel as one buffer)
   }
-  return 0;
+  return {};
 }
 
-// The 16x16x32 family with ONE 16-pixel half per wave (MODE | 32: 128-pixel workgroups, always four passes).  Twice the
+// The 16x16x32 family with ONE 16-pixel half per wave (MODE | NET_HALF: 128-pixel workgroups, always four passes).  Twice the
 // workgroups at half the work per phase: chosen where the 256-pixel workgroups with their passes as workgroups of their own
 // still leave half the CUs idle (latency-bound grids: the deeper levels at the reference's batch sizes of 30 / 32 tiles), and for
 // shapes whose small-conv fragments only fit the registers at one half per wave (the 32-channel level's backward network: K = 288).
 inline bool half_wave_grid(const NetArgs& a) { return 8 * ((a.Q + 255) / 256) <= num_cus(); }
 
 template <int KIN, int MOUT, int NF, int MODE>
-int launch_h3s_half(const NetArgs& a, hipStream_t s, bool dry) {
-  if constexpr (RingS<KIN, MOUT, NF, MODE | 32, 4>::FITS) {
-    if (a.max_np < 4) return 0;
+NetLaunch launch_h3s_half(const NetArgs& a, hipStream_t s, bool dry) {
+  if constexpr (RingS<KIN, MOUT, NF, MODE | NET_HALF, 4>::FITS) {
+    if (a.max_np < 4) return {};
     const int wgs = (a.Q + 127) / 128;
     // passes as workgroups of their own, each alone on its CU: the form with all conv1 blocks first (glowk_q.h), where it has an instance
     if constexpr (RingQ<KIN, MOUT, NF, MODE>::FITS) {
       if (4 * wgs <= num_cus() && !env().q_off) {
-        if (!dry) { hipLaunchKernelGGL((k_net_h3q<KIN, MOUT, NF, MODE>), dim3(wgs, 4), dim3(512), 0, s, a); note_family(3); note_q(); }
-        return 4;
+        if (!dry) hipLaunchKernelGGL((k_net_h3q<KIN, MOUT, NF, MODE>), dim3(wgs, 4), dim3(512), 0, s, a);
+        return {4, FAM_H3S_HALF, false, true};
       }
     }
     if (!dry) {
-      if (4 * wgs <= num_cus()) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | 32, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | 32, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-      note_family(3);
+      if (4 * wgs <= num_cus()) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_HALF, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
+      else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_HALF, 4, false>), dim3(wgs), dim3(512), 0, s, a);
     }
-    return 4;
+    return {4, FAM_H3S_HALF};
   }
-  return 0;
+  return {};
 }
 
 // the saving forward pass and the backward pass of a level must agree on the form (their ReLU-mask layouts differ: one entry per
-// pixel block of a wave): both have a half-wave instance
-template <int CI, int NF>
+// pixel block of a wave): both have a half-wave instance (STORE: the training sweep's launches, which also store their hiddens)
+template <int CI, int NF, int STORE = 0>
 constexpr bool half_ok() {
-  return RingS<CI, 18 * CI, NF, NET_FWD_SAVE | 32, 4>::FITS && RingS<2 * CI, 9 * CI, NF, NET_BWD | 32, 4>::FITS;
+  return RingS<CI, 18 * CI, NF, NET_FWD_SAVE | STORE | NET_HALF, 4>::FITS && RingS<2 * CI, 9 * CI, NF, NET_BWD | STORE | NET_HALF, 4>::FITS;
 }
 // ... and for this level the half-wave form is the ONLY split form of the gradient path (no 256-pixel instance of the backward network)
 template <int CI, int NF>
@@ -184,19 +216,16 @@ constexpr bool half_only() {
   return half_ok<CI, NF>() && !(RingS<2 * CI, 9 * CI, NF, NET_BWD, 2>::FITS || RingS<2 * CI, 9 * CI, NF, NET_BWD, 4>::FITS) &&
          !(RingH<2 * CI, 9 * CI, NF, NET_BWD, 2>::FITS || RingH<2 * CI, 9 * CI, NF, NET_BWD, 4>::FITS);
 }
-// the same for the training sweep (MODE | 8: the launches also store their hidden tensors)
-template <int CI, int NF>
-constexpr bool half_train_ok() {
-  return RingS<CI, 18 * CI, NF, (NET_FWD_SAVE | 8) | 32, 4>::FITS && RingS<2 * CI, 9 * CI, NF, (NET_BWD | 8) | 32, 4>::FITS;
-}
+// ... of the training sweep: no 32x32x16 instance of both storing launches
 template <int CI, int NF>
 constexpr bool half_train_only() {
-  return half_train_ok<CI, NF>() && !((RingH<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), 2>::FITS || RingH<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), 4>::FITS) &&
-                                      (RingH<2 * CI, 9 * CI, NF, (NET_BWD | 8), 2>::FITS || RingH<2 * CI, 9 * CI, NF, (NET_BWD | 8), 4>::FITS));
+  constexpr int FS = NET_FWD_SAVE | NET_STORE, BS = NET_BWD | NET_STORE;
+  return half_ok<CI, NF, NET_STORE>() && !((RingH<CI, 18 * CI, NF, FS, 2>::FITS || RingH<CI, 18 * CI, NF, FS, 4>::FITS) &&
+                                           (RingH<2 * CI, 9 * CI, NF, BS, 2>::FITS || RingH<2 * CI, 9 * CI, NF, BS, 4>::FITS));
 }
 template <int CI, int NF>
 inline bool use_half_train(const NetArgs& a) {
-  if constexpr (!half_train_ok<CI, NF>()) return false;
+  if constexpr (!half_ok<CI, NF, NET_STORE>()) return false;
   return a.fam16 && a.max_np >= 4 && (half_train_only<CI, NF>() || half_wave_grid(a));
 }
 
@@ -227,103 +256,117 @@ inline bool co_split_grad(const NetArgs& a) {
   return false;
 }
 
-// The training sweep of a level in the co-resident form (k_net_h3c<..., MODE | 8>: the launches also store their hidden tensors): where
-// both the saving forward and the backward network have an instance, every workgroup is full (the kernels count their stores: Q % 128
-// == 0): more workgroups than CUs with both passes in a workgroup, otherwise a workgroup per pass.  Same question, same answer for
-// the two launches of a level (their ReLU-mask layouts must agree).
-template <int CI, int NF>
-inline bool co_train(const NetArgs& a) {
-  if constexpr (RingC<CI, 18 * CI, NF, (NET_FWD_SAVE | 8)>::FITS && RingC<2 * CI, 9 * CI, NF, (NET_BWD | 8)>::FITS) {
-    const int wgc = (a.Q + CO_PX - 1) / CO_PX, cus = num_cus();
-    if (!(a.co && !env().co_off && !env().co_train_off && a.fam16 && a.Q % CO_PX == 0 && a.max_np >= 2)) return false;
-    if (wgc > cus)
-      return co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), false>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, (NET_BWD | 8), false>);
-    return co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, (NET_FWD_SAVE | 8), true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, (NET_BWD | 8), true>);
-  }
-  return false;
-}
-// (after co_train said yes; returns the number of partial P buffers)
-template <int KIN, int MOUT, int NF, int MODE>
-int launch_co_train(const NetArgs& a, hipStream_t s, bool dry) {
-  if constexpr (RingC<KIN, MOUT, NF, MODE>::FITS) {
-    const int wgc = (a.Q + CO_PX - 1) / CO_PX;
-    const bool split = wgc <= num_cus();
-    if (!dry) {
-      if (split) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, false>), dim3(wgc), dim3(256), 0, s, a);
-      note_family(2); note_co();
-    }
-    return split ? 2 : 1;
-  }
-  return 0;
-}
-
 template <int CI, int NF>
 constexpr bool fam16_ok() {
   return RingS<CI, 18 * CI, NF, NET_FWD_SAVE, 2>::FITS && (RingS<2 * CI, 9 * CI, NF, NET_BWD, 2>::FITS || RingS<2 * CI, 9 * CI, NF, NET_BWD, 4>::FITS);
 }
 
-// returns the number of partial P buffers written (>= 1), or -1 on error
+// The training sweep of a level in the co-resident form (k_net_h3c<..., DIR | NET_STORE>): where both the saving forward and the
+// backward network have an instance and every workgroup is full (the kernels count their stores: Q % CO_PX == 0): more workgroups
+// than CUs with both passes in a workgroup (np = 1), otherwise a workgroup per pass (np = 2).  Same question, same answer for the two
+// launches of a level (their ReLU-mask layouts must agree).
+template <int CI, int NF, int DIR>
+NetLaunch launch_co_train(const NetArgs& a, hipStream_t s, bool dry) {
+  constexpr int FS = NET_FWD_SAVE | NET_STORE, BS = NET_BWD | NET_STORE;
+  if constexpr (RingC<CI, 18 * CI, NF, FS>::FITS && RingC<2 * CI, 9 * CI, NF, BS>::FITS) {
+    const int wgc = (a.Q + CO_PX - 1) / CO_PX, cus = num_cus();
+    if (!(a.co && !env().co_off && !env().co_train_off && a.fam16 && a.Q % CO_PX == 0 && a.max_np >= 2)) return {};
+    using Sh = NetShape<CI, DIR>;
+    if (wgc > cus) {
+      if (!(co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, FS, false>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, BS, false>))) return {};
+      if (!dry) hipLaunchKernelGGL((k_net_h3c<Sh::KIN, Sh::MOUT, NF, DIR | NET_STORE, false>), dim3(wgc), dim3(256), 0, s, a);
+      return {1, FAM_H3S, true};
+    }
+    if (!(co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, FS, true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, BS, true>))) return {};
+    if (!dry) hipLaunchKernelGGL((k_net_h3c<Sh::KIN, Sh::MOUT, NF, DIR | NET_STORE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
+    return {2, FAM_H3S, true};
+  }
+  return {};
+}
+
+// The plain forward network in the three-term split (half: the half-wave form may be taken); shapes without an instance run the
+// exact fp32 kernel
 template <int CI, int NF>
-int launch_net_t(const NetArgs& a, int mode, hipStream_t s, bool dry) {
-  const int ntiles = (a.Q + 127) / 128;
-  int np = 0;
-  switch (mode) {
-    case NET_FWD:      if (!dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD>), dim3(ntiles), dim3(256), 0, s, a); break;
-    case NET_FWD_SAVE: if (!dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD_SAVE>), dim3(ntiles), dim3(256), 0, s, a); break;
-    case NET_BWD:      if (!dry) hipLaunchKernelGGL((k_net_f32<2 * CI, 9 * CI, NF, NET_BWD>), dim3(ntiles), dim3(256), 0, s, a); break;
-    // training (exact fp32 only): the same two kernels, also storing their hidden tensors planar (NetArgs::st1 / st2)
-    case 7:            if (!dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD, true>), dim3(ntiles), dim3(256), 0, s, a); break;
-    case 8:            if (!dry) hipLaunchKernelGGL((k_net_f32<2 * CI, 9 * CI, NF, NET_BWD, true>), dim3(ntiles), dim3(256), 0, s, a); break;
-    // training in the split arithmetic: the 32x32x16 family's saving forward and backward launches, storing their hiddens (MODE | 8)
-    case 10:   // (dry: returns 0 when the shape has no instance -- glowk_param_grad asks before it chooses the arithmetic of the sweep)
-      if (use_half_train<CI, NF>(a)) np = launch_h3s_half<CI, 18 * CI, NF, (NET_FWD_SAVE | 8)>(a, s, dry);
-      if (!np && co_train<CI, NF>(a)) np = launch_co_train<CI, 18 * CI, NF, (NET_FWD_SAVE | 8)>(a, s, dry);
-      if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, (NET_FWD_SAVE | 8)>(a, s, dry);
-      if (!np) { if (dry) return 0; launch_fail("no split-arithmetic training instance for this shape"); return -1; }
-      break;
-    case 11:
-      if (use_half_train<CI, NF>(a)) np = launch_h3s_half<2 * CI, 9 * CI, NF, (NET_BWD | 8)>(a, s, dry);
-      if (!np && co_train<CI, NF>(a)) np = launch_co_train<2 * CI, 9 * CI, NF, (NET_BWD | 8)>(a, s, dry);
-      if (!np && a.RHp) np = launch_h3<2 * CI, 9 * CI, NF, (NET_BWD | 8)>(a, s, dry);
-      if (!np) { if (dry) return 0; launch_fail("no split-arithmetic training instance for this shape"); return -1; }
-      break;
-    case 9:            if (!dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD_SAVE, true>), dim3(ntiles), dim3(256), 0, s, a); break;   // saving forward pass that keeps its hiddens
-    case 3:   // f16x3 arithmetic: forward / forward with saves / backward; shapes without an instance run the exact fp32 kernel
-      if (a.RSp && half_wave_grid(a) && !a.fuse) np = launch_h3s_half<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD>), dim3(ntiles), dim3(256), 0, s, a);
-      break;
-    case 6:   // two-term forward (GLOWK_PREC_F16X2): 16x16x32 kernel only; without an instance, the three-term forms of case 3
-      if (a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD2>(a, s, dry);
-      if (!np && a.RSp) np = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
-      if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD>), dim3(ntiles), dim3(256), 0, s, a);
-      break;
-    case 4:
-      if (use_half<CI, NF>(a)) np = launch_h3s_half<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
-      if constexpr (fam16_ok<CI, NF>()) {
-        if (!np && a.fam16 && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
-      }
-      if (!np && a.RHp) np = launch_h3<CI, 18 * CI, NF, NET_FWD_SAVE>(a, s, dry);
-      if (!np && !dry) hipLaunchKernelGGL((k_net_f32<CI, 18 * CI, NF, NET_FWD_SAVE>), dim3(ntiles), dim3(256), 0, s, a);
-      break;
-    case 5:
-      if (use_half<CI, NF>(a)) np = launch_h3s_half<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
-      if constexpr (fam16_ok<CI, NF>()) {
-        if (!np && a.fam16 && (big_grid(a) || co_split_grad<CI, NF>(a))) np = launch_h3s<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
-      }
-      if (!np && a.RHp) np = launch_h3<2 * CI, 9 * CI, NF, NET_BWD>(a, s, dry);
-      if (!np && !dry) hipLaunchKernelGGL((k_net_f32<2 * CI, 9 * CI, NF, NET_BWD>), dim3(ntiles), dim3(256), 0, s, a);
-      break;
-    default: launch_fail("bad k_net mode"); return -1;
+NetLaunch launch_split3_fwd(const NetArgs& a, bool half, hipStream_t s, bool dry) {
+  NetLaunch r;
+  if (half && a.RSp && half_wave_grid(a) && !a.fuse) r = launch_h3s_half<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+  if (!r && a.RSp) r = launch_h3s<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+  if (!r && a.RHp) r = launch_h3<CI, 18 * CI, NF, NET_FWD>(a, s, dry);
+  if (!r) r = launch_f32<CI, NF, NET_FWD, false>(a, s, dry);
+  return r;
+}
+// ... in the two-term split (GLOWK_PREC_F16X2): the 16x16x32 kernel only (NET_FWD2); without an instance, the three-term forms but
+// the half-wave one
+template <int CI, int NF>
+NetLaunch launch_split2_fwd(const NetArgs& a, hipStream_t s, bool dry) {
+  NetLaunch r;
+  if (a.RSp) r = launch_h3s<CI, 18 * CI, NF, NET_FWD2>(a, s, dry);
+  return r ? r : launch_split3_fwd<CI, NF>(a, false, s, dry);
+}
+
+// The gradient path's saving forward (DIR = NET_FWD_SAVE) or backward network (NET_BWD) in the three-term split.  The two launches
+// of a level ask the same questions, so they take the same family.
+template <int CI, int NF, int DIR>
+NetLaunch launch_split_grad(const NetArgs& a, hipStream_t s, bool dry) {
+  using Sh = NetShape<CI, DIR>;
+  NetLaunch r;
+  if (use_half<CI, NF>(a)) r = launch_h3s_half<Sh::KIN, Sh::MOUT, NF, DIR>(a, s, dry);
+  if constexpr (fam16_ok<CI, NF>()) {
+    if (!r && a.fam16 && (big_grid(a) || co_split_grad<CI, NF>(a))) r = launch_h3s<Sh::KIN, Sh::MOUT, NF, DIR>(a, s, dry);
   }
-  if (!dry) {
+  if (!r && a.RHp) r = launch_h3<Sh::KIN, Sh::MOUT, NF, DIR>(a, s, dry);
+  if (!r) r = launch_f32<CI, NF, DIR, false>(a, s, dry);
+  return r;
+}
+
+inline NetLaunch net_failed(const std::string& m) { launch_fail(m); NetLaunch r; r.failed = true; return r; }
+
+// The training sweep in the three-term split: the same two launches, storing their hiddens.  No exact fallback (the sweep's weight
+// gradients expect the split units): not taken if the shape has no instance -- glowk_param_grad asks dry before it chooses the
+// arithmetic of the sweep.
+template <int CI, int NF, int DIR>
+NetLaunch launch_split_train(const NetArgs& a, hipStream_t s, bool dry) {
+  using Sh = NetShape<CI, DIR>;
+  constexpr int MODE = DIR | NET_STORE;
+  NetLaunch r;
+  if (use_half_train<CI, NF>(a)) r = launch_h3s_half<Sh::KIN, Sh::MOUT, NF, MODE>(a, s, dry);
+  if (!r) r = launch_co_train<CI, NF, DIR>(a, s, dry);
+  if (!r && a.RHp) r = launch_h3<Sh::KIN, Sh::MOUT, NF, MODE>(a, s, dry);
+  if (!r && !dry) return net_failed("no split-arithmetic training instance for this shape");
+  return r;
+}
+
+// exact fp32: the kernel of the direction, storing or not
+template <int CI, int NF, bool STORE>
+NetLaunch launch_exact(const NetArgs& a, int dir, hipStream_t s, bool dry) {
+  if (dir == NET_FWD) return launch_f32<CI, NF, NET_FWD, STORE>(a, s, dry);
+  if (dir == NET_FWD_SAVE) return launch_f32<CI, NF, NET_FWD_SAVE, STORE>(a, s, dry);
+  return launch_f32<CI, NF, NET_BWD, STORE>(a, s, dry);
+}
+
+// The policy: which kernel instance a request launches, on which grid.  A request with no launch form (a two-term or storing plain
+// forward split, a two-term saving or backward network, an unknown direction) fails.
+template <int CI, int NF>
+NetLaunch launch_net_t(const NetArgs& a, NetCall call, hipStream_t s, bool dry) {
+  const bool save = call.dir == NET_FWD_SAVE;
+  if (call.dir != NET_FWD && !save && call.dir != NET_BWD) return net_failed("bad k_net mode");
+  NetLaunch r;
+  if (call.arith == NET_EXACT) {
+    r = !call.store ? launch_exact<CI, NF, false>(a, call.dir, s, dry) : launch_exact<CI, NF, true>(a, call.dir, s, dry);
+  } else if (call.store) {
+    if (call.dir == NET_FWD || call.arith != NET_SPLIT3) return net_failed("bad k_net mode");
+    r = save ? launch_split_train<CI, NF, NET_FWD_SAVE>(a, s, dry) : launch_split_train<CI, NF, NET_BWD>(a, s, dry);
+  } else if (call.dir == NET_FWD) {
+    r = call.arith == NET_SPLIT3 ? launch_split3_fwd<CI, NF>(a, true, s, dry) : launch_split2_fwd<CI, NF>(a, s, dry);
+  } else {
+    if (call.arith != NET_SPLIT3) return net_failed("bad k_net mode");
+    r = save ? launch_split_grad<CI, NF, NET_FWD_SAVE>(a, s, dry) : launch_split_grad<CI, NF, NET_BWD>(a, s, dry);
+  }
+  if (!dry && !r.failed) {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { launch_fail(std::string("k_net: ") + hipGetErrorString(e)); return -1; }
+    if (e != hipSuccess) return net_failed(std::string("k_net: ") + hipGetErrorString(e));
   }
-  return np ? np : 1;
+  return r;
 }
 
 }  // namespace glowk_detail

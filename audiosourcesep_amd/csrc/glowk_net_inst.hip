@@ -8,5 +8,5 @@
 #include "glowk_launch.h"
 
 namespace glowk_detail {
-template int launch_net_t<GLOWK_INST_CI, GLOWK_INST_NF>(const NetArgs&, int, hipStream_t, bool);
+template NetLaunch launch_net_t<GLOWK_INST_CI, GLOWK_INST_NF>(const NetArgs&, NetCall, hipStream_t, bool);
 }

@@ -1,7 +1,7 @@
 // k_net_h3q: the small-grid form of the split coupling network with the conv1 blocks FIRST (round-3 verdict, item 3).
 //
 // At the reference's batch sizes (30 mixture tiles, training batch 32) the deeper levels launch a few dozen workgroups, each alone on its
-// CU, and a launch of the half-wave form (k_net_h3s<..., MODE | 32, 4, true>: 128 pixels, one pass per workgroup) is a chain of 16
+// CU, and a launch of the half-wave form (k_net_h3s<..., MODE | NET_HALF, 4, true>: 128 pixels, one pass per workgroup) is a chain of 16
 // dependent X_i -> Y_i phase pairs, 27-31 us per launch whatever the batch.  X_i does not depend on Y_{i-1} -- only Y accumulates -- so
 // this form takes X out of the chain, the hidden width in two halves (so that NF/2 x 8 registers hold split B fragments at a time):
 //     X half  conv1 + activation + split of NF/2 hidden blocks in batches of XB (2 XB interleaved MFMA chains; conv1 operands through a
@@ -25,8 +25,8 @@
 
 template <int KIN, int MOUT, int NF, int MODE>
 struct RingQ {
-  using S = RingS<KIN, MOUT, NF, MODE | 32, 4>;        // geometry, weight image and epilogue constants of the half-wave four-pass form
-  static constexpr int MODE7 = MODE & 7;
+  using S = RingS<KIN, MOUT, NF, MODE | NET_HALF, 4>;        // geometry, weight image and epilogue constants of the half-wave four-pass form
+  static constexpr int MODE7 = net_dir<MODE>;
   static constexpr bool BWD = MODE7 == NET_BWD;
   static constexpr int KS = S::KS, NFH = S::NFH, NRB = S::NRB;
   static constexpr int EPN = BWD ? 4 : S::EPN;          // (the backward network has no epilogue constants)
@@ -38,9 +38,9 @@ struct RingQ {
   static constexpr int NB = NF / XB;                    // X batches
   static constexpr int PPW = S::MAINP / 4;              // DMA instructions per group-0 wave and chunk
   static constexpr int GS = NRB % 4 == 0 ? 4 : 2;       // row blocks per group of MFMAs in Y (3 GS MFMAs, dependent ones GS apart)
-  static constexpr int XST = ((MODE7 == NET_FWD_SAVE) ? 1 : 0) + ((MODE & 8) ? 8 : 0);     // stores a pass-0 wave issues per X (ReLU mask, hidden values)
+  static constexpr int XST = ((MODE7 == NET_FWD_SAVE) ? 1 : 0) + ((MODE & NET_STORE) ? 8 : 0);     // stores a pass-0 wave issues per X (ReLU mask, hidden values)
   static constexpr bool FITS = S::FITS && LDS_BYTES <= 160 * 1024 && NF % (2 * XB) == 0 && NF % 4 == 0 && KS <= 5 && S::MAINP % 4 == 0 && NF >= 8 &&
-                               (MODE7 == NET_FWD || MODE7 == NET_FWD_SAVE || MODE7 == NET_BWD) && !(MODE & 16);
+                               (MODE7 == NET_FWD || MODE7 == NET_FWD_SAVE || MODE7 == NET_BWD) && !(MODE & NET_FUSE);
 };
 
 // op end: all but this wave's N youngest vector-memory operations are done, its LDS reads have retired, workgroup barrier
@@ -122,8 +122,8 @@ __device__ __forceinline__ void q_X_batch(const NetArgs& a, const H3Ctx& c, cons
     const int fi = B * XB + x;
     const int stq = (int)c.wblk * 16 + (lane & 15);
     h8 bh, bl;
-    const unsigned bits = h3s_act<MODE7, (MODE & 8) != 0>(h1[x][0], h1[x][1], a.sc1, mask[x], bh, bl, (MODE & 8) && PASS == 0 && stq < a.Q,
-                                                         (MODE & 8) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
+    const unsigned bits = h3s_act<MODE7, (MODE & NET_STORE) != 0>(h1[x][0], h1[x][1], a.sc1, mask[x], bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+                                                         (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                                          ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u);
     if (MODE7 == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
     bfh[fi % (NF / 2)] = bh;
@@ -236,7 +236,7 @@ __device__ __forceinline__ void q_pass(const NetArgs& a, const H3Ctx& c, const Q
   f32x4 acc3[S::G0N][2];
   f32x4 keep[S::G0N][2];                     // (never touched: a solo pass writes its own partial P)
   h8 bh[2], bl[2];
-  h3s_tail<KIN, MOUT, NF, MODE | 32, 4, 0, PASS, true>(a, c, epl, acc2, acc3, bh, bl, g, q, qok, lane, kq, keep, std::make_integer_sequence<int, 2 * S::NCH>());
+  h3s_tail<KIN, MOUT, NF, MODE | NET_HALF, 4, 0, PASS, true>(a, c, epl, acc2, acc3, bh, bl, g, q, qok, lane, kq, keep, std::make_integer_sequence<int, 2 * S::NCH>());
 }
 
 // grid (workgroups of 128 pixels, 4 passes); each workgroup runs ONE pass
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
       pm = nan_max(pm, __shfl_xor(pm, 16, 64));
       pm = nan_max(pm, __shfl_xor(pm, 32, 64));
       xmax = pm;
-      const float fac = (MODE & 8) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[0]);
+      const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[0]);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
 #pragma unroll
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
   }
   if (!G::BWD)
     for (int i = tid; i < G::EPN; i += 512) epl[i] = a.eph[i];
-  if (((G::BWD && !(MODE & 8)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
+  if (((G::BWD && !(MODE & NET_STORE)) ? !(xmax <= 3.0e38f) : !(xmax <= a.xlim)) && a.flag) *a.flag = 1;
   if (a.xmax_out) range_probe(a.xmax_out, xmax);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();

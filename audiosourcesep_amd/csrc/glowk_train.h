@@ -3,7 +3,7 @@
 //
 // The data-gradient sweep of glowk_log_prob_grad already walks the steps in reverse; the training sweep adds:
 //   1. the saving forward launch also stores  R1 = relu(conv1 + b1), R2 = relu(conv2 + b2)      planar [F][Q]
-//      (k_net_f32<.., STORE> / k_net_h3<.., MODE | 8>; kept for all steps, or recomputed per step when memory is short)
+//      (k_net_f32<.., STORE> / k_net_h3<.., MODE | NET_STORE>; kept for all steps, or recomputed per step when memory is short)
 //   2. the backward launch also stores        M2 = mask2 . conv3^T(g_o), M1 = mask1 . (K2 g_a2)   planar [F][Q]
 //   and then, for a whole level at a time (every kernel below takes a batch index = step; step by step when memory is short):
 //   3. k_im2col_planar                 Xcol[(tap, ci)][q] = v_b[q + d(tap)][ci] (+ a row of ones), Gcol[(tap, co)][q] = g_o[q - d(tap)][co]
@@ -502,7 +502,7 @@ struct StepGradArgs {
   const float* bn;      // [8][F]: gamma1, beta1, mean1, var1, gamma2, beta2, mean2, var2
   const float* ep;      // [6][F]: b1, g1, d1, b2, g2, d2 -- the step's folded BatchNorm block as the kernels read it (k_fold_bn / pack_step)
   float eps;
-  // scaled = 1: the planar arrays came from the split kernels (k_net_h3, MODE | 8) in the units those kernels split in:
+  // scaled = 1: the planar arrays came from the split kernels (k_net_h3, MODE | NET_STORE) in the units those kernels split in:
   //   A1 = ACT 2^e1[f] R1,  A2 = ACT 2^e2[f] R2  (g = m 2^e: the power of two of the BatchNorm gain is folded into the producer),
   //   G2 = ACT g2[f] M2 = ACT g_a2,  G1 = ACT g1[f] M1 = ACT g_a1  (the backward images carry the gains),  ACT = GLOWK_ACT_SCALE.
   // The GEMMs ran on those; the per-row factors are undone here (powers of two and the gains themselves; a gain of exactly zero

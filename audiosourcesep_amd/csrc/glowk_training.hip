@@ -496,7 +496,8 @@ static int param_grad_impl(glowk_handle* h, const float* x_dev, int N, float sca
     if (split) {      // ... and the launch policy has an instance of both storing kernels for this level at this batch size
       NetArgs pf = net_args(h, lv, sd, nullptr, lv.c, lv.c / 2, N), pb = net_args(h, lv, sd, nullptr, lv.c, 0, N);
       pb.RHp = sd.RHBp; pb.RSp = sd.RSBp;
-      split = launch_net_raw(lv.c, h->cfg.F, pf, 10, nullptr, true) > 0 && launch_net_raw(lv.c, h->cfg.F, pb, 11, nullptr, true) > 0;
+      split = launch_net_raw(lv.c, h->cfg.F, pf, net_call(h, NET_FWD_SAVE, true), nullptr, true) &&
+              launch_net_raw(lv.c, h->cfg.F, pb, net_call(h, NET_BWD, true), nullptr, true);
     }
   }
   h->precision = split ? GLOWK_PREC_F16X3 : GLOWK_PREC_F32;
