@@ -114,6 +114,11 @@ SYMBOLS = {
     "glowk_bss_xcorr": (_i, [_vp, _i, ctypes.c_int64, _vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp]),
     "glowk_bss_solve": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "glowk_bss_project": (_i, [_vp, ctypes.c_int64, _i, _i, _i, _vp, _i, ctypes.c_int64, _vp, _i, _vp, _i, _vp, _vp]),
+    "glowk_sp_stft": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp]),
+    "glowk_sp_istft": (_i, [_vp, _i, _i, ctypes.c_int64, _vp, _vp]),
+    "glowk_oracle_mask": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    "glowk_mwf": (_i, [_vp, _i, _i, _vp]),
+    "glowk_oracle_mel": (_i, [_vp, _vp, _i, ctypes.c_int64, _i, _i, ctypes.c_double, _vp, _vp]),
 }
 
 _lib = None

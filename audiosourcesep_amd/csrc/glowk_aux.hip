@@ -1,9 +1,11 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
-// the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h)
+// the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
+// systems (glowk_oracle.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
 #include "glowk_bsseval.h"
+#include "glowk_oracle.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -461,6 +463,118 @@ int glowk_bss_project(const double* sig_dev, int64_t nsampl, int nsrc, int nchan
   }
   (void)hipFreeAsync(part, s);
   if (e != hipSuccess) return fail(std::string("launch k_bss_project: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// ---- oracle separation systems (glowk_oracle.h) -----------------------------------------------------------------------------------
+namespace {
+constexpr int64_t SP_MAX_SAMPLES = (int64_t)1 << 40;
+constexpr int64_t SP_MAX_GRID = ((int64_t)1 << 31) - 1;
+unsigned stride_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)1 << 18)); }
+}
+
+int glowk_sp_stft(const float* x_dev, int nsig, int64_t n, float* spec_dev, void* stream) {
+  using namespace glowk_oracle;
+  if (!x_dev || !spec_dev) return fail("null tensor");
+  if (nsig < 0 || n < 1 || n > SP_MAX_SAMPLES) return fail("sp_stft: need nsig >= 0 and 1 <= n <= 2^40");
+  if (nsig == 0) return 0;
+  const int64_t T = sp_frames(n), ftiles = (T + 31) / 32;
+  if (nsig * ftiles > SP_MAX_GRID) return fail("sp_stft: too many signals x frames for one launch");
+  int dev;
+  if (int rc = audio_device({x_dev, spec_dev}, &dev, "sp_stft")) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  hipLaunchKernelGGL(k_sp_stft, dim3((unsigned)(nsig * ftiles), (NBIN + 127) / 128), dim3(256), 0, (hipStream_t)stream, x_dev, n, (int)T,
+                     (int)ftiles, c, reinterpret_cast<float2*>(spec_dev));
+  LAUNCHCHK("k_sp_stft");
+  return 0;
+}
+
+int glowk_sp_istft(const float* spec_dev, int nsig, int frames, int64_t length, float* out_dev, void* stream) {
+  using namespace glowk_oracle;
+  if (!spec_dev || !out_dev) return fail("null tensor");
+  if (nsig < 0 || frames < 2 || frames > sp_frames(SP_MAX_SAMPLES)) return fail("sp_istft: need nsig >= 0 and frames >= 2");
+  if (length < 0 || length > (int64_t)(frames - 1) * HOP) return fail("sp_istft: length must be in [0, (frames - 1) * 1024]");
+  if (nsig == 0 || length == 0) return 0;
+  const int64_t htiles = ((int64_t)frames - 1 + 31) / 32;
+  if (nsig * htiles > SP_MAX_GRID) return fail("sp_istft: too many signals x frames for one launch");
+  int dev;
+  if (int rc = audio_device({spec_dev, out_dev}, &dev, "sp_istft")) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  hipLaunchKernelGGL(k_sp_istft, dim3((unsigned)(nsig * htiles), HOP / 128), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float2*>(spec_dev), frames, (int)htiles, length, c, out_dev);
+  LAUNCHCHK("k_sp_istft");
+  return 0;
+}
+
+int glowk_oracle_mask(float* spec_dev, int nsrc, int nchan, int frames, int irm, double alpha, double theta, uint8_t* mask_dev, void* stream) {
+  using namespace glowk_oracle;
+  if (!spec_dev) return fail("null tensor");
+  if (nsrc < 1 || nsrc > 1024 || nchan < 1 || nchan > 1024 || frames < 1 || frames > sp_frames(SP_MAX_SAMPLES))
+    return fail("oracle_mask: need 1 <= nsrc, nchan <= 1024 and frames >= 1");
+  if (!std::isfinite(alpha) || std::isnan(theta)) return fail("oracle_mask: alpha must be finite and theta a number");
+  if (irm && mask_dev) return fail("oracle_mask: the mask output is for the binary mask only");
+  int dev;
+  if (int rc = audio_device({spec_dev, mask_dev}, &dev, "oracle_mask")) return rc;
+  DeviceGuard dg(dev);
+  MaskArgs a;
+  a.spec = reinterpret_cast<float2*>(spec_dev); a.plane = (int64_t)NBIN * frames; a.nsrc = nsrc; a.nchan = nchan; a.irm = irm ? 1 : 0;
+  a.alpha = alpha; a.theta = theta; a.mask = mask_dev;
+  hipLaunchKernelGGL(k_oracle_mask, dim3(stride_grid(nchan * a.plane)), dim3(256), 0, (hipStream_t)stream, a);
+  LAUNCHCHK("k_oracle_mask");
+  return 0;
+}
+
+int glowk_mwf(float* spec_dev, int nsrc, int frames, void* stream) {
+  using namespace glowk_oracle;
+  if (!spec_dev) return fail("null tensor");
+  if (nsrc < 1 || nsrc > MWF_MAX_SRC) return fail("mwf: nsrc must be in [1, 16]");
+  if (frames < 1 || frames > sp_frames(SP_MAX_SAMPLES)) return fail("mwf: frames must be >= 1");
+  int dev;
+  if (int rc = audio_device({spec_dev}, &dev, "mwf")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t s = (hipStream_t)stream;
+  double* stats = nullptr;                     // [nsrc][1025][4] doubles, then the matrices [nsrc][1025][8] double2
+  const size_t n_stats = (size_t)nsrc * NBIN * 4, n_mat = (size_t)nsrc * NBIN * 16;
+  HIPCHK(hipMallocAsync((void**)&stats, (n_stats + n_mat) * sizeof(double), s));
+  double2* rmat = reinterpret_cast<double2*>(stats + n_stats);
+  float2* spec = reinterpret_cast<float2*>(spec_dev);
+  hipLaunchKernelGGL(k_mwf_stats, dim3(NBIN, nsrc), dim3(MS_THREADS), 0, s, (const float2*)spec, frames, stats);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mwf_norm, dim3((nsrc * NBIN + 255) / 256), dim3(256), 0, s, (const double*)stats, nsrc, rmat);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mwf_gain, dim3(stride_grid((int64_t)NBIN * frames)), dim3(256), 0, s, spec, nsrc, frames, (const double2*)rmat);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(stats, s);
+  if (e != hipSuccess) return fail(std::string("launch k_mwf_*: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64_t n, int src_f64, int irm, double theta, void* out_dev,
+                     void* stream) {
+  using namespace glowk_oracle;
+  if (!mix_dev || !src_dev || !out_dev) return fail("null tensor");
+  if (nsrc < 1 || n < 0 || n > SP_MAX_SAMPLES) return fail("oracle_mel: need nsrc >= 1 and 0 <= n <= 2^40");
+  if (std::isnan(theta)) return fail("oracle_mel: theta must be a number");
+  if (n == 0) return 0;
+  int dev;
+  if (int rc = audio_device({mix_dev, src_dev, out_dev}, &dev, "oracle_mel")) return rc;
+  DeviceGuard dg(dev);
+  const unsigned g = stride_grid(n);
+  if (src_f64)
+    hipLaunchKernelGGL(k_oracle_mel<double>, dim3(g), dim3(256), 0, (hipStream_t)stream, mix_dev, (const double*)src_dev, nsrc, n,
+                       irm ? 1 : 0, theta, (double*)out_dev);
+  else
+    hipLaunchKernelGGL(k_oracle_mel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, mix_dev, (const float*)src_dev, nsrc, n,
+                       irm ? 1 : 0, theta, (float*)out_dev);
+  LAUNCHCHK("k_oracle_mel");
   return 0;
 }
 

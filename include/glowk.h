@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 430
+#define GLOWK_VERSION 440
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -346,6 +346,37 @@ int glowk_bss_solve(const double* corr_dev, int nwin, int npairs, int nref, int 
 int glowk_bss_project(const double* sig_dev, int64_t nsampl, int nsrc, int nchan, int filters_len, const int64_t* items_dev, int nitems,
                       int64_t max_len, const double* coef_c_dev, int nsys_c, const double* coef_j_dev, int nsys_j, double* energy_dev,
                       void* stream);
+
+/* --- oracle separation systems: IBM, IRM, MWF and the mel-domain masks (oracle_systems.py, from sigsep-mus-oracle) ---------- */
+/* Handle-free.  STFT / iSTFT in scipy.signal's conventions for nperseg 2048: periodic Hann, hop 1024, 1024 zeros on each side,
+ * zero-padded to whole frames, scaled by 1/sum(win) = 1/1024, one-sided; T = ceil(n / 1024) + 1 frames.  Spectra are
+ * [nsig][1025][T] complex (re/im interleaved, frame fastest), fp32 on the exact-fp32 MFMA.  The mask and MWF calls take the spectra
+ * of one separation: rows 0 .. nchan-1 the mixture's channels, then source j's channel c at row nchan + j * nchan + c, and
+ * overwrite the source rows with the estimates' spectra.  eps = DBL_EPSILON.  Every tensor must be device memory on one device (a
+ * host pointer is refused); each call enqueues on `stream`; scratch comes from the stream-ordered allocator.
+ * audiosourcesep_amd/oracle_systems.py drives the calls.
+ */
+/* x [nsig][n] (float) -> spec [nsig][1025][T] (scipy.signal.stft(x, nperseg=2048)).  1 <= n <= 2^40. */
+int glowk_sp_stft(const float* x_dev, int nsig, int64_t n, float* spec_dev, void* stream);
+/* spec [nsig][1025][frames] -> out [nsig][length] (scipy.signal.istft defaults, then [:length]): irfft (the imaginary parts of DC
+ * and Nyquist dropped) times sum(win), overlap-add of the 2 frames of each sample, divided by the overlap-added win^2, 1024
+ * samples trimmed at each end.  frames >= 2, 0 <= length <= (frames - 1) * 1024. */
+int glowk_sp_istft(const float* spec_dev, int nsig, int frames, int64_t length, float* out_dev, void* stream);
+/* in place on the source rows, per channel, fp64: irm == 0: Y_j = X * [|Y_j|^alpha / (eps + |X|^alpha) >= theta] (the reference's
+ * two assignments in order: >= theta -> 1, then < theta -> 0), the bits optionally to mask [nsrc][nchan][1025][frames] (uint8,
+ * nullable); irm != 0: Y_j = X * |Y_j|^alpha / (eps + sum_k |Y_k|^alpha), mask must be null.  nsrc, nchan in [1, 1024]. */
+int glowk_oracle_mask(float* spec_dev, int nsrc, int nchan, int frames, int irm, double alpha, double theta, uint8_t* mask_dev,
+                      void* stream);
+/* the multichannel Wiener filter, stereo (nchan = 2), in place on the source rows, fp64: R_j(f) = mean_t Y Y^H / (eps + P_j),
+ * normalised as the reference's np.trace of the [F, 2, 2] array does (column k of every R_j(f) times 2 / (R_j(0)[0][k] +
+ * R_j(1)[1][k])), + eps I; P_j = Re tr(R_j^-1 Y Y^H) / 2; Y_j = P_j R_j (sum_k P_k R_k)^-1 X, 2 x 2 inverses with eps added to the
+ * determinant.  nsrc in [1, 16]; the time means are fixed-order reductions (bitwise reproducible). */
+int glowk_mwf(float* spec_dev, int nsrc, int frames, void* stream);
+/* IBM_melspec (irm == 0) / IRM_melspec (irm != 0), elementwise: mix [n] (double), src [nsrc][n] and out [nsrc][n] in float
+ * (src_f64 == 0) or double; the IRM's source sum in the sources' type, in source order; + eps, the ratio, the threshold and the
+ * product in double; one rounding to the output type.  0 <= n <= 2^40. */
+int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64_t n, int src_f64, int irm, double theta, void* out_dev,
+                     void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
