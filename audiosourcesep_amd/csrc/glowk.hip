@@ -75,9 +75,9 @@ NetLaunch launch_net_raw(int c, int F, const NetArgs& a, NetCall call, hipStream
 int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipStream_t s, NetCall call, NetLaunch* out = nullptr) {
   if (h->profiling) {
     while (h->ev_pool.size() < h->ev_used + 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      h->ev_pool.push_back(e);
+      OwnedEvent e;
+      HIPCHK(event_create(e, hipEventDefault));
+      h->ev_pool.push_back(std::move(e));
     }
     HIPCHK(hipEventRecord(h->ev_pool[h->ev_used], s));
   }
@@ -259,10 +259,14 @@ SaveSizes save_sizes(const glowk_handle* h, size_t N, std::vector<size_t>* offV 
 
 int ensure_flag(glowk_handle* h) {
   if (h->d_flag) return 0;
-  HIPCHK(hipMalloc(&h->d_flag, 16));
-  HIPCHK(hipMemset(h->d_flag, 0, 16));
-  HIPCHK(hipHostMalloc(&h->h_flag, 16));
-  h->h_flag[0] = 0;
+  DeviceMem<int> d_flag;      // both words, or neither: moved in once both exist
+  PinnedMem<int> h_flag;
+  HIPCHK(dev_alloc(d_flag, 16));
+  HIPCHK(hipMemset(d_flag, 0, 16));
+  HIPCHK(pinned_alloc(h_flag, 16));
+  h_flag[0] = 0;
+  h->d_flag = std::move(d_flag);
+  h->h_flag = std::move(h_flag);
   return 0;
 }
 
@@ -270,16 +274,15 @@ int ensure_ws(glowk_handle* h, int N) {
   if (int rc = ensure_flag(h)) return rc;
   if (N <= h->wsN) return 0;
   HIPCHK(hipDeviceSynchronize());
-  if (h->bufA) { hipFree(h->bufA); hipFree(h->bufB); hipFree(h->bufP); hipFree(h->bufZ); hipFree(h->bufLd); hipFree(h->bufLdSlot); }
-  h->bufA = h->bufB = h->bufP = h->bufZ = nullptr; h->bufLd = nullptr; h->bufLdSlot = nullptr; h->wsN = 0;
+  h->bufA.reset(); h->bufB.reset(); h->bufP.reset(); h->bufZ.reset(); h->bufLd.reset(); h->bufLdSlot.reset(); h->wsN = 0;
   const WsSizes W = ws_sizes(h, (size_t)N);
-  HIPCHK(hipMalloc(&h->bufA, W.act));
-  HIPCHK(hipMalloc(&h->bufB, W.act));
+  HIPCHK(dev_alloc(h->bufA, W.act));
+  HIPCHK(dev_alloc(h->bufB, W.act));
   h->pstride = W.P / 16;          // floats per partial
-  HIPCHK(hipMalloc(&h->bufP, W.P));
-  HIPCHK(hipMalloc(&h->bufZ, W.act));
-  HIPCHK(hipMalloc(&h->bufLd, W.ld));
-  HIPCHK(hipMalloc(&h->bufLdSlot, W.slots));
+  HIPCHK(dev_alloc(h->bufP, W.P));
+  HIPCHK(dev_alloc(h->bufZ, W.act));
+  HIPCHK(dev_alloc(h->bufLd, W.ld));
+  HIPCHK(dev_alloc(h->bufLdSlot, W.slots));
   h->wsN = N;
   return 0;
 }
@@ -288,9 +291,8 @@ int ensure_ws(glowk_handle* h, int N) {
 int ensure_c(glowk_handle* h, int N) {
   if ((size_t)N <= h->cN) return 0;
   HIPCHK(hipDeviceSynchronize());
-  if (h->bufC) hipFree(h->bufC);
-  h->bufC = nullptr; h->cN = 0;
-  HIPCHK(hipMalloc(&h->bufC, (size_t)N * h->cfg.H * h->cfg.W * h->cfg.C * 4));
+  h->bufC.reset(); h->cN = 0;
+  HIPCHK(dev_alloc(h->bufC, (size_t)N * h->cfg.H * h->cfg.W * h->cfg.C * 4));
   h->cN = (size_t)N;
   return 0;
 }
@@ -338,17 +340,15 @@ NetArgs net_args(glowk_handle* h, const Level& lv, const StepDev& sd, const floa
 // per-step save buffers of the input-gradient path, forward order index sidx = level*K + (K-1-k)
 int ensure_save(glowk_handle* h, int N) {
   if (int rc = ensure_c(h, N)) return rc;
-  const SaveSizes need = save_sizes(h, (size_t)N);
   if (N <= h->saveN) return 0;
   const int Na = std::max(N, h->saveN);
   HIPCHK(hipDeviceSynchronize());
-  if (h->saveV) { hipFree(h->saveV); hipFree(h->saveP); hipFree(h->saveM); hipFree(h->bufGz); }
-  h->saveV = h->saveP = h->bufGz = nullptr; h->saveM = nullptr; h->saveN = 0;
+  h->saveV.reset(); h->saveP.reset(); h->saveM.reset(); h->bufGz.reset(); h->saveN = 0;
   SaveSizes S = save_sizes(h, (size_t)Na, &h->offV, &h->offP, &h->offM);
-  HIPCHK(hipMalloc(&h->saveV, S.v * 4));
-  HIPCHK(hipMalloc(&h->saveP, S.p * 4));
-  HIPCHK(hipMalloc(&h->saveM, S.m * 2));
-  HIPCHK(hipMalloc(&h->bufGz, S.gz));
+  HIPCHK(dev_alloc(h->saveV, S.v * 4));
+  HIPCHK(dev_alloc(h->saveP, S.p * 4));
+  HIPCHK(dev_alloc(h->saveM, S.m * 2));
+  HIPCHK(dev_alloc(h->bufGz, S.gz));
   h->saveN = Na;
   return 0;
 }
@@ -676,32 +676,8 @@ int glowk_create(const glowk_config* cfg, int device, glowk_handle** out) {
 int glowk_destroy(glowk_handle* h) {
   if (!h) return 0;
   DeviceGuard dg(h->device);
-  if (h->arena) hipFree(h->arena);
-  if (h->d_flag) hipFree(h->d_flag);
-  if (h->d_probe) hipFree(h->d_probe);
-  if (h->tr_gmax) hipFree(h->tr_gmax);
-  if (h->h_gmax) hipHostFree(h->h_gmax);
-  if (h->h_flag) hipHostFree(h->h_flag);
-  {
-    void* tr[] = {h->tr_params, h->tr_m, h->tr_v, h->trR1, h->trR2, h->trM1, h->trM2, h->trXcol, h->trGcol, h->trCpart, h->trC1, h->trC2, h->trC3,
-                  h->trGv, h->trGo, h->trAffPart, h->trAffSum, h->trSmall, h->trKeep, h->tr16_src, h->tr16_S, h->tr16_scales};
-    for (void* p : tr) if (p) hipFree(p);
-    for (int* m : h->tr_map) if (m) hipFree(m);
-    for (int* m : h->tr_map16) if (m) hipFree(m);
-  }
-  if (h->bufA) { hipFree(h->bufA); hipFree(h->bufB); hipFree(h->bufP); hipFree(h->bufZ); hipFree(h->bufLd); hipFree(h->bufLdSlot); }
-  if (h->bufC) hipFree(h->bufC);
-  if (h->bufStat) hipFree(h->bufStat);
-  if (h->saveV) { hipFree(h->saveV); hipFree(h->saveP); hipFree(h->saveM); hipFree(h->bufGz); }
-  for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
-  for (hipEvent_t e : h->tr_events) hipEventDestroy(e);
-  if (h->tr_pinned) hipHostFree(h->tr_pinned);
-  for (hipStream_t t : h->tr_streams) hipStreamDestroy(t);
-  if (h->tr_ev_sums) hipEventDestroy(h->tr_ev_sums);
-  if (h->tr_ev_up) hipEventDestroy(h->tr_ev_up);
-  if (h->tr_side) hipStreamDestroy(h->tr_side);
-  if (h->h_sums) hipHostFree(h->h_sums);
-  if (h->h_up) hipHostFree(h->h_up);
+  // work still queued on the handle's buffers, streams or pinned staging ends before the owners release them (one synchronise, not a member order)
+  (void)hipDeviceSynchronize();
   delete h;
   return 0;
 }
@@ -757,7 +733,6 @@ int glowk_get_tensor(const glowk_handle* h, int level, int step, int tensor_id, 
 int glowk_finalize_weights(glowk_handle* h) {
   if (!h) return fail("null handle");
   if (h->host_stale) { DeviceGuard dg0(h->device); if (int rc = sync_host(h)) return rc; }
-  h->split_stale = false;
   const glowk_config& cfg = h->cfg;
   for (const Level& lv : h->levels)
     if (lv.c != 4 && lv.c != 8 && lv.c != 16 && lv.c != 32)
@@ -768,8 +743,6 @@ int glowk_finalize_weights(glowk_handle* h) {
   const size_t prior_off = total;
   total += 2 * pad4(E);
   std::vector<float> stage(total, 0.0f);
-  h->ld_step.assign((size_t)cfg.L * cfg.K, 0.0);
-  h->ld_const = 0.0;
   // every step packs into its own block of the staging arena: steps are packed by a few host threads
   std::vector<PackJob> jobs;
   std::vector<size_t> offs;
@@ -788,8 +761,12 @@ int glowk_finalize_weights(glowk_handle* h) {
     if (sched_getaffinity(0, sizeof(set), &set) == 0) nthr = std::min<unsigned>(nthr ? nthr : 1, (unsigned)CPU_COUNT(&set));
     pack_all_steps(cfg, h->levels, stage.data(), jobs, std::min<unsigned>(nthr, 16u));
   }
-  for (const PackJob& jb : jobs) {
+  for (const PackJob& jb : jobs)    // (a packer error leaves the handle as it was: the images it has, split_stale, finalized)
     if (!jb.ok) return fail("level " + std::to_string(jb.l) + " step " + std::to_string(jb.k) + ": " + jb.err);
+  h->finalized = false;             // from here until the new images and step pointers are in place
+  h->ld_step.assign((size_t)cfg.L * cfg.K, 0.0);
+  h->ld_const = 0.0;
+  for (const PackJob& jb : jobs) {
     StepDev& d = h->levels[jb.l].dev[jb.k];
     h->ld_step[jb.l * cfg.K + jb.k] = jb.ldc;
     d.sc1 = jb.sc[0]; d.sc2 = jb.sc[1]; d.sc3 = jb.sc[2];
@@ -806,8 +783,8 @@ int glowk_finalize_weights(glowk_handle* h) {
 
   DeviceGuard dg(h->device);
   HIPCHK(hipDeviceSynchronize());
-  if (h->arena) { hipFree(h->arena); h->arena = nullptr; }
-  HIPCHK(hipMalloc(&h->arena, total * 4));
+  h->arena.reset();
+  HIPCHK(dev_alloc(h->arena, total * 4));
   HIPCHK(hipMemcpy(h->arena, stage.data(), total * 4, hipMemcpyHostToDevice));
   size_t idx = 0;
   for (Level& lv : h->levels) {
@@ -831,6 +808,7 @@ int glowk_finalize_weights(glowk_handle* h) {
   h->d_loc = cfg.learntop ? h->arena + prior_off : nullptr;
   h->d_log_scale = cfg.learntop ? h->arena + prior_off + pad4(E) : nullptr;
   h->finalized = true;
+  h->split_stale = false;
   return 0;
 }
 
@@ -882,7 +860,7 @@ int glowk_actnorm_data_init(glowk_handle* h, const float* x_dev, int N, int runt
   if (int rc = ensure_c(h, N)) return rc;
   if (h->host_stale) if (int rc = sync_host(h)) return rc;
   h->tr_active = false;
-  if (!h->bufStat) HIPCHK(hipMalloc(&h->bufStat, (size_t)(STAT_BLOCKS + 1) * 32 * 8));
+  if (!h->bufStat) HIPCHK(dev_alloc(h->bufStat, (size_t)(STAT_BLOCKS + 1) * 32 * 8));
   // y = SpecPreprocessing.forward(minibatch) (flow_builder.py:121), kept in bufZ
   hipLaunchKernelGGL(k_pre_only, dim3(N), dim3(256), 0, s, x_dev, (int)E, pre_args(cfg), 0, h->bufZ, (float*)nullptr, 0.0);
   LAUNCHCHK("k_pre_only");
@@ -995,7 +973,7 @@ int glowk_range_probe_begin(glowk_handle* h) {
   if (!h) return fail("null handle");
   DeviceGuard dg(h->device);
   const size_t n = (size_t)2 * h->cfg.L * h->cfg.K;
-  if (!h->d_probe) HIPCHK(hipMalloc(&h->d_probe, n * sizeof(unsigned)));
+  if (!h->d_probe) HIPCHK(dev_alloc(h->d_probe, n * sizeof(unsigned)));
   HIPCHK(hipMemset(h->d_probe, 0, n * sizeof(unsigned)));
   return 0;
 }
@@ -1008,8 +986,7 @@ int glowk_range_probe_end(glowk_handle* h, float* fwd_ratio, float* bwd_ratio, v
   std::vector<float> v((size_t)2 * LK);
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipMemcpy(v.data(), h->d_probe, v.size() * sizeof(float), hipMemcpyDeviceToHost));
-  hipFree(h->d_probe);
-  h->d_probe = nullptr;
+  h->d_probe.reset();
   float rf = 0.f, rb = 0.f;
   for (int l = 0; l < h->cfg.L; ++l)
     for (int k = 0; k < h->cfg.K; ++k) {

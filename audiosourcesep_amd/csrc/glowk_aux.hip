@@ -249,8 +249,8 @@ static int audio_consts(int dev, glowk_audio::AudioConsts* out) {
     if (e.first == dev) { *out = e.second; return 0; }
   const size_t nf = host.tab.size() + host.win.size() + host.mel_w.size() + host.bin_w.size() + host.pinv.size();
   const size_t ni = host.mel_lo.size() + host.mel_len.size() + host.mel_off.size() + host.bin_mel.size();
-  char* base = nullptr;
-  HIPCHK(hipMalloc(&base, (nf + ni) * 4));
+  DeviceMem<char> base;
+  HIPCHK(dev_alloc(base, (nf + ni) * 4));
   std::vector<char> img((nf + ni) * 4);
   size_t pos = 0;
   auto put = [&](const void* src, size_t n) { std::memcpy(img.data() + pos, src, n * 4); const char* p = base + pos; pos += n * 4; return p; };
@@ -265,11 +265,8 @@ static int audio_consts(int dev, glowk_audio::AudioConsts* out) {
   c.mel_off = (const int*)put(host.mel_off.data(), host.mel_off.size());
   c.bin_mel = (const int*)put(host.bin_mel.data(), host.bin_mel.size());
   c.step = host.step;
-  hipError_t e = hipMemcpy(base, img.data(), img.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(base);
-    return fail(std::string("audio constants upload: ") + hipGetErrorString(e));
-  }
+  HIPCHK(hipMemcpy(base, img.data(), img.size(), hipMemcpyHostToDevice));
+  base.release();              // the cache keeps the raw pointers: no static destructor frees device memory at process exit
   cache.emplace_back(dev, c);
   *out = c;
   return 0;
@@ -299,17 +296,13 @@ int glowk_mel_frontend(const float* audio_dev, int N, int n_samples, float top_d
   if (int rc = audio_consts(dev, &c)) return rc;
   const int F = 1 + n_samples / HOP, ftiles = (F + 31) / 32;
   hipStream_t s = (hipStream_t)stream;
-  float* power = nullptr;                      // |X|^2 scratch, only when the caller does not take the complex STFT (k_mel_db squares X)
-  if (!stft_dev) HIPCHK(hipMallocAsync((void**)&power, (size_t)N * NBIN * F * sizeof(float), s));
+  Scratch<float> power(HipFreeAsync{s});       // |X|^2 scratch, only when the caller does not take the complex STFT (k_mel_db squares X)
+  if (!stft_dev) HIPCHK(scratch_alloc(power, (size_t)N * NBIN * F * sizeof(float)));
   hipLaunchKernelGGL(k_stft, dim3((unsigned)(N * ftiles), (NBIN + 127) / 128), dim3(256), 0, s, audio_dev, n_samples, F, ftiles, c, power, stft_dev);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mel_db, dim3((unsigned)N), dim3(256), NMEL * F * sizeof(float), s, (const float*)power,
-                       (const float2*)stft_dev, F, top_db, c, mel_db_dev);
-    e = hipGetLastError();
-  }
-  if (power) (void)hipFreeAsync(power, s);
-  if (e != hipSuccess) return fail(std::string("launch k_stft / k_mel_db: ") + hipGetErrorString(e));
+  LAUNCHCHK("k_stft");
+  hipLaunchKernelGGL(k_mel_db, dim3((unsigned)N), dim3(256), NMEL * F * sizeof(float), s, (const float*)power,
+                     (const float2*)stft_dev, F, top_db, c, mel_db_dev);
+  LAUNCHCHK("k_mel_db");
   return 0;
 }
 
@@ -375,24 +368,20 @@ int glowk_bss_xcorr(const double* sig_dev, int nsig, int64_t nsampl, const int64
   const int per = (int)((nsub + 1023) / 1024), nblk = (int)((nsub + per - 1) / per);
   const size_t per_win = (size_t)npairs * nblk * filters_len * sizeof(double);
   const int group = (int)std::max<size_t>(1, std::min<size_t>({BSS_SCRATCH_CAP / per_win, (size_t)nwin, (size_t)65535}));
-  double* part = nullptr;
-  HIPCHK(hipMallocAsync((void**)&part, group * per_win, s));
-  hipError_t e = hipSuccess;
-  for (int w0 = 0; w0 < nwin && e == hipSuccess; w0 += group) {
+  Scratch<double> part(HipFreeAsync{s});
+  HIPCHK(scratch_alloc(part, group * per_win));
+  for (int w0 = 0; w0 < nwin; w0 += group) {
     const int g = std::min(group, nwin - w0);
     XcorrArgs a;
     a.sig = sig_dev; a.nsig = nsig; a.nsampl = nsampl; a.win = win_dev + 2 * (int64_t)w0; a.pairs = pairs_dev; a.npairs = npairs;
     a.L = filters_len; a.per = per; a.nblk = nblk; a.part = part;
     hipLaunchKernelGGL(k_bss_xcorr, dim3(nblk, npairs, g), dim3(XC_THREADS), 0, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) break;
+    LAUNCHCHK("k_bss_xcorr");
     const int64_t n = (int64_t)g * npairs * filters_len;
     hipLaunchKernelGGL(k_bss_xcorr_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)part, n, filters_len, nblk,
                        corr_dev + (int64_t)w0 * npairs * filters_len);
-    e = hipGetLastError();
+    LAUNCHCHK("k_bss_xcorr_sum");
   }
-  (void)hipFreeAsync(part, s);
-  if (e != hipSuccess) return fail(std::string("launch k_bss_xcorr: ") + hipGetErrorString(e));
   return 0;
 }
 
@@ -413,18 +402,15 @@ int glowk_bss_solve(const double* corr_dev, int nwin, int npairs, int nref, int 
   const int M = nchan_sys * filters_len;
   const size_t per_sys = (size_t)M * M * sizeof(double);
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>(BSS_CHOL_CAP / per_sys, (size_t)nsys));
-  double* A = nullptr;
-  HIPCHK(hipMallocAsync((void**)&A, chunk * per_sys, s));
-  hipError_t e = hipSuccess;
-  for (int k0 = 0; k0 < nsys && e == hipSuccess; k0 += chunk) {
+  Scratch<double> A(HipFreeAsync{s});
+  HIPCHK(scratch_alloc(A, chunk * per_sys));
+  for (int k0 = 0; k0 < nsys; k0 += chunk) {
     CholArgs a;
     a.corr = corr_dev; a.nwin = nwin; a.npairs = npairs; a.P = nref; a.L = filters_len; a.np = nchan_sys; a.sys = sys_dev; a.sys0 = k0;
     a.A = A; a.X = coef_dev; a.status = status_dev;
     hipLaunchKernelGGL(k_bss_chol, dim3(std::min(chunk, nsys - k0)), dim3(CH_THREADS), 0, s, a);
-    e = hipGetLastError();
+    LAUNCHCHK("k_bss_chol");
   }
-  (void)hipFreeAsync(A, s);
-  if (e != hipSuccess) return fail(std::string("launch k_bss_chol: ") + hipGetErrorString(e));
   return 0;
 }
 
@@ -446,23 +432,19 @@ int glowk_bss_project(const double* sig_dev, int64_t nsampl, int nsrc, int nchan
   if (nchunk > (1 << 24)) return fail("bss_project: window too long");
   const size_t per_item = (size_t)nchunk * NENERGY * sizeof(double);
   const int group = (int)std::max<size_t>(1, std::min<size_t>({BSS_SCRATCH_CAP / per_item, (size_t)nitems, (size_t)(((int64_t)1 << 30) / nchunk)}));
-  double* part = nullptr;
-  HIPCHK(hipMallocAsync((void**)&part, group * per_item, s));
-  hipError_t e = hipSuccess;
-  for (int i0 = 0; i0 < nitems && e == hipSuccess; i0 += group) {
+  Scratch<double> part(HipFreeAsync{s});
+  HIPCHK(scratch_alloc(part, group * per_item));
+  for (int i0 = 0; i0 < nitems; i0 += group) {
     const int g = std::min(group, nitems - i0);
     ProjArgs a;
     a.sig = sig_dev; a.nsampl = nsampl; a.nsrc = nsrc; a.nchan = nchan; a.L = filters_len; a.items = items_dev + 6 * (int64_t)i0; a.nitems = g;
     a.nchunk = (int)nchunk; a.coefC = coef_c_dev; a.nsysC = nsys_c; a.coefJ = coef_j_dev; a.nsysJ = nsys_j; a.part = part;
     hipLaunchKernelGGL(k_bss_project, dim3((unsigned)(g * nchunk)), dim3(PJ_THREADS), 0, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) break;
+    LAUNCHCHK("k_bss_project");
     hipLaunchKernelGGL(k_bss_energy_sum, dim3((unsigned)((g * NENERGY + 255) / 256)), dim3(256), 0, s, (const double*)part, g, (int)nchunk,
                        energy_dev + (int64_t)i0 * NENERGY);
-    e = hipGetLastError();
+    LAUNCHCHK("k_bss_energy_sum");
   }
-  (void)hipFreeAsync(part, s);
-  if (e != hipSuccess) return fail(std::string("launch k_bss_project: ") + hipGetErrorString(e));
   return 0;
 }
 
@@ -537,23 +519,17 @@ int glowk_mwf(float* spec_dev, int nsrc, int frames, void* stream) {
   if (int rc = audio_device({spec_dev}, &dev, "mwf")) return rc;
   DeviceGuard dg(dev);
   hipStream_t s = (hipStream_t)stream;
-  double* stats = nullptr;                     // [nsrc][1025][4] doubles, then the matrices [nsrc][1025][8] double2
+  Scratch<double> stats(HipFreeAsync{s});      // [nsrc][1025][4] doubles, then the matrices [nsrc][1025][8] double2
   const size_t n_stats = (size_t)nsrc * NBIN * 4, n_mat = (size_t)nsrc * NBIN * 16;
-  HIPCHK(hipMallocAsync((void**)&stats, (n_stats + n_mat) * sizeof(double), s));
+  HIPCHK(scratch_alloc(stats, (n_stats + n_mat) * sizeof(double)));
   double2* rmat = reinterpret_cast<double2*>(stats + n_stats);
   float2* spec = reinterpret_cast<float2*>(spec_dev);
   hipLaunchKernelGGL(k_mwf_stats, dim3(NBIN, nsrc), dim3(MS_THREADS), 0, s, (const float2*)spec, frames, stats);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mwf_norm, dim3((nsrc * NBIN + 255) / 256), dim3(256), 0, s, (const double*)stats, nsrc, rmat);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mwf_gain, dim3(stride_grid((int64_t)NBIN * frames)), dim3(256), 0, s, spec, nsrc, frames, (const double2*)rmat);
-    e = hipGetLastError();
-  }
-  (void)hipFreeAsync(stats, s);
-  if (e != hipSuccess) return fail(std::string("launch k_mwf_*: ") + hipGetErrorString(e));
+  LAUNCHCHK("k_mwf_stats");
+  hipLaunchKernelGGL(k_mwf_norm, dim3((nsrc * NBIN + 255) / 256), dim3(256), 0, s, (const double*)stats, nsrc, rmat);
+  LAUNCHCHK("k_mwf_norm");
+  hipLaunchKernelGGL(k_mwf_gain, dim3(stride_grid((int64_t)NBIN * frames)), dim3(256), 0, s, spec, nsrc, frames, (const double2*)rmat);
+  LAUNCHCHK("k_mwf_gain");
   return 0;
 }
 

@@ -84,11 +84,8 @@ bool level_uniform(const Level& lv) {
 int ensure_train(glowk_handle* h, int N) {
   if (N <= h->trN) return 0;
   HIPCHK(hipDeviceSynchronize());
-  float** bufs[] = {&h->trR1, &h->trR2, &h->trM1, &h->trM2, &h->trXcol, &h->trGcol, &h->trGv, &h->trGo, &h->trC1, &h->trC2, &h->trC3};
-  for (float** b : bufs) { if (*b) hipFree(*b); *b = nullptr; }
-  if (h->trAffPart) { hipFree(h->trAffPart); h->trAffPart = nullptr; }
-  if (h->trKeep) { hipFree(h->trKeep); h->trKeep = nullptr; h->trKeepN = 0; }
-  h->trN = 0;
+  for (DeviceMem<float>* b : {&h->trR1, &h->trM1, &h->trM2, &h->trXcol, &h->trGcol, &h->trGv, &h->trGo, &h->trC1, &h->trC2, &h->trC3, &h->trKeep}) b->reset();
+  h->trAffPart.reset(); h->trKeepN = 0; h->trN = 0;
   const size_t F = h->cfg.F, K = h->cfg.K;
   size_t qmax = 0, xcol = 0, gcol = 0, gv = 0;
   for (const Level& lv : h->levels) {
@@ -110,7 +107,7 @@ int ensure_train(glowk_handle* h, int N) {
       }
     size_t free_b = 0, tot_b = 0;
     if (hipMemGetInfo(&free_b, &tot_b) == hipSuccess && per_tile * N * 4 <= free_b / 4 && !glowk_detail::env().train_recompute) {
-      HIPCHK(hipMalloc(&h->trKeep, per_tile * N * 4));
+      HIPCHK(dev_alloc(h->trKeep, per_tile * N * 4));
       h->trKeepN = N;
     }
   }
@@ -125,18 +122,16 @@ int ensure_train(glowk_handle* h, int N) {
     if (uniform && hipMemGetInfo(&free_b, &tot_b) == hipSuccess && extra <= free_b / 3) h->trNB = (int)K;
   }
   const size_t nb = (size_t)h->trNB;
-  if (!h->trKeep) HIPCHK(hipMalloc(&h->trR1, 2 * F * qmax * 4));   // R1 | R2 of the step at hand (recomputed)
-  HIPCHK(hipMalloc(&h->trM1, nb * F * qmax * 4)); HIPCHK(hipMalloc(&h->trM2, nb * F * qmax * 4));
-  HIPCHK(hipMalloc(&h->trXcol, nb * xcol * 4)); HIPCHK(hipMalloc(&h->trGcol, nb * gcol * 4));
-  HIPCHK(hipMalloc(&h->trGv, nb * gv * 4)); HIPCHK(hipMalloc(&h->trGo, nb * gv * 4));
-  HIPCHK(hipMalloc(&h->trC1, nb * F * (9 * 16 + 1) * 4));
-  HIPCHK(hipMalloc(&h->trC2, nb * (F + 1) * F * 4));
-  HIPCHK(hipMalloc(&h->trC3, nb * (F + 1) * 9 * 32 * 4));
-  HIPCHK(hipMalloc(&h->trAffPart, nb * AFF_BLOCKS * AFF_NOUT_MAX * 8));
-  if (!h->trCpart) {
-    HIPCHK(hipMalloc(&h->trCpart, CPART_FLOATS * 4));
-    HIPCHK(hipMalloc(&h->trAffSum, (size_t)h->cfg.L * h->cfg.K * AFF_NOUT_MAX * 8));
-  }
+  if (!h->trKeep) HIPCHK(dev_alloc(h->trR1, 2 * F * qmax * 4));   // R1 | R2 of the step at hand (recomputed)
+  HIPCHK(dev_alloc(h->trM1, nb * F * qmax * 4)); HIPCHK(dev_alloc(h->trM2, nb * F * qmax * 4));
+  HIPCHK(dev_alloc(h->trXcol, nb * xcol * 4)); HIPCHK(dev_alloc(h->trGcol, nb * gcol * 4));
+  HIPCHK(dev_alloc(h->trGv, nb * gv * 4)); HIPCHK(dev_alloc(h->trGo, nb * gv * 4));
+  HIPCHK(dev_alloc(h->trC1, nb * F * (9 * 16 + 1) * 4));
+  HIPCHK(dev_alloc(h->trC2, nb * (F + 1) * F * 4));
+  HIPCHK(dev_alloc(h->trC3, nb * (F + 1) * 9 * 32 * 4));
+  HIPCHK(dev_alloc(h->trAffPart, nb * AFF_BLOCKS * AFF_NOUT_MAX * 8));
+  if (!h->trCpart) HIPCHK(dev_alloc(h->trCpart, CPART_FLOATS * 4));
+  if (!h->trAffSum) HIPCHK(dev_alloc(h->trAffSum, (size_t)h->cfg.L * h->cfg.K * AFF_NOUT_MAX * 8));
   h->trN = N;
   return 0;
 }
@@ -351,27 +346,28 @@ int train_begin(glowk_handle* h) {
   if (h->tr_active) return 0;
   if (!h->finalized) return fail("glowk_finalize_weights has not been called");
   if (h->tr_n == 0) train_layout(h);
-  if (!h->tr_params) {
-    HIPCHK(hipMalloc(&h->tr_params, h->tr_n * 4));
-    HIPCHK(hipMalloc(&h->tr_m, h->tr_n * 4));
-    HIPCHK(hipMalloc(&h->tr_v, h->tr_n * 4));
-    HIPCHK(hipMemset(h->tr_m, 0, h->tr_n * 4));
-    HIPCHK(hipMemset(h->tr_v, 0, h->tr_n * 4));
-    h->tr_map.assign(h->levels.size(), nullptr);
-    h->tr_map_n.assign(h->levels.size(), 0);
-    for (size_t l = 0; l < h->levels.size(); ++l) {
+  if (!h->tr_params) {     // built in locals and moved in whole: a failure part way leaves none of it in the handle
+    const size_t nl = h->levels.size();
+    DeviceMem<float> tr_params, tr_m, tr_v, tr16_src, tr16_scales;
+    DeviceMem<int> tr16_S;
+    std::vector<DeviceMem<int>> tr_map(nl), tr_map16(nl);
+    std::vector<size_t> tr_map_n(nl, 0), tr_map16_n(nl, 0);
+    HIPCHK(dev_alloc(tr_params, h->tr_n * 4));
+    HIPCHK(dev_alloc(tr_m, h->tr_n * 4));
+    HIPCHK(dev_alloc(tr_v, h->tr_n * 4));
+    HIPCHK(hipMemset(tr_m, 0, h->tr_n * 4));
+    HIPCHK(hipMemset(tr_v, 0, h->tr_n * 4));
+    for (size_t l = 0; l < nl; ++l) {
       std::vector<int> map;
       size_t lo;
       if (int rc = build_repack_map(h, (int)l, map, &lo)) return rc;
-      HIPCHK(hipMalloc(&h->tr_map[l], map.size() * 4));
-      HIPCHK(hipMemcpy(h->tr_map[l], map.data(), map.size() * 4, hipMemcpyHostToDevice));
-      h->tr_map_n[l] = map.size();
+      HIPCHK(dev_alloc(tr_map[l], map.size() * 4));
+      HIPCHK(hipMemcpy(tr_map[l], map.data(), map.size() * 4, hipMemcpyHostToDevice));
+      tr_map_n[l] = map.size();
     }
     // the same for the fp16-split images: the packer in map mode
-    h->tr_map16.assign(h->levels.size(), nullptr);
-    h->tr_map16_n.assign(h->levels.size(), 0);
     size_t src_max = 0;
-    for (size_t l = 0; l < h->levels.size(); ++l) {
+    for (size_t l = 0; l < nl; ++l) {
       const Level& lv = h->levels[l];
       const StepLayout SL = step_layout(lv.c, h->cfg.F);
       if (!(SL.slotH || SL.slotS || SL.slotHB || SL.slotSB)) continue;
@@ -383,17 +379,19 @@ int train_begin(glowk_handle* h) {
       double ldc; float sc[8]; std::string err;
       if (!pack_step(h->cfg, tmp, 0, stage.data(), &ldc, sc, &err, map16.data())) return fail("f16 repack map: " + err);
       const size_t lo = SL.RHp * 2, n = (SL.Afwd - SL.RHp) * 2;
-      HIPCHK(hipMalloc(&h->tr_map16[l], n * 4));
-      HIPCHK(hipMemcpy(h->tr_map16[l], map16.data() + lo, n * 4, hipMemcpyHostToDevice));
-      h->tr_map16_n[l] = n;
+      HIPCHK(dev_alloc(tr_map16[l], n * 4));
+      HIPCHK(hipMemcpy(tr_map16[l], map16.data() + lo, n * 4, hipMemcpyHostToDevice));
+      tr_map16_n[l] = n;
       src_max = std::max(src_max, f16_code_bases(lv.c, h->cfg.F).total);
     }
     if (src_max) {
-      HIPCHK(hipMalloc(&h->tr16_src, (size_t)h->cfg.L * h->cfg.K * src_max * 4));
-      HIPCHK(hipMalloc(&h->tr16_S, (size_t)h->cfg.L * h->cfg.K * 6 * 4));
-      HIPCHK(hipMalloc(&h->tr16_scales, (size_t)h->cfg.L * h->cfg.K * 8 * 4));
-      h->tr16_src_max = src_max;
+      HIPCHK(dev_alloc(tr16_src, (size_t)h->cfg.L * h->cfg.K * src_max * 4));
+      HIPCHK(dev_alloc(tr16_S, (size_t)h->cfg.L * h->cfg.K * 6 * 4));
+      HIPCHK(dev_alloc(tr16_scales, (size_t)h->cfg.L * h->cfg.K * 8 * 4));
     }
+    h->tr_params = std::move(tr_params); h->tr_m = std::move(tr_m); h->tr_v = std::move(tr_v);
+    h->tr_map = std::move(tr_map); h->tr_map_n = std::move(tr_map_n); h->tr_map16 = std::move(tr_map16); h->tr_map16_n = std::move(tr_map16_n);
+    h->tr16_src = std::move(tr16_src); h->tr16_S = std::move(tr16_S); h->tr16_scales = std::move(tr16_scales); h->tr16_src_max = src_max;
   }
   std::vector<float> flat;
   params_to_flat(h, flat);
@@ -516,21 +514,30 @@ static int param_grad_impl(glowk_handle* h, const float* x_dev, int N, float sca
                        grad_dev + h->tr_prior_off, grad_dev + h->tr_prior_off + pad4((size_t)E));
     LAUNCHCHK("k_prior_wgrad");
   }
-  if (!h->tr_gmax) {
-    HIPCHK(hipMalloc(&h->tr_gmax, sizeof(unsigned) * 64));
-    HIPCHK(hipHostMalloc(&h->h_gmax, sizeof(float) * 64));
+  if (!h->tr_gmax) {     // (each lazy group below is built in locals and moved in whole)
+    DeviceMem<unsigned> tr_gmax;
+    PinnedMem<float> h_gmax;
+    HIPCHK(dev_alloc(tr_gmax, sizeof(unsigned) * 64));
+    HIPCHK(pinned_alloc(h_gmax, sizeof(float) * 64));
+    h->tr_gmax = std::move(tr_gmax); h->h_gmax = std::move(h_gmax);
     h->tr_bfac.assign(4, 1.0f);
   }
   HIPCHK(hipMemsetAsync(h->tr_gmax, 0, sizeof(unsigned) * 64, s));
   const size_t steps = (size_t)cfg.L * cfg.K;
   if (!h->tr_side) {
-    HIPCHK(hipStreamCreateWithFlags(&h->tr_side, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&h->tr_ev_sums, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->tr_ev_up, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void**)&h->h_sums, steps * AFF_NOUT_MAX * 8, hipHostMallocDefault));
+    OwnedStream tr_side;
+    OwnedEvent tr_ev_sums, tr_ev_up;
+    PinnedMem<double> h_sums;
+    PinnedMem<float> h_up;
+    HIPCHK(stream_create(tr_side));
+    HIPCHK(event_create(tr_ev_sums, hipEventDisableTiming));
+    HIPCHK(event_create(tr_ev_up, hipEventDisableTiming));
+    HIPCHK(pinned_alloc(h_sums, steps * AFF_NOUT_MAX * 8));
     size_t up = 0;
     for (int lvl = 0; lvl < cfg.L; ++lvl) up += (size_t)cfg.K * train_off(h->levels[lvl].c, cfg.F).K1;
-    HIPCHK(hipHostMalloc((void**)&h->h_up, up * 4, hipHostMallocDefault));
+    HIPCHK(pinned_alloc(h_up, up * 4));
+    h->tr_side = std::move(tr_side); h->tr_ev_sums = std::move(tr_ev_sums); h->tr_ev_up = std::move(tr_ev_up);
+    h->h_sums = std::move(h_sums); h->h_up = std::move(h_up);
   }
   TrainCtx tc{grad_dev, scale, split, h->tr_ev_sums};
   // (the input gradient falls out of the sweep as well; the trainer has no use for it: it lands in the block-level scratch,
@@ -627,10 +634,11 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
   //      the updated small tensors: they come down FIRST, so the fold runs while the device refreshes the images; the split kernels'
   //      scale arguments (host-side step descriptors) come down before the last, longest kernel of the chain ----
   const int L = cfg.L;
-  if (h->tr_streams.empty()) {
-    h->tr_streams.resize(2 * L); h->tr_events.resize(1 + 4 * L);     // streams: [lvl] chain, [L + lvl] side; events: [0] fork, [1 + lvl] chain done,
-    for (hipStream_t& t : h->tr_streams) HIPCHK(hipStreamCreateWithFlags(&t, hipStreamNonBlocking));      // [1 + L + lvl] small tensors down,
-    for (hipEvent_t& e : h->tr_events) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));        // [1 + 2L + lvl] scales down, [1 + 3L + lvl] side done
+  if (h->tr_streams.empty()) {     // (streams, events and staging: built in locals, moved in whole)
+    std::vector<OwnedStream> tr_streams(2 * L);     // streams: [lvl] chain, [L + lvl] side; events: [0] fork, [1 + lvl] chain done,
+    std::vector<OwnedEvent> tr_events(1 + 4 * L);   // [1 + L + lvl] small tensors down, [1 + 2L + lvl] scales down, [1 + 3L + lvl] side done
+    for (OwnedStream& t : tr_streams) HIPCHK(stream_create(t));
+    for (OwnedEvent& e : tr_events) HIPCHK(event_create(e, hipEventDisableTiming));
     size_t tot = 0;
     h->tr_pin_off.assign(L + 1, 0);
     for (int lvl = 0; lvl < L; ++lvl) {
@@ -640,7 +648,9 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
       tot += (size_t)cfg.K * (8 + t.K1 + h->levels[lvl].c + (SL.total - SL.Afwd));
     }
     h->tr_pin_off[L] = tot;
-    HIPCHK(hipHostMalloc((void**)&h->tr_pinned, tot * 4, hipHostMallocDefault));
+    PinnedMem<float> tr_pinned;
+    HIPCHK(pinned_alloc(tr_pinned, tot * 4));
+    h->tr_streams = std::move(tr_streams); h->tr_events = std::move(tr_events); h->tr_pinned = std::move(tr_pinned);
   }
   HIPCHK(hipEventRecord(h->tr_events[0], s));
   // pinned staging of level lvl: scales | small tensors | conv3 biases | folded affine blocks

@@ -25,6 +25,12 @@ def _ptr(t):
 
 
 class GlowEngine:
+    # sizing state of the gradient path's chunks (grad_max_tiles, _reserve_or_shrink)
+    _reserved_grad = 0          # tiles the gradient buffers are reserved for
+    _grad_cap = None            # upper bound on the chunk once a reserve ran out of memory
+    _ran_grad = 0               # largest batch run through the gradient path on the buffers that exist
+    _grad_chunk = (None, 0)     # (memory picture, chunk) of the last sizing
+
     def __init__(self, cfg: GlowConfig, device=None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
@@ -164,9 +170,10 @@ class GlowEngine:
                 torch.cuda.empty_cache()
                 m = max(1, m // 2)
                 self._reserved_grad = 0          # (a failed glowk_reserve leaves the gradient buffers released)
+                self._ran_grad = 0
                 self._grad_cap = m               # ... and every later chunk is at most this large
         if with_grad:
-            self._reserved_grad = max(getattr(self, "_reserved_grad", 0), int(m))
+            self._reserved_grad = max(self._reserved_grad, int(m))
 
     @property
     def max_tiles(self):
@@ -191,13 +198,14 @@ class GlowEngine:
         # its own, anything else that was allocated since (a second prior's engine, training state, pinned staging) shrinks the
         # budget -- so the key carries the free memory in 1-GiB steps plus this engine's own reservation
         free = self._free_bytes()
-        own = self.workspace_bytes(self._reserved_grad, True) if getattr(self, "_reserved_grad", 0) else 0
+        own = self.workspace_bytes(self._reserved_grad, True) if self._reserved_grad else 0
         key = (self.get_precision(), self._max_tiles_cap, (free + own) >> 30)
-        key = key + (getattr(self, "_grad_cap", None),)
-        if getattr(self, "_grad_chunk", (None, 0))[0] == key:
+        key = key + (self._grad_cap,)
+        if self._grad_chunk[0] == key:
             return self._grad_chunk[1]
         budget = min(0.6 * (free + own), float(os.environ.get("GLOWK_GRAD_BUDGET_GB", "64")) * 2 ** 30)
-        lo, hi = 1, min(self.max_tiles, getattr(self, "_grad_cap", None) or self.max_tiles)
+        top = min(self.max_tiles, self._grad_cap or self.max_tiles)
+        lo, hi = 1, top
         if self.workspace_bytes(hi, True) > budget:
             while lo < hi:      # largest n with bytes(n) <= budget (bytes is monotone in n)
                 mid = (lo + hi + 1) // 2
@@ -210,7 +218,7 @@ class GlowEngine:
         # never below a batch this handle has already run through the gradient path: its buffers exist (the training buffers of
         # glowk_param_grad are not part of `own`, so free memory -- and with it the budget -- drops after the first training step;
         # round-3 advisor: a batch that ran on step 1 must not be refused on step 2)
-        lo = max(lo, min(getattr(self, "_ran_grad", 0), self.max_tiles))
+        lo = max(lo, min(self._ran_grad, top))
         self._grad_chunk = (key, lo)
         return lo
 
@@ -331,12 +339,12 @@ class GlowEngine:
         if n == 0:
             return lp, dx
         chunk = self.grad_max_tiles
-        if min(n, chunk) > getattr(self, "_reserved_grad", 0):
+        if min(n, chunk) > self._reserved_grad:
             self._reserve_or_shrink(min(n, chunk), True)      # (may shrink the chunk when the memory is no longer there)
             chunk = min(chunk, self.grad_max_tiles)
         for a, b in self._chunks(n, chunk):
             self._compute(self.lib.glowk_log_prob_grad(self.h, _ptr(x[a:b]), b - a, _ptr(lp[a:b]), _ptr(dx[a:b]), self._stream()))
-        self._ran_grad = max(getattr(self, "_ran_grad", 0), min(n, chunk))
+        self._ran_grad = max(self._ran_grad, min(n, chunk))
         return lp, dx
 
     # ---- training step (train_glow.py:29-44) ------------------------------------------------------------
@@ -363,7 +371,7 @@ class GlowEngine:
         if grad is None:
             grad = self._new(self.param_vector_size)
         self._compute(self.lib.glowk_param_grad(self.h, _ptr(x), n, float(scale), _ptr(lp), _ptr(grad), self._stream()))
-        if n > getattr(self, "_ran_grad", 0):
+        if n > self._ran_grad:
             self._ran_grad = n
             self._grad_chunk = (None, 0)      # (new training buffers changed the memory picture: size the chunk again)
         return lp, grad

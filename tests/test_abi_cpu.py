@@ -154,6 +154,37 @@ def test_batch_chunking_host_logic():
     assert e.grad_max_tiles == 1
 
 
+def test_grad_chunk_stays_within_what_an_out_of_memory_reserve_left():
+    """A reserve that runs out of memory halves the chunk and releases the gradient buffers: the batch that ran before no longer
+    sets a floor above the halved chunk, so the next chunk does not allocate (and fail) again."""
+    from audiosourcesep_amd.engine import GlowEngine
+    from audiosourcesep_amd.config import GlowConfig
+
+    class FakeLib:
+        def glowk_max_tiles(self, h):
+            return 1000
+
+        def glowk_get_precision(self, h):
+            return 0
+
+        def glowk_workspace_bytes(self, h, n, with_grad):
+            return n * 3000
+
+        def glowk_reserve(self, h, n, with_grad):
+            if n > 50:
+                raise _lib.GlowkError("glowk_reserve: hipMalloc: out of memory")
+            return 0
+
+    e = GlowEngine.__new__(GlowEngine)
+    e.lib, e.h, e._max_tiles_cap, e.cfg = FakeLib(), None, None, GlowConfig(H=64, W=64, C=1, L=3, K=2, F=128)
+    e._finalized = True
+    e._free_bytes = lambda: 10 ** 12
+    e._ran_grad = 64                       # a 64-tile batch has run through the gradient path
+    e.reserve(200, with_grad=True)         # 200 -> 100 -> 50 tiles
+    assert e._reserved_grad == 50
+    assert e.grad_max_tiles <= 50
+
+
 def test_status_and_policy_enums_match_header(repo_root):
     text = open(os.path.join(repo_root, "include", "glowk.h")).read()
     enum = dict((k, int(v)) for k, v in re.findall(r"(GLOWK_[A-Z0-9_]+) = (\d+)", text))

@@ -173,6 +173,39 @@ def test_workspace_bytes_is_what_reserve_allocates():
         eng.close()
 
 
+def test_closing_an_engine_gives_back_all_its_device_memory():
+    """glowk_destroy releases everything the handle made on the way: workspace and saves, training state and staging, the side and
+    refresh streams, profiler events, the range-probe buffer."""
+    cfg = GlowConfig(H=16, W=32, C=1, L=3, K=2, F=256)
+    x = dev(synthetic_mel_tiles(8, cfg, seed=12))
+
+    def use_and_close():
+        eng, _ = calibrated_engine(cfg, device=0, init_tiles=8)
+        eng.set_precision(_lib.PREC_F16X3)
+        eng.profile_begin()
+        eng.range_probe_begin()
+        eng.log_prob(x)
+        eng.log_prob_grad(x)
+        eng.range_probe_end()
+        eng.profile_end()
+        _, g = eng.param_grad(x, -1.0 / 8.0)
+        eng.apply_gradients(g)
+        eng.range_probe_begin()              # left open: the handle owns its buffer until it is destroyed
+        eng.log_prob(x)
+        eng.close()
+
+    def free_now():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    use_and_close()                          # warm-up: the code objects the first launches load stay resident
+    before = free_now()
+    use_and_close()
+    assert free_now() == before
+
+
 @pytest.mark.parametrize("big,small", [(40, 30), (12, 8), (160, 128)])
 def test_smaller_batch_after_a_larger_reserve_keeps_its_masks_apart(big, small):
     """Round-3 advisor (high): the per-step ReLU-mask offsets are laid out once for the largest batch a handle has seen; the
