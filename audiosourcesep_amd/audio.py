@@ -1,20 +1,26 @@
 """Audio in, audio out: wav I/O, the mel front end and the mel-to-audio inversion around the BASIS loop.
 
-Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) and the ``frame`` method of
-``melspec_inversion_basis.py`` (:42-93, ``run_basis_sep.py --inverse``) without librosa, soundfile or TensorFlow.  The constants
-are those of ``tile_io.MEL_FRONTEND`` (16 kHz, n_fft 2048, hop 512, 96 Slaney mels over 125..7600 Hz, -100..20 dB, 2.04 s
-extracts), compiled into the HIP kernels of ``csrc/glowk_audio.h``:
+Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) and ``melspec_inversion_basis.py`` (:21-93,
+``run_basis_sep.py --inverse``) without librosa, soundfile or TensorFlow.  The constants are those of ``tile_io.MEL_FRONTEND``
+(16 kHz, n_fft 2048, hop 512, 96 Slaney mels over 125..7600 Hz, -100..20 dB, 2.04 s extracts), compiled into the HIP kernels of
+``csrc/glowk_audio.h``:
 
 * ``mel_tiles``: STFT (a GEMM on the exact-fp32 MFMA), |X|^2, mel, dB with the per-extract ``top_db`` floor, clip;
 * ``mel_to_power``: 10^(L/10), then mel -> linear power by NNLS per frame.  librosa solves it with L-BFGS-B, whose particular
   minimiser of the underdetermined problem (96 equations, 1025 unknowns) no other solver reproduces; here it is FISTA from
   max(0, W+ b) with step 1/|W|_2^2 and a fixed iteration count (200 by default);
-* ``invert``: reuse the mixture's phase (or a single-channel Wiener filter over the sources) and the inverse STFT.
+* ``griffinlim`` / ``mel_to_audio``: librosa.griffinlim and librosa.feature.inverse.mel_to_audio (NNLS, square root, 32
+  Griffin-Lim iterations with momentum 0.99).  Each iteration is one STFT and one iSTFT with the phase update folded into its
+  spectrum staging; the whole loop is one C call.  ``init='random'`` draws its phases from the device RNG (stream
+  ``GRIFFINLIM_STREAM`` of ``seed``), not from NumPy's global RNG, so librosa's own random start is not reproduced;
+* ``invert``: reuse the mixture's phase (or a single-channel Wiener filter over the sources) or Griffin-Lim, per tile
+  (``method='frame'``) or on the tiles concatenated along time (``'whole'``).
 
-Not covered: resampling (input must be 16 kHz), Griffin-Lim, the ``whole`` inversion method, the power-scale flows
-(``scale='power'``) and stereo output.
+Not covered: resampling (input must be 16 kHz), the power-scale flows (``scale='power'``) and stereo output.
 """
 import ctypes
+import math
+import warnings
 import wave
 
 import numpy as np
@@ -28,6 +34,10 @@ HOP = MEL_FRONTEND["hop_length"]
 NBIN = MEL_FRONTEND["n_fft"] // 2 + 1
 NMEL = MEL_FRONTEND["n_mels"]
 EXTRACT = int(SR * MEL_FRONTEND["length_sec"])          # 32 640 samples (datasets/preprocessing.py:9-26)
+GRIFFINLIM_STREAM = 13      # device RNG stream of init='random' (stream ids are 0..15; 0-3 serve the flows, 14 / 15 separate_audio)
+GRIFFINLIM_MAX_FRAMES = 1 << 20                          # glowk_griffinlim's cap: 9.3 h of 16 kHz audio in one signal
+ALGORITHMS = ("reuse_phase", "griffin")
+METHODS = ("frame", "whole")
 
 
 def _p(t):
@@ -148,34 +158,163 @@ def masked_istft(powers, stft_mixture, wiener=False):
     return out
 
 
-def invert(tile_batches, stft_mixture, wiener=False, iters=200):
-    """The ``frame`` inversion of melspec_inversion_basis.py: S batches of dB tiles [N, 96, F(, 1)] of one mixture and its STFT
-    [N, 1025, F] -> [S, N * (F - 1) * 512] (the extracts' signals concatenated).  ``wiener`` needs S >= 2.  One NNLS launch
-    covers the frames of all S batches."""
+def _check_griffin(n_iter, momentum):
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= n_iter <= 100000:
+        raise ValueError("n_iter: expected an integer in [0, 100000], got %r" % (n_iter,))
+    if not (isinstance(momentum, (int, float, np.integer, np.floating)) and math.isfinite(momentum) and momentum >= 0):
+        raise ValueError("momentum: expected a finite number >= 0, got %r" % (momentum,))
+    if momentum > 1:
+        warnings.warn("Griffin-Lim with momentum=%g > 1 can be unstable. Proceed with caution!" % momentum)
+
+
+def _check_init(init, shape):
+    """init: 'random', None or a complex tensor of ``shape``; returns the tensor form (or the string / None)."""
+    if init is None or (isinstance(init, str) and init == "random"):
+        return init
+    if isinstance(init, str):
+        raise ValueError("init: expected 'random', None or a complex tensor, got %r" % init)
+    a = init if torch.is_tensor(init) else torch.as_tensor(np.asarray(init))
+    if not a.is_complex() or tuple(a.shape) != tuple(shape):
+        raise ValueError("init: expected a complex tensor of shape %s, got %s %s" % (tuple(shape), a.dtype, tuple(a.shape)))
+    return a
+
+
+def griffinlim(S, n_iter=32, momentum=0.99, init="random", seed=0):
+    """librosa.griffinlim (center=True, the front end's window and hop): magnitudes [N, 1025, F] -> audio [N, (F - 1) * 512].
+
+    ``init``: 'random' (phases exp(2 pi i U), U ~ U(0, 1) from the device RNG stream ``GRIFFINLIM_STREAM`` of ``seed``, drawn
+    over [N, 1025, F]), None (all ones) or a complex [N, 1025, F] tensor used as iteration 0's phases as given.  ``n_iter`` = 0
+    is the plain iSTFT of S init.  Needs 4 <= F <= 2^20.  One C call: 2 n_iter + 1 kernels on the current stream."""
+    m = _tensor(S, "S")
+    if m.dim() != 3 or m.shape[1] != NBIN or not 4 <= m.shape[2] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("S: expected [N, 1025, F] magnitudes with 4 <= F <= %d, got %s" % (GRIFFINLIM_MAX_FRAMES, tuple(m.shape)))
+    _check_griffin(n_iter, momentum)
+    a = _check_init(init, m.shape)
+    dev = _device(m, *([a] if torch.is_tensor(a) else []))
+    m = m.to(device=dev, dtype=torch.float32).contiguous()
+    N, _, F = m.shape
+    if isinstance(a, str):
+        u = basis.device_randn(tuple(m.shape), dev, seed=seed, which=GRIFFINLIM_STREAM, uniform=True)
+        a = torch.exp((2j * math.pi) * u.double()).to(torch.complex64)          # the phases rounded once
+    if a is not None:
+        a = torch.view_as_real(a.to(device=dev, dtype=torch.complex64)).contiguous()
+    out = torch.empty((N, (F - 1) * HOP), device=dev, dtype=torch.float32)
+    _lib.check(_lib.load().glowk_griffinlim(_p(m), _p(a), N, F, int(n_iter), float(momentum), _p(out), _s(m)))
+    return out
+
+
+def _whole(x):
+    """[N, ..., F] -> [1, ..., N F]: the tiles side by side along the frame axis (np.concatenate(list(x), axis=-1))."""
+    return torch.cat(list(x), dim=-1)[None]
+
+
+def _check_method(method):
+    if method not in METHODS:
+        raise ValueError("method: expected one of %s, got %r" % (METHODS, method))
+
+
+def _check_frames(N, F, method):
+    """Frames of each signal the iSTFT / Griffin-Lim inverts: F per tile ('frame') or N F ('whole'); 4 .. 2^20 of them."""
+    frames = N * F if method == "whole" else F
+    if not 4 <= frames <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("tiles: the %r inversion of %d tiles of %d frames gives signals of %d frames, expected 4 <= frames <= %d"
+                         % (method, N, F, frames, GRIFFINLIM_MAX_FRAMES))
+
+
+def mel_to_audio(tiles, n_iter=32, momentum=0.99, init="random", seed=0, iters=200, method="frame"):
+    """librosa.feature.inverse.mel_to_audio of the dB tiles [N, 96, F(, 1)]: NNLS (``iters`` FISTA iterations), square root,
+    ``griffinlim``.  ``method='frame'`` inverts each tile on its own -> [N * (F - 1) * 512]; ``'whole'`` inverts the tiles laid side
+    by side along time as one signal -> [(N F - 1) * 512].  ``init`` as for ``griffinlim``, of the spectra it inverts: a tensor is
+    [N, 1025, F] (concatenated like the tiles for 'whole'); 'random' draws over [N, 1025, F] ('frame') or [1, 1025, N F] ('whole')."""
+    t = _tensor(tiles, "tiles")
+    _check_tiles(t)
+    _check_method(method)
+    _check_frames(t.shape[0], t.shape[2], method)
+    _check_griffin(n_iter, momentum)
+    a = _check_init(init, (t.shape[0], NBIN, t.shape[2]))
+    S = torch.sqrt(mel_to_power(t, iters))
+    if torch.is_tensor(a) and method == "whole":
+        a = _whole(a)
+    if method == "whole":
+        S = _whole(S)
+    return griffinlim(S, n_iter=n_iter, momentum=momentum, init=a, seed=seed).reshape(-1)
+
+
+def invert(tile_batches, stft_mixture=None, wiener=False, iters=200, algorithm="reuse_phase", method="frame", n_iter=32, momentum=0.99,
+           seed=0):
+    """melspec_inversion_basis.py: S batches of dB tiles [N, 96, F(, 1)] of one mixture -> S signals.  ``method='frame'`` inverts
+    each tile and concatenates the signals -> [S, N * (F - 1) * 512]; ``'whole'`` concatenates the tiles (and the mixture STFTs)
+    along time and inverts one signal per source -> [S, (N F - 1) * 512].  One NNLS launch covers the frames of all S batches.
+
+    ``algorithm='reuse_phase'`` needs the mixture's STFT [N, 1025, F] and reuses its phase, or with ``wiener`` (S >= 2) applies
+    the single-channel Wiener filter.  ``'griffin'`` needs no mixture: ``mel_to_audio``'s Griffin-Lim (``n_iter``, ``momentum``,
+    random phases from ``seed``).  The reuse-phase and Wiener 'whole' inversions are ``griffinlim(n_iter=0)`` of the
+    concatenated spectra with init = exp(i angle(X))."""
+    if algorithm not in ALGORITHMS:
+        raise ValueError("algorithm: expected one of %s, got %r" % (ALGORITHMS, algorithm))
+    _check_method(method)
+    griffin = algorithm == "griffin"
+    if griffin and wiener:
+        raise ValueError("wiener: the Wiener filter applies to algorithm='reuse_phase' only")
+    if not griffin and stft_mixture is None:
+        raise ValueError("stft_mixture: algorithm='reuse_phase' needs the mixture's STFT [N, 1025, F]")
     tiles = [_tensor(t, "tiles") for t in tile_batches]
-    X = _tensor(stft_mixture, "stft_mixture")
+    if not tiles:
+        raise ValueError("tile_batches: expected at least one batch of tiles")
     for t in tiles:
         _check_tiles(t)
-        if tuple(t.shape[:3]) != (X.shape[0], NMEL, X.shape[-1]):
-            raise ValueError("tiles %s do not match stft_mixture %s: expected [N, 96, F] = %s"
-                             % (tuple(t.shape), tuple(X.shape), (X.shape[0], NMEL, X.shape[-1])))
-    dev = _device(X, *tiles)
+    if griffin:
+        for t in tiles[1:]:
+            if tuple(t.shape[:3]) != tuple(tiles[0].shape[:3]):
+                raise ValueError("tiles %s do not match the first batch %s" % (tuple(t.shape), tuple(tiles[0].shape)))
+        _check_frames(tiles[0].shape[0], tiles[0].shape[2], method)
+        _check_griffin(n_iter, momentum)
+        dev = _device(*tiles)
+    else:
+        X = _tensor(stft_mixture, "stft_mixture")
+        for t in tiles:
+            if tuple(t.shape[:3]) != (X.shape[0], NMEL, X.shape[-1]):
+                raise ValueError("tiles %s do not match stft_mixture %s: expected [N, 96, F] = %s"
+                                 % (tuple(t.shape), tuple(X.shape), (X.shape[0], NMEL, X.shape[-1])))
+        if wiener and len(tiles) < 2:
+            raise ValueError("the Wiener filter needs at least 2 sources, got %d" % len(tiles))
+        if method == "whole":
+            _check_frames(X.shape[0], X.shape[-1], method)
+        dev = _device(X, *tiles)
     batch = torch.cat([t.to(device=dev, dtype=torch.float32).reshape(t.shape[0], NMEL, -1) for t in tiles])
     powers = mel_to_power(batch, iters).reshape(len(tiles), -1, NBIN, batch.shape[2])
-    y = masked_istft(powers, X, wiener)
-    return y.reshape(y.shape[0], -1)
+    if griffin:
+        S = torch.sqrt(powers)
+        S = torch.cat([_whole(s) for s in S]) if method == "whole" else S.reshape(-1, NBIN, S.shape[-1])
+        y = griffinlim(S, n_iter=n_iter, momentum=momentum, init="random", seed=seed)
+    elif method == "frame":
+        y = masked_istft(powers, X, wiener)
+    else:
+        Xw = _whole(X.to(device=dev, dtype=torch.complex64))[0]                   # [1025, N F]
+        P = torch.cat([_whole(p) for p in powers])                                  # [S, 1025, N F]
+        S = P / (P.sum(0) + 1e-10) * Xw.abs() if wiener else torch.sqrt(P)
+        phase = torch.polar(torch.ones_like(Xw.real), Xw.angle())                  # exp(i angle(X)), angle(0) = 0
+        y = griffinlim(S, n_iter=0, init=phase.expand(S.shape))
+    return y.reshape(len(tiles), -1)
 
 
 def separate_audio(mix, flow1, flow2, sigmas, restore_1=None, restore_2=None, T=100, delta=2e-5, seed=0, skip=0, n=None, wiener=False,
-                   top_db=80.0, iters=200):
+                   top_db=80.0, iters=200, algorithm="reuse_phase", method="frame", n_iter=32, momentum=0.99):
     """A mixture (wav path or 16 kHz samples) -> two separated signals: front end, ``basis.basis_outer_loop`` from the reference's
     uniform start over [-100, 20] dB (run_basis_sep.py:360-361; device RNG streams 14 / 15 of ``seed``, apart from the Langevin
-    noise's 0 / 1), inversion.  Returns ``(y1, y2, mixed, x1, x2)``: the signals [N * 32256] and the tiles [N, 96, 64, 1]."""
+    noise's 0 / 1), inversion (``invert``'s ``algorithm``, ``method``, ``n_iter`` and ``momentum``; Griffin-Lim's phases from
+    ``seed``).  Returns ``(y1, y2, mixed, x1, x2)``: the signals ([N * 32256] per tile, [(64 N - 1) * 512] for 'whole') and the
+    tiles [N, 96, 64, 1].  ``run_basis_sep.py --inverse`` is ``algorithm='griffin', method='whole'``."""
+    if algorithm not in ALGORITHMS:
+        raise ValueError("algorithm: expected one of %s, got %r" % (ALGORITHMS, algorithm))
+    _check_method(method)
+    if algorithm == "griffin":
+        _check_griffin(n_iter, momentum)
     y = read_wav(mix) if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__") else mix
     mixed, X = mel_tiles(extracts(y, skip, n), top_db=top_db, return_stft=True)
     x1 = -100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14, uniform=True)
     x2 = -100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=15, uniform=True)
     x1, x2, _ = basis.basis_outer_loop(mixed, x1, x2, flow1, flow2, sigmas, restore_1=restore_1, restore_2=restore_2, T=T, delta=delta,
                                        seed=seed)
-    out = invert([x1, x2], X, wiener=wiener, iters=iters)
+    out = invert([x1, x2], X, wiener=wiener, iters=iters, algorithm=algorithm, method=method, n_iter=n_iter, momentum=momentum, seed=seed)
     return out[0], out[1], mixed, x1, x2

@@ -20,6 +20,7 @@ namespace glowk_audio {
 
 constexpr int NFFT = 2048, HOP = 512, PAD = NFFT / 2, NBIN = NFFT / 2 + 1, NMEL = 96;
 constexpr int MAX_FRAMES = 128;                      // k_mel_db holds an extract's [96][F] dB tile in LDS (48 KB at F = 128)
+constexpr int GL_MAX_FRAMES = 1 << 20;               // Griffin-Lim signals: (F - 1) 512 samples and F 512 + 1024 stay below 2^31
 constexpr int EXTRACT = 32640;                       // int(16000 * 2.04) samples (datasets/preprocessing.py:9-26)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -216,24 +217,79 @@ __global__ __launch_bounds__(256) void k_nnls(const float* __restrict__ mel_db, 
   }
 }
 
-// ---- masked iSTFT.  Output hop block h (padded samples [512 h, 512 h + 512)) gathers frames h - q, q = 0..3, at offset 512 q:
+// ---- spectrum sources of k_istft: the complex bin Y of signal sn at o = b F + frame of its [1025][F] plane, before the irfft weights.
+// MaskSource: power [S][N][1025][F] with the mixture STFT [N][1025][F] (signal sn = s N + n) -- reuse the mixture's phase, or the
+// single-channel Wiener filter (melspec_inversion_basis.py:42-93).
+struct MaskSource {
+  const float* power;
+  int S;
+  const float2* xm;
+  int N, wiener;
+  __device__ __forceinline__ float2 bin(int sn, size_t plane, size_t o) const {
+    const int n = sn % N;
+    const float2 X = xm[(size_t)n * plane + o];
+    const float x = power[(size_t)sn * plane + o];
+    float yr = 0.0f, yi = 0.0f;
+    if (wiener) {                                    // single_channel_wiener_filter: x_i / (sum_j x_j + 1e-10) X
+      float tot = 0.0f;
+      for (int s = 0; s < S; ++s) tot += power[(size_t)(s * N + n) * plane + o];
+      const float g = x / (tot + 1e-10f);
+      yr = g * X.x; yi = g * X.y;
+    } else {                                         // sqrt(x) e^{i angle(X)}, angle(0) = 0
+      const float mag = sqrtf(X.x * X.x + X.y * X.y), sx = sqrtf(x);
+      if (mag > 0.0f) { yr = sx * (X.x / mag); yi = sx * (X.y / mag); }
+      else yr = sx;
+    }
+    return make_float2(yr, yi);
+  }
+};
+
+// GriffinSource: magnitudes mag [N][1025][F] and librosa.griffinlim's phase.  Iteration 0 (R == null): mag init (init == null: ones).
+// After it: a = R - beta P from the latest rebuilt spectrum R and the one before it P (P == null: the first update, tprev = 0),
+// Y = mag a / (|a| + 1e-16) -- a zero stays zero.  R and P are complex [N][1025][F].
+struct GriffinSource {
+  const float* mag;
+  const float2* init;
+  const float2* R;
+  const float2* P;
+  float beta;                                        // momentum / (1 + momentum)
+  __device__ __forceinline__ float2 bin(int sn, size_t plane, size_t o) const {
+    const size_t e = (size_t)sn * plane + o;
+    const float s = mag[e];
+    if (!R) {
+      if (!init) return make_float2(s, 0.0f);
+      const float2 a = init[e];
+      return make_float2(s * a.x, s * a.y);
+    }
+    float2 a = R[e];
+    if (P) {
+      const float2 p = P[e];
+      a.x = fmaf(-beta, p.x, a.x);
+      a.y = fmaf(-beta, p.y, a.y);
+    }
+    const float r = 1.0f / (sqrtf(a.x * a.x + a.y * a.y) + 1e-16f);
+    return make_float2(s * (a.x * r), s * (a.y * r));
+  }
+};
+
+// ---- iSTFT of the spectra a Source gives.  Output hop block h (padded samples [512 h, 512 h + 512)) gathers frames h - q, q = 0..3,
+// at offset 512 q:
 //   out[h][u] = sum_q hann[512 q + u] C_q[h][u],   C_q[h][u] = frame_{h-q}[512 q + u] = sum_b Y_{h-q}[b] basis[b][512 q + u]
 // so each q is a GEMM with its own accumulator (spectra rows shifted by q), summed in the order q = 0, 1, 2, 3 in the epilogue.
 // One wave = 32 hop blocks x 32 samples; 4 waves = 128 samples; the spectra of the 35 frames a tile touches are staged in LDS,
-// masked and scaled as they are loaded, 41 bins at a time (1025 = 25 x 41).
+// built by the Source and scaled as they are loaded, 41 bins at a time (1025 = 25 x 41).  One block row per signal and hop tile:
+// grid (signals x htiles, 4).  Indices into the spectra and the audio are size_t; F < 2^22 keeps the int hop-block index exact.
 constexpr int IS_BC = 41, IS_ROWS = 35, IS_PITCH = 2 * IS_BC + 1;
 
-__global__ __launch_bounds__(256) void k_istft(const float* __restrict__ power, int S, const float* __restrict__ stft_mix, int N, int F,
-                                               int htiles, int wiener, AudioConsts c, float* __restrict__ audio) {
+template <class Source>
+__global__ __launch_bounds__(256) void k_istft(Source src, int F, int htiles, AudioConsts c, float* __restrict__ audio) {
   __shared__ float tab[NFFT];
   __shared__ float sp[IS_ROWS * IS_PITCH];           // [frame - fbase][2 (b - b0) + re/im]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, i = lane & 31;
-  const int sn = blockIdx.x / htiles, ht = blockIdx.x % htiles, n = sn % N;
+  const int sn = blockIdx.x / htiles, ht = blockIdx.x % htiles;
   const int u0 = blockIdx.y * 128 + wave * 32;
   const int fbase = ht * 32 - 1;                     // hop block h = 2 + 32 ht + i needs frames h - 3 .. h
   const size_t plane = (size_t)NBIN * F;
-  const float* px = power + (size_t)sn * plane;
-  const float2* xm = reinterpret_cast<const float2*>(stft_mix) + (size_t)n * plane;
   for (int k = tid; k < NFFT; k += 256) tab[k] = c.tab[k];
   f32x16 acc[4] = {{}, {}, {}, {}};
   for (int b0 = 0; b0 < NBIN; b0 += IS_BC) {
@@ -242,19 +298,8 @@ __global__ __launch_bounds__(256) void k_istft(const float* __restrict__ power, 
       const int bl = k / IS_ROWS, ri = k % IS_ROWS, b = b0 + bl, fr = fbase + ri;
       float yr = 0.0f, yi = 0.0f;
       if (fr >= 0 && fr < F) {
-        const size_t o = (size_t)b * F + fr;
-        const float2 X = xm[o];
-        const float x = px[o];
-        if (wiener) {                                // single_channel_wiener_filter: x_i / (sum_j x_j + 1e-10) X
-          float tot = 0.0f;
-          for (int s = 0; s < S; ++s) tot += power[(size_t)(s * N + n) * plane + o];
-          const float g = x / (tot + 1e-10f);
-          yr = g * X.x; yi = g * X.y;
-        } else {                                     // sqrt(x) e^{i angle(X)}, angle(0) = 0
-          const float mag = sqrtf(X.x * X.x + X.y * X.y), sx = sqrtf(x);
-          if (mag > 0.0f) { yr = sx * (X.x / mag); yi = sx * (X.y / mag); }
-          else yr = sx;
-        }
+        const float2 y = src.bin(sn, plane, (size_t)b * F + fr);
+        yr = y.x; yi = y.y;
         const bool edge = b == 0 || b == NBIN - 1;   // irfft: DC and Nyquist once and real, the other bins twice
         yr *= edge ? (1.0f / NFFT) : (2.0f / NFFT);
         yi = edge ? 0.0f : yi * (2.0f / NFFT);

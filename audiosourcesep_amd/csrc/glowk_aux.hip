@@ -339,9 +339,52 @@ int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev,
   AudioConsts c;
   if (int rc = audio_consts(dev, &c)) return rc;
   const int htiles = (frames - 1 + 31) / 32;
-  hipLaunchKernelGGL(k_istft, dim3((unsigned)(S * N * htiles), HOP / 128), dim3(256), 0, (hipStream_t)stream, power_dev, S, stft_mix_dev, N, frames,
-                     htiles, wiener ? 1 : 0, c, audio_dev);
+  const MaskSource src{power_dev, S, reinterpret_cast<const float2*>(stft_mix_dev), N, wiener ? 1 : 0};
+  hipLaunchKernelGGL(k_istft<MaskSource>, dim3((unsigned)(S * N * htiles), HOP / 128), dim3(256), 0, (hipStream_t)stream, src, frames, htiles, c,
+                     audio_dev);
   LAUNCHCHK("k_istft");
+  return 0;
+}
+
+// Griffin-Lim: iteration 0 is one iSTFT of mag init; each of the n_iter iterations is k_stft of the latest signal into one of two
+// complex spectra, then k_istft with the phase update folded into its staging (GriffinSource).  The STFT of iteration k overwrites
+// the spectrum iteration k - 1's iSTFT consumed as P.  The signal between the two launches lives in audio_dev.
+int glowk_griffinlim(const float* mag_dev, const float* angles0_dev, int N, int frames, int n_iter, float momentum, float* audio_dev,
+                     void* stream) {
+  using namespace glowk_audio;
+  if (!mag_dev || !audio_dev) return fail("null tensor");
+  if (N < 0 || N > (1 << 20)) return fail("griffinlim: N must be in [0, 2^20]");
+  if (frames < 4 || frames > GL_MAX_FRAMES)
+    return fail("griffinlim: frames must be in [4, 2^20]: the STFT's reflect padding needs (frames - 1) * 512 > 1024 samples");
+  if (n_iter < 0 || n_iter > 100000) return fail("griffinlim: n_iter must be in [0, 100000]");
+  if (!(momentum >= 0.0f && momentum < INFINITY)) return fail("griffinlim: momentum must be finite and >= 0");
+  const int ftiles = (frames + 31) / 32, htiles = (frames - 1 + 31) / 32;
+  if ((int64_t)N * ftiles > INT32_MAX) return fail("griffinlim: N x frames too large for one launch");
+  if (N == 0) return 0;
+  int dev;
+  if (int rc = audio_device({mag_dev, angles0_dev, audio_dev}, &dev, "griffinlim")) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 is_grid((unsigned)(N * htiles), HOP / 128), st_grid((unsigned)(N * ftiles), (NBIN + 127) / 128);
+  const int n_samples = (frames - 1) * HOP;
+  const size_t spec = (size_t)N * NBIN * frames;   // complex elements of one spectrum
+  Scratch<float2> R(HipFreeAsync{s});              // two rebuilt spectra, ping-pong
+  if (n_iter > 0) HIPCHK(scratch_alloc(R, (n_iter > 1 ? 2 : 1) * spec * sizeof(float2)));
+  const float beta = (float)((double)momentum / (1.0 + (double)momentum));
+  GriffinSource src{mag_dev, reinterpret_cast<const float2*>(angles0_dev), nullptr, nullptr, beta};
+  hipLaunchKernelGGL(k_istft<GriffinSource>, is_grid, dim3(256), 0, s, src, frames, htiles, c, audio_dev);
+  LAUNCHCHK("k_istft");
+  for (int it = 1; it <= n_iter; ++it) {
+    float2* cur = R + (size_t)((it - 1) & 1) * spec;
+    hipLaunchKernelGGL(k_stft, st_grid, dim3(256), 0, s, (const float*)audio_dev, n_samples, frames, ftiles, c, (float*)nullptr, (float*)cur);
+    LAUNCHCHK("k_stft");
+    src.R = cur;
+    src.P = it > 1 ? R + (size_t)(it & 1) * spec : nullptr;
+    hipLaunchKernelGGL(k_istft<GriffinSource>, is_grid, dim3(256), 0, s, src, frames, htiles, c, audio_dev);
+    LAUNCHCHK("k_istft");
+  }
   return 0;
 }
 

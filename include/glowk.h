@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 440
+#define GLOWK_VERSION 450
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -293,7 +293,7 @@ int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int whi
 int glowk_add_noise(const float* x_dev, float* out_dev, size_t n, float sigma, uint64_t seed, uint64_t step, int which, uint64_t offset,
                     void* stream);
 
-/* --- audio: mel front end and mel-to-audio inversion (datasets/data_loader.py:146-164, melspec_inversion_basis.py:42-93) ----- */
+/* --- audio: mel front end and mel-to-audio inversion (datasets/data_loader.py:146-164, melspec_inversion_basis.py:21-93) ----- */
 /* Handle-free; the constants of the reference's front end are compiled in: 16 kHz, n_fft 2048, hop 512, periodic Hann, 96 Slaney
  * mels over 125..7600 Hz (librosa.filters.mel defaults), dB clipped to [-100, 20].  Spectra are [.., 1025, F] with the frame
  * fastest; a complex spectrum is re/im interleaved (torch.complex64).  The first call on a device uploads its constants there.
@@ -315,6 +315,15 @@ int glowk_mel_to_power(const float* mel_db_dev, int N, int frames, int iters, fl
  * S in [1, 16], F in [2, 128]. */
 int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev, int N, int frames, int wiener, float* audio_dev,
                        void* stream);
+/* Griffin-Lim (librosa.griffinlim: n_iter iterations, momentum, then one last iSTFT): magnitudes mag [N, 1025, F] -> audio
+ * [N, (F-1)*512].  angles0_dev (nullable: all ones) [N, 1025, F] complex holds iteration 0's phases as given; each iteration is
+ * an STFT of the latest signal, then an iSTFT of mag a / (|a| + 1e-16), a = rebuilt - momentum / (1 + momentum) * previous
+ * rebuilt (previous = 0 at the first update).  2n_iter + 1 launches on `stream`, no host synchronisation; for n_iter >= 1 the
+ * call takes two complex [N, 1025, F] spectra from the stream-ordered allocator (one when n_iter == 1), and audio_dev holds the
+ * signal between launches.  N in [0, 2^20], F in [4, 2^20], n_iter in [0, 100000], momentum finite and >= 0; bitwise
+ * reproducible. */
+int glowk_griffinlim(const float* mag_dev, const float* angles0_dev, int N, int frames, int n_iter, float momentum, float* audio_dev,
+                     void* stream);
 
 /* --- BSS Eval v4: SDR / ISR / SIR / SAR (bsseval_v4.py, sigsep's v4 with the v3 wrappers) ----------------------------------- */
 /* Handle-free, fp64 throughout.  sig_dev [nsig][nsampl] holds the reference channels p = j * nchan + c (P = nsrc * nchan of
