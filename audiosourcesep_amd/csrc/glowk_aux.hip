@@ -500,9 +500,9 @@ unsigned stride_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min
 
 int glowk_sp_stft(const float* x_dev, int nsig, int64_t n, float* spec_dev, void* stream) {
   using namespace glowk_oracle;
-  if (!x_dev || !spec_dev) return fail("null tensor");
   if (nsig < 0 || n < 1 || n > SP_MAX_SAMPLES) return fail("sp_stft: need nsig >= 0 and 1 <= n <= 2^40");
-  if (nsig == 0) return 0;
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!x_dev || !spec_dev) return fail("null tensor");
   const int64_t T = sp_frames(n), ftiles = (T + 31) / 32;
   if (nsig * ftiles > SP_MAX_GRID) return fail("sp_stft: too many signals x frames for one launch");
   int dev;
@@ -518,10 +518,10 @@ int glowk_sp_stft(const float* x_dev, int nsig, int64_t n, float* spec_dev, void
 
 int glowk_sp_istft(const float* spec_dev, int nsig, int frames, int64_t length, float* out_dev, void* stream) {
   using namespace glowk_oracle;
-  if (!spec_dev || !out_dev) return fail("null tensor");
   if (nsig < 0 || frames < 2 || frames > sp_frames(SP_MAX_SAMPLES)) return fail("sp_istft: need nsig >= 0 and frames >= 2");
   if (length < 0 || length > (int64_t)(frames - 1) * HOP) return fail("sp_istft: length must be in [0, (frames - 1) * 1024]");
-  if (nsig == 0 || length == 0) return 0;
+  if (nsig == 0 || length == 0) return 0;      // an empty output has no storage: its pointer may be null
+  if (!spec_dev || !out_dev) return fail("null tensor");
   const int64_t htiles = ((int64_t)frames - 1 + 31) / 32;
   if (nsig * htiles > SP_MAX_GRID) return fail("sp_istft: too many signals x frames for one launch");
   int dev;
@@ -579,10 +579,10 @@ int glowk_mwf(float* spec_dev, int nsrc, int frames, void* stream) {
 int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64_t n, int src_f64, int irm, double theta, void* out_dev,
                      void* stream) {
   using namespace glowk_oracle;
-  if (!mix_dev || !src_dev || !out_dev) return fail("null tensor");
   if (nsrc < 1 || n < 0 || n > SP_MAX_SAMPLES) return fail("oracle_mel: need nsrc >= 1 and 0 <= n <= 2^40");
   if (std::isnan(theta)) return fail("oracle_mel: theta must be a number");
-  if (n == 0) return 0;
+  if (n == 0) return 0;                        // empty tensors have no storage: their pointers may be null
+  if (!mix_dev || !src_dev || !out_dev) return fail("null tensor");
   int dev;
   if (int rc = audio_device({mix_dev, src_dev, out_dev}, &dev, "oracle_mel")) return rc;
   DeviceGuard dg(dev);

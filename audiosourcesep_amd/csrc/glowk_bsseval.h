@@ -300,8 +300,9 @@ __global__ __launch_bounds__(PJ_THREADS) void k_bss_project(ProjArgs a) {
   const int64_t* it = a.items + (int64_t)item * 6;
   const int64_t s = max(it[0], (int64_t)0), e = min(it[1], a.nsampl);
   const int64_t len = e > s ? e - s : 0;
-  const int jtrue = (int)it[2], jest = (int)it[3], sc = (int)it[4], sj = (int)it[5];
-  const bool ok = jtrue >= 0 && jtrue < a.nsrc && jest >= 0 && jest < a.nsrc && sc >= 0 && sc < a.nsysC && sj >= 0 && sj < a.nsysJ;
+  // range-checked as the 64-bit words they are: narrowed first, 2^32 would pass for 0
+  const bool ok = it[2] >= 0 && it[2] < a.nsrc && it[3] >= 0 && it[3] < a.nsrc && it[4] >= 0 && it[4] < a.nsysC && it[5] >= 0 && it[5] < a.nsysJ;
+  const int jtrue = ok ? (int)it[2] : 0, jest = ok ? (int)it[3] : 0, sc = ok ? (int)it[4] : 0, sj = ok ? (int)it[5] : 0;
   const int64_t n0 = (int64_t)chunk * PJ_OUT, nout = len + L - 1;
   double en[NENERGY] = {};
   if (ok && n0 < nout) {

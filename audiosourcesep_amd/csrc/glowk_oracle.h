@@ -301,6 +301,9 @@ __global__ __launch_bounds__(256) void k_sp_istft(const float2* __restrict__ spe
       sp[ri * SI_PITCH + 2 * bl + 1] = yi;
     }
     __syncthreads();
+    // each chunk's 82 terms in a chain of their own, then added: one chain over all 2050 terms rounds an impulse's 1025 equal
+    // terms the same way at every step, and the bias grows to 1.5e-5 of the sample (n = 1); blocked, it stays below 1e-6
+    f32x16 part[2] = {{}, {}};
     for (int bl = 0; bl < SI_BC; ++bl) {
       const int b = b0 + bl;
 #pragma unroll
@@ -308,9 +311,11 @@ __global__ __launch_bounds__(256) void k_sp_istft(const float2* __restrict__ spe
         const float av = sp[(i + 1 - q) * SI_PITCH + 2 * bl + half];
         const int t = HOP * q + u0 + i;
         const float bvv = tab[(b * t + 512 * half) & (NFFT - 1)];
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bvv, acc[q], 0, 0, 0);
+        part[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bvv, part[q], 0, 0, 0);
       }
     }
+    acc[0] += part[0];
+    acc[1] += part[1];
   }
   const int u = u0 + i;                              // C/D: column = lane & 31 (sample), row = (r & 3) + 8 (r >> 2) + 4 half (hop block)
   const float w0 = c.win[u], w1 = c.win[HOP + u];

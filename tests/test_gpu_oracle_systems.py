@@ -44,7 +44,7 @@ def sig_rel(got, want):
     return max(np.linalg.norm(g - w) / np.linalg.norm(w) for g, w in zip(got, want))
 
 
-@pytest.mark.parametrize("n", [2048, 2049, 16000, 5 * 1024])
+@pytest.mark.parametrize("n", [2048, 2049, 16000, 5 * 1024, 32000, 33 * 1024])   # the last two: a second tile of frames
 def test_stft_istft_against_the_restatement(n):
     rng = np.random.default_rng(n)
     x = rng.standard_normal((3, n)).astype(np.float32)

@@ -151,6 +151,21 @@ def test_value_errors_before_any_device_call(no_device):
         O.istft(np.zeros((1025, 4), np.complex64), 3 * 1024 + 1)
 
 
+def test_empty_calls_succeed_with_null_pointers_and_no_device():
+    """An empty tensor has no storage (torch gives it a null data pointer): length = 0, zero signals and n = 0, all inside the
+    ranges of include/glowk.h, return 0 before any pointer or device is looked at; the same sizes out of range are refused."""
+    lib = _lib.load()
+    z = None
+    assert lib.glowk_sp_istft(z, 3, 34, 0, z, z) == 0
+    assert lib.glowk_sp_istft(z, 0, 34, 100, z, z) == 0
+    assert lib.glowk_sp_stft(z, 0, 5000, z, z) == 0
+    assert lib.glowk_oracle_mel(z, z, 7, 0, 0, 1, 0.5, z, z) == 0
+    assert lib.glowk_sp_istft(z, 3, 34, -1, z, z) != 0 and b"length" in lib.glowk_last_error()
+    assert lib.glowk_sp_istft(z, 3, 34, 100, z, z) != 0 and b"null" in lib.glowk_last_error()
+    assert lib.glowk_sp_stft(z, 1, 5000, z, z) != 0 and b"null" in lib.glowk_last_error()
+    assert lib.glowk_oracle_mel(z, z, 7, 1, 0, 1, 0.5, z, z) != 0 and b"null" in lib.glowk_last_error()
+
+
 def test_frame_count():
     assert [O.nframes(n) for n in (1, 1024, 1025, 2048, 2049, 16000)] == [2, 2, 3, 3, 4, 17]
     assert all(O.nframes(n) == R.nframes(n) for n in range(1, 5000, 37))
