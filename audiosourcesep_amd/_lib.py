@@ -112,7 +112,10 @@ SYMBOLS = {
     "glowk_mel_to_power": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "glowk_masked_istft": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "glowk_griffinlim": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp]),
-    "glowk_bss_xcorr": (_i, [_vp, _i, ctypes.c_int64, _vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp]),
+    "glowk_resample_length": (ctypes.c_int64, [ctypes.c_int64, _i, _i]),
+    "glowk_resample_filter": (_i, [ctypes.POINTER(ctypes.c_double)]),
+    "glowk_resample": (_i, [_vp, _i, ctypes.c_int64, _i, _i, _vp, _vp]),
+    "glowk_bss_xcorr":(_i, [_vp, _i, ctypes.c_int64, _vp, _i, ctypes.c_int64, _vp, _i, _i, _vp, _vp]),
     "glowk_bss_solve": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "glowk_bss_project": (_i, [_vp, ctypes.c_int64, _i, _i, _i, _vp, _i, ctypes.c_int64, _vp, _i, _vp, _i, _vp, _vp]),
     "glowk_sp_stft": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp]),

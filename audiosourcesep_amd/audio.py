@@ -14,12 +14,18 @@ Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) 
   spectrum staging; the whole loop is one C call.  ``init='random'`` draws its phases from the device RNG (stream
   ``GRIFFINLIM_STREAM`` of ``seed``), not from NumPy's global RNG, so librosa's own random start is not reproduced;
 * ``invert``: reuse the mixture's phase (or a single-channel Wiener filter over the sources) or Griffin-Lim, per tile
-  (``method='frame'``) or on the tiles concatenated along time (``'whole'``).
+  (``method='frame'``) or on the tiles concatenated along time (``'whole'``);
+* ``resample`` / ``load_audio`` / ``save_audio`` / ``separate_wav``: PCM wavs of 8 to 32 bits at any rate in, 16-bit wavs at any
+  rate out, around a band-limited sample-rate converter on the GPU (``csrc/glowk_resample.h``) -- what ``librosa.core.load(path,
+  sr=16000)`` does for the reference (datasets/preprocessing.py:21).  The filter is the same design as librosa 0.7's default
+  (resampy's ``kaiser_best``), evaluated at the exact position of every tap; it is not bit-compatible with resampy, whose samples
+  cannot be observed here (derived, not observed).  ``read_wav`` / ``write_wav`` / ``separate_audio`` keep to 16 kHz.
 
-Not covered: resampling (input must be 16 kHz), the power-scale flows (``scale='power'``) and stereo output.
+Not covered: IEEE-float and WAVE_FORMAT_EXTENSIBLE wavs, the power-scale flows (``scale='power'``) and stereo separation.
 """
 import ctypes
 import math
+import struct
 import warnings
 import wave
 
@@ -36,6 +42,7 @@ NMEL = MEL_FRONTEND["n_mels"]
 EXTRACT = int(SR * MEL_FRONTEND["length_sec"])          # 32 640 samples (datasets/preprocessing.py:9-26)
 GRIFFINLIM_STREAM = 13      # device RNG stream of init='random' (stream ids are 0..15; 0-3 serve the flows, 14 / 15 separate_audio)
 GRIFFINLIM_MAX_FRAMES = 1 << 20                          # glowk_griffinlim's cap: 9.3 h of 16 kHz audio in one signal
+MIN_RATE, MAX_RATE = 1000, 768000                        # glowk_resample's sampling rates, at most a factor 64 apart
 ALGORITHMS = ("reuse_phase", "griffin")
 METHODS = ("frame", "whole")
 
@@ -71,6 +78,105 @@ def write_wav(path, y, sr=SR):
         w.setsampwidth(2)
         w.setframerate(sr)
         w.writeframes(q.tobytes())
+
+
+def _check_rate(sr, what):
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not MIN_RATE <= sr <= MAX_RATE:
+        raise ValueError("%s: expected an integer sampling rate in [%d, %d] Hz, got %r" % (what, MIN_RATE, MAX_RATE, sr))
+    return int(sr)
+
+
+def resample(y, orig_sr, target_sr):
+    """librosa.resample(y, orig_sr, target_sr) on the GPU: [n] or [..., n] (numpy or torch, any device) -> float32 CUDA tensor
+    [..., ceil(n * target_sr / orig_sr)] (``glowk_resample``: one launch for all signals, bitwise reproducible).
+
+    Same filter design as librosa 0.7's default (resampy's ``kaiser_best``: Kaiser-windowed sinc, 64 zero crossings), evaluated at
+    the exact tap positions; not bit-compatible with it; derived, not observed.  Rates are integers in [1000, 768000] Hz, at most
+    a factor 64 apart.  Equal rates return the input as a float32 tensor where it is, without a launch (as librosa does)."""
+    orig_sr, target_sr = _check_rate(orig_sr, "orig_sr"), _check_rate(target_sr, "target_sr")
+    if max(orig_sr, target_sr) > 64 * min(orig_sr, target_sr):
+        raise ValueError("target_sr: expected within a factor 64 of orig_sr = %d Hz, got %d" % (orig_sr, target_sr))
+    x = _tensor(y, "y")
+    if x.dim() < 1:
+        raise ValueError("y: expected [n] or [..., n] audio, got a scalar")
+    if orig_sr == target_sr:
+        return x.to(torch.float32)
+    x = x.to(device=_device(x), dtype=torch.float32).contiguous()
+    lib = _lib.load()
+    n, nsig = x.shape[-1], x.numel() // max(x.shape[-1], 1)
+    if nsig > 1 << 20:
+        raise ValueError("y: expected at most 2^20 signals, got %d" % nsig)
+    out = torch.empty(tuple(x.shape[:-1]) + (lib.glowk_resample_length(n, orig_sr, target_sr),), device=x.device, dtype=torch.float32)
+    _lib.check(lib.glowk_resample(_p(x), nsig, n, orig_sr, target_sr, _p(out), _s(x)))
+    return out
+
+
+def _wav_format_tag(path):
+    """wFormatTag of a RIFF/WAVE file's fmt chunk (1 = PCM, 3 = IEEE float, 0xFFFE = WAVE_FORMAT_EXTENSIBLE)."""
+    with open(str(path), "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:] != b"WAVE":
+            raise ValueError("%s: not a RIFF/WAVE file" % (path,))
+        while True:
+            ck = f.read(8)
+            if len(ck) < 8:
+                raise ValueError("%s: no fmt chunk" % (path,))
+            size = struct.unpack("<I", ck[4:])[0]
+            if ck[:4] == b"fmt ":
+                body = f.read(2)
+                if len(body) < 2:
+                    raise ValueError("%s: truncated fmt chunk" % (path,))
+                return struct.unpack("<H", body)[0]
+            f.seek(size + (size & 1), 1)
+
+
+def load_audio(path, sr=SR, mono=True):
+    """librosa.core.load(path, sr=sr, mono=mono) for PCM wavs: 8 (unsigned), 16, 24 or 32 bits at any rate -> ``(y, native_rate)``.
+    Samples are scaled to [-1, 1) by 2^(bits - 1); ``mono`` averages the channels (librosa.to_mono), else y is [channels, n].
+    ``sr``: the rate y is resampled to on the GPU (``resample``; a float32 CUDA tensor); ``None`` or the file's own rate: no
+    resampling, no GPU, a float32 host tensor.  IEEE-float and WAVE_FORMAT_EXTENSIBLE files raise ValueError."""
+    if sr is not None:
+        sr = _check_rate(sr, "sr")
+    tag = _wav_format_tag(path)
+    if tag != 1:
+        kind = {3: "IEEE float", 0xFFFE: "WAVE_FORMAT_EXTENSIBLE"}.get(tag, "format tag 0x%04x" % tag)
+        raise ValueError("%s: only plain PCM wavs are supported (format tag 1), this file is %s" % (path, kind))
+    try:
+        with wave.open(str(path), "rb") as w:
+            rate, ch, width = w.getframerate(), w.getnchannels(), w.getsampwidth()
+            raw = w.readframes(w.getnframes())
+    except wave.Error as e:
+        raise ValueError("%s: not a readable PCM wav (%s)" % (path, e))
+    if width not in (1, 2, 3, 4):
+        raise ValueError("%s: expected 8, 16, 24 or 32-bit PCM, got a sample width of %d bytes" % (path, width))
+    raw = raw[:len(raw) - len(raw) % (width * ch)]
+    if width == 1:
+        v = np.frombuffer(raw, dtype=np.uint8).astype(np.int64) - 128
+    elif width == 3:
+        b3 = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int64)
+        v = ((b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)) ^ 0x800000) - 0x800000
+    else:
+        v = np.frombuffer(raw, dtype="<i2" if width == 2 else "<i4").astype(np.int64)
+    y = (v.astype(np.float64) / float(1 << (8 * width - 1))).reshape(-1, ch).T          # [channels, n]
+    y = torch.from_numpy((y.mean(axis=0) if mono else y).astype(np.float32))
+    if sr is not None and sr != rate:
+        _check_rate(rate, "%s: sampling rate" % (path,))
+        y = resample(y, rate, sr)
+    return y, rate
+
+
+def save_audio(path, y, sr):
+    """float [n] or [channels, n] -> 16-bit PCM wav at ``sr`` Hz (round(y * 32767), clipped to [-1, 1] first, like ``write_wav``)."""
+    sr = _check_rate(sr, "sr")
+    y = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+    if y.ndim not in (1, 2) or (y.ndim == 2 and not 1 <= y.shape[0] <= 65535):
+        raise ValueError("y: expected [n] or [channels, n] audio, got %s" % (tuple(y.shape),))
+    q = np.rint(np.clip(y.astype(np.float64), -1.0, 1.0) * 32767.0).astype("<i2")
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(1 if y.ndim == 1 else y.shape[0])
+        w.setsampwidth(2)
+        w.setframerate(sr)
+        w.writeframes(np.ascontiguousarray(q.T).tobytes())              # frames interleave the channels
 
 
 def extracts(y, skip=0, n=None):
@@ -318,3 +424,19 @@ def separate_audio(mix, flow1, flow2, sigmas, restore_1=None, restore_2=None, T=
                                        seed=seed)
     out = invert([x1, x2], X, wiener=wiener, iters=iters, algorithm=algorithm, method=method, n_iter=n_iter, momentum=momentum, seed=seed)
     return out[0], out[1], mixed, x1, x2
+
+
+def separate_wav(path, flow1, flow2, sigmas, out_rate="input", **kwargs):
+    """A PCM wav at any rate -> two separated signals at ``out_rate``: ``load_audio(path, sr=16000)`` (channels averaged, resampled
+    on the GPU), ``separate_audio`` on the 16 kHz samples (``kwargs`` are its keyword arguments), the two signals resampled in
+    one launch.  ``out_rate``: 'input' (the file's rate), an integer rate, or None (left at 16 kHz).  Returns what
+    ``separate_audio`` returns plus the output rate: ``(y1, y2, mixed, x1, x2, rate)``."""
+    if not (out_rate is None or (isinstance(out_rate, str) and out_rate == "input")):
+        if isinstance(out_rate, str):
+            raise ValueError("out_rate: expected 'input', None or an integer sampling rate, got %r" % (out_rate,))
+        out_rate = _check_rate(out_rate, "out_rate")
+    y, native = load_audio(path, sr=SR, mono=True)
+    rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
+    y1, y2, mixed, x1, x2 = separate_audio(y, flow1, flow2, sigmas, **kwargs)
+    y1, y2 = resample(torch.stack([y1, y2]), SR, rate)
+    return y1, y2, mixed, x1, x2, rate

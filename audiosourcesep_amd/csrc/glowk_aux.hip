@@ -1,11 +1,12 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
-// systems (glowk_oracle.h)
+// systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
 #include "glowk_bsseval.h"
 #include "glowk_oracle.h"
+#include "glowk_resample.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -385,6 +386,116 @@ int glowk_griffinlim(const float* mag_dev, const float* angles0_dev, int N, int 
     hipLaunchKernelGGL(k_istft<GriffinSource>, is_grid, dim3(256), 0, s, src, frames, htiles, c, audio_dev);
     LAUNCHCHK("k_istft");
   }
+  return 0;
+}
+
+// ---- sample-rate conversion (glowk_resample.h) ------------------------------------------------------------------------------------
+namespace glowk_eng {
+// I0 by its power series sum_k ((x / 2)^k / k!)^2: all terms positive, so fp64 keeps ~1e-16 relative at the beta used here
+static double bessel_i0(double x) {
+  const double h = 0.5 * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    term *= (h / k) * (h / k);
+    sum += term;
+    if (term < 1e-18 * sum) break;
+  }
+  return sum;
+}
+
+struct ResampleHost {
+  std::vector<double> T;            // [Z P + 1]
+  std::vector<float2> pairs;        // (T[k], T[k + 1] - T[k]) rounded once; the last difference is 0
+  ResampleHost() {
+    using namespace glowk_rs;
+    const double pi = 3.14159265358979323846, beta = 14.769656459379492, rolloff = 0.9475937167399596;
+    const double i0b = bessel_i0(beta);
+    T.resize(RS_ZP + 1);
+    for (int k = 0; k <= RS_ZP; ++k) {
+      const double u = (double)k / RS_ZP, x = pi * rolloff * k / RS_P;
+      const double sinc = k == 0 ? 1.0 : std::sin(x) / x;
+      T[k] = rolloff * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b;
+    }
+    pairs.resize(RS_ZP + 1);
+    for (int k = 0; k <= RS_ZP; ++k) pairs[k] = make_float2((float)T[k], k < RS_ZP ? (float)(T[k + 1] - T[k]) : 0.0f);
+  }
+};
+
+static const ResampleHost& resample_host() {
+  static const ResampleHost host;              // function-local static: built once, thread-safe by the language
+  return host;
+}
+
+// one upload per device, kept for the life of the process (allocated under the caller's DeviceGuard), like audio_consts
+static int resample_table(int dev, const float2** out) {
+  const ResampleHost& host = resample_host();
+  static std::mutex mu;
+  static std::vector<std::pair<int, const float2*>> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& e : cache)
+    if (e.first == dev) { *out = e.second; return 0; }
+  DeviceMem<float2> tab;
+  HIPCHK(dev_alloc(tab, host.pairs.size() * sizeof(float2)));
+  HIPCHK(hipMemcpy(tab, host.pairs.data(), host.pairs.size() * sizeof(float2), hipMemcpyHostToDevice));
+  *out = tab.release();
+  cache.emplace_back(dev, *out);
+  return 0;
+}
+
+// the arguments glowk_resample takes: rates, ratio and length; a, b = the rates over their gcd
+static int resample_check(int64_t n_in, int sr_in, int sr_out, uint32_t* a, uint32_t* b) {
+  if (sr_in < 1000 || sr_in > 768000 || sr_out < 1000 || sr_out > 768000) return fail("resample: sr_in and sr_out must be in [1000, 768000]");
+  if ((int64_t)sr_out > 64 * (int64_t)sr_in || (int64_t)sr_in > 64 * (int64_t)sr_out) return fail("resample: sr_out / sr_in must be in [1/64, 64]");
+  if (n_in < 0 || n_in > ((int64_t)1 << 32)) return fail("resample: n_in must be in [0, 2^32]");
+  uint32_t x = (uint32_t)sr_in, y = (uint32_t)sr_out;
+  while (y) { const uint32_t z = x % y; x = y; y = z; }
+  *a = (uint32_t)sr_in / x;
+  *b = (uint32_t)sr_out / x;
+  return 0;
+}
+}  // namespace glowk_eng
+
+int64_t glowk_resample_length(int64_t n_in, int sr_in, int sr_out) {
+  uint32_t a, b;
+  if (resample_check(n_in, sr_in, sr_out, &a, &b)) return -1;
+  return (n_in * (int64_t)b + a - 1) / a;        // n_in b < 2^52
+}
+
+int glowk_resample_filter(double* host_out) {
+  if (!host_out) return fail("null buffer");
+  const ResampleHost& host = resample_host();
+  std::memcpy(host_out, host.T.data(), host.T.size() * sizeof(double));
+  return 0;
+}
+
+int glowk_resample(const float* x_dev, int nsig, int64_t n_in, int sr_in, int sr_out, float* y_dev, void* stream) {
+  using namespace glowk_rs;
+  uint32_t a, b;
+  if (int rc = resample_check(n_in, sr_in, sr_out, &a, &b)) return rc;
+  if (nsig < 0 || nsig > (1 << 20)) return fail("resample: nsig must be in [0, 2^20]");
+  if (nsig == 0 || n_in == 0) return 0;          // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!x_dev || !y_dev) return fail("null tensor");
+  ResampleArgs g;
+  g.x = x_dev; g.y = y_dev; g.n_in = n_in; g.n_out = (n_in * (int64_t)b + a - 1) / a;
+  g.a = a; g.b = b; g.d = std::max(a, b);
+  g.stepk = (uint32_t)(((uint64_t)b * RS_P) / g.d); g.stepr = (uint32_t)(((uint64_t)b * RS_P) % g.d);
+  g.H = (int)(((int64_t)RS_Z * g.d) / b) + 1;    // <= 4097 at the ratio 1/64
+  g.scale = (float)std::min(1.0, (double)b / (double)a); g.inv_d = 1.0f / (float)g.d;
+  // the staged span of tb outputs: their centres cover at most floor((tb - 1) a / b) + 1 steps, plus H samples on each side
+  auto span = [&](int tb) { return ((int64_t)(tb - 1) * a) / b + 2 * (int64_t)g.H + 2; };
+  g.tb = RS_THREADS;
+  if (span(g.tb) > RS_LDS_FLOATS) {
+    g.tb = (int)(((RS_LDS_FLOATS - 2 * (int64_t)g.H - 2) * b) / a) + 1;
+    while (g.tb > 1 && span(g.tb) > RS_LDS_FLOATS) --g.tb;
+  }
+  g.blocks_per_sig = (g.n_out + g.tb - 1) / g.tb;
+  if (g.blocks_per_sig * nsig > (int64_t)INT32_MAX) return fail("resample: too many signals x outputs for one launch");
+  int dev;
+  if (int rc = audio_device({x_dev, y_dev}, &dev, "resample")) return rc;
+  DeviceGuard dg(dev);
+  if (int rc = resample_table(dev, &g.tab)) return rc;
+  hipLaunchKernelGGL(k_resample, dim3((unsigned)(g.blocks_per_sig * nsig)), dim3(RS_THREADS), (size_t)span(g.tb) * sizeof(float), (hipStream_t)stream, g);
+  LAUNCHCHK("k_resample");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 450
+#define GLOWK_VERSION 460
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -324,6 +324,27 @@ int glowk_masked_istft(const float* power_dev, int S, const float* stft_mix_dev,
  * reproducible. */
 int glowk_griffinlim(const float* mag_dev, const float* angles0_dev, int N, int frames, int n_iter, float momentum, float* audio_dev,
                      void* stream);
+
+/* --- sample-rate conversion: the resampling of librosa.core.load (datasets/preprocessing.py:21) ---------------------------- */
+/* Handle-free.  The filter is librosa 0.7's default design (resampy's kaiser_best: Kaiser-windowed sinc, 64 zero crossings, 512
+ * table points per zero crossing, beta = 14.769656459379492, roll-off 0.9475937167399596), evaluated at the exact position of every
+ * tap: same design, not bit-compatible with resampy (whose samples cannot be observed here; derived, not observed).  With a, b =
+ * sr_in, sr_out over their gcd, s = min(1, b / a) and t a = q b + r in 64-bit integers:
+ *   y[t] = s sum_m x[m] h(s ((q - m) + r / b)),  h(u) = T[k] + (p - k) (T[k + 1] - T[k]) with p = |u| 512, k = floor(p), 0 for p > 32768,
+ *   T[k] = rho sinc(rho k / 512) I0(beta sqrt(1 - (k / 32768)^2)) / I0(beta);  x is zero outside [0, n_in).
+ * Ranges: sr_in, sr_out in [1000, 768000] with 1/64 <= sr_out / sr_in <= 64, nsig in [0, 2^20], n_in in [0, 2^32]; anything else
+ * is GLOWK_ERR. */
+/* ceil(n_in * sr_out / sr_in), or -1 for arguments the conversion would refuse; no device call */
+int64_t glowk_resample_length(int64_t n_in, int sr_in, int sr_out);
+/* the table T [32769] (double) as the kernel's host builder makes it, into a host buffer; no device call */
+int glowk_resample_filter(double* host_out);
+/* x [nsig][n_in] -> y [nsig][n_out], n_out as above; float32 device memory on one device (a host pointer is refused), one launch
+ * on `stream`, no allocation beyond the first call's table upload on a device, no host synchronisation.  fp32 accumulation in an
+ * order fixed relative to each output's centre q: bitwise reproducible, and independent of nsig, of n_in and of the position in
+ * the signal (x delayed by a samples gives y delayed by b).  nsig == 0 or n_in == 0 is a successful no-op.  sr_in == sr_out runs
+ * the filter (a low-pass at 0.9476 of Nyquist, not the identity): audio.resample returns its input for equal rates instead.  One
+ * launch holds at most 2^31 - 1 workgroups of 256 outputs (fewer per workgroup when sr_in / sr_out exceeds 40). */
+int glowk_resample(const float* x_dev, int nsig, int64_t n_in, int sr_in, int sr_out, float* y_dev, void* stream);
 
 /* --- BSS Eval v4: SDR / ISR / SIR / SAR (bsseval_v4.py, sigsep's v4 with the v3 wrappers) ----------------------------------- */
 /* Handle-free, fp64 throughout.  sig_dev [nsig][nsampl] holds the reference channels p = j * nchan + c (P = nsrc * nchan of
