@@ -350,6 +350,7 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   }
 
   // im2col fragments of this lane's two pixels: k-step s holds k = 32 s + 8 kq + j (natural order), scaled and split
+  // (stacked forward conv1, RingS::STK: xh[s] / xl[s] = the B fragments of stacked k-steps 2 s / 2 s + 1)
   h8 xh[KS][2], xl[KS][2];
   float xmax = 0.0f;                 // range guard: largest |network input| (scaled) this lane gathers
   {
@@ -379,6 +380,8 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
           for (int j = 0; j < 8; ++j) v[s][j] *= fac;
           split8(v[s], xh[s][hf], xl[s][hf]);
         }
+      } else if constexpr (S::STK) {
+        xmax = gather_stacked<KIN, SGN, G::MODE7 == NET_FWD2, KS, S::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], kq, xh, xl, hf, xmax);
       } else {
 #pragma unroll
         for (int s = 0; s < KS; ++s) {

@@ -632,6 +632,74 @@ __device__ __forceinline__ void gather8(const float* base, int i, int j0, int h,
   }
 }
 
+// The B fragment of the STACKED forward conv1 (glowk_act_scale.h; RingS::STK): slots p0 .. p0 + 7 (p0 a multiple of 8) of
+// [x_hi | x_lo | x_hi | c c | 0 ...], slot p < 3 K1 = im2col entry p mod K1 of the pixel, gathered, scaled and split as gather8 + split8
+// do.  K1 and with it every segment start is a multiple of the channel group G, so a group of G slots is one vector load and one
+// segment -- hi or lo is chosen per group (a lane's eight slots may straddle two segments: K1 = 18).  TWO (NET_FWD2: no w_hi x_lo term):
+// the x_lo segment is zero.  Returns the range guard's maximum over every gathered value (and the bias constant, as gather8's
+// callers count it).
+template <int KIN, int SGN, bool TWO>
+__device__ __forceinline__ float gather8_stacked(const float* base, int i, int j0, int h, int w, int in_stride, bool qok, int p0, h8& f, float xmax) {
+  constexpr int K1 = 9 * KIN;
+  constexpr int G = KIN < 8 ? KIN : 8;
+  static_assert(G == 2 || G == 4 || G == 8, "channel group");
+#pragma unroll
+  for (int t = 0; t < 8 / G; ++t) {
+    const int p = p0 + t * G;
+    const int seg = p / K1, k = p - seg * K1;
+    const int tap = k / KIN, cin = k % KIN;
+    const int dy = SGN * (tap / 3 - 1), dx = SGN * (tap % 3 - 1);
+    const int ii = i + dy, jj = j0 + dx;
+    const bool ok = qok && seg < 3 && ii >= 0 && ii < h && jj >= 0 && jj < w;
+    const float* ptr = base + (ok ? (dy * w + dx) * in_stride + cin : 0);     // clamped: always in bounds
+    // "ok ? x : constant" as bit masks held in VGPRs, opaque to the compiler: as selects, the lane masks of all 16 groups of a lane stay live
+    // in SGPR pairs across the loads' latency, and the fused instances then park four SGPRs in a VGPR across the whole kernel
+    int okv = ok ? -1 : 0, cbv = p == 3 * K1 ? __float_as_int(GLOWK_ACT_SCALE) : 0;     // slots 3 K1, 3 K1 + 1: the bias constant against b_hi, b_lo
+    asm volatile("" : "+v"(okv), "+v"(cbv));
+    float x[G];
+    if constexpr (G == 8) {
+      const float4 a = *reinterpret_cast<const float4*>(ptr), b = *(reinterpret_cast<const float4*>(ptr) + 1);
+      x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+    } else if constexpr (G == 4) {
+      const float4 a = *reinterpret_cast<const float4*>(ptr);
+      x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
+    } else {
+      const float2 a = *reinterpret_cast<const float2*>(ptr);
+      x[0] = a.x; x[1] = a.y;
+    }
+#pragma unroll
+    for (int e = 0; e < G; e += 2) {
+      const int cbe = e == 0 ? cbv : 0;                                       // (the group at 3 K1 is never `ok`: or-ing is selecting)
+      const f32x2 v = {__int_as_float((__float_as_int(x[e] * GLOWK_ACT_SCALE) & okv) | cbe), __int_as_float((__float_as_int(x[e + 1] * GLOWK_ACT_SCALE) & okv) | cbe)};
+      xmax = nan_max(nan_max(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));
+      const h2v hi = __builtin_convertvector(v, h2v);                         // (split8's arithmetic)
+      const h2v lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), h2v);
+      const h2v z = {(_Float16)0.0f, (_Float16)0.0f};
+      const h2v sel = seg == 1 ? (TWO ? z : lo) : hi;
+      f[t * G + e] = sel[0]; f[t * G + e + 1] = sel[1];
+    }
+  }
+  return xmax;
+}
+// ... all of a pixel's stacked fragments: xh[s] / xl[s] = stacked k-steps 2 s / 2 s + 1 (a k-step beyond KSX is never read)
+template <int KIN, int SGN, bool TWO, int KS, int KSX>
+__device__ __forceinline__ float gather_stacked(const float* base, int i, int j0, int h, int w, int in_stride, bool qok, int kq, h8 (&xh)[KS][2],
+                                                h8 (&xl)[KS][2], int hf, float xmax) {
+#pragma unroll
+  for (int sx = 0; sx < 2 * KS; ++sx) {
+    h8& f = (sx & 1) ? xl[sx >> 1][hf] : xh[sx >> 1][hf];
+    if (sx < KSX) xmax = gather8_stacked<KIN, SGN, TWO>(base, i, j0, h, w, in_stride, qok, 32 * sx + 8 * kq, f, xmax);
+    else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = (_Float16)0.0f;
+    }
+  }
+  return xmax;
+}
+// (B fragment of stacked k-step sx, pixel half hf)
+template <int KS>
+__device__ __forceinline__ const h8& x_frag(const h8 (&xh)[KS][2], const h8 (&xl)[KS][2], int sx, int hf) { return (sx & 1) ? xl[sx >> 1][hf] : xh[sx >> 1][hf]; }
+
 // end of a phase.  DMA is only issued by ops that end with the bare barrier (Y); the op after it (X, Z) ends with
 // "everything of this wave has landed" + barrier, so a piece has two phases to land and is published by the second barrier.
 // The waits are builtins so that the compiler's own wait-count bookkeeping sees them.
@@ -1054,6 +1122,12 @@ struct RingS {
   static constexpr int MAIN4 = MAINP * 64;
   static constexpr int K1P = KS * 4;                              // one block's conv1 operands: KS x 2 row blocks x (hi, lo)
   static constexpr int K14 = K1P * 64;
+  // forward conv1 STACKED along K (glowk_act_scale.h): KSX k-steps of ONE MFMA on [w_hi | w_hi | w_lo | b_hi b_lo] x [x_hi | x_lo | x_hi | c c]
+  // instead of KS k-steps of three.  Taken where KSX <= 2 KS, so the block's operands are the same K1P pieces ([k-step][row block]) and
+  // the B fragments the same registers: the kernels' xh[s] / xl[s] then hold the fragments of stacked k-steps 2 s / 2 s + 1 (x_frag).
+  // (The KS limits in FITS below are register limits in units of one three-term k-step = two stacked ones: unchanged.)
+  static constexpr bool STK = !BWD && glowk_conv1_stacked(K1);
+  static constexpr int KSX = STK ? glowk_conv1_ks_stacked(K1) : KS;
   static constexpr int M3 = MOUT;
   static constexpr int NMT = (M3 + 15) / 16;                      // 16-row blocks of P
   static constexpr int TPC = MAINP / 2;                           // conv3 tiles (16 rows x 32 k, hi + lo) per chunk
@@ -1191,8 +1265,21 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) h1[i >> 1][i & 1][r] = 0.0f;
-  const h8* k1 = reinterpret_cast<const h8*>(KP ? c.k1s1 : c.k1s0) + lane;   // [s][row block][hi|lo][64]
-  if constexpr (G::KS <= 3) {       // all operand reads in flight before the first MFMA
+  const h8* k1 = reinterpret_cast<const h8*>(KP ? c.k1s1 : c.k1s0) + lane;   // [s][row block][hi|lo][64]; stacked: [s][row block][64]
+  if constexpr (G::STK) {           // one MFMA per stacked k-step (the two-term mode's B fragments carry zeros for x_lo: gather8_stacked)
+    static_assert(G::KSX <= 6, "operand reads in flight");
+    h8 kf[G::KSX * 2];
+#pragma unroll
+    for (int i = 0; i < G::KSX * 2; ++i) kf[i] = k1[i * 64];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < G::KSX; ++s)
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int hf = 0; hf < G::PXH; ++hf)
+          h1[rb][hf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s * 2 + rb], x_frag(xh, xl, s, hf), h1[rb][hf], 0, 0, 0);
+  } else if constexpr (G::KS <= 3) {       // all operand reads in flight before the first MFMA
     h8 kf[G::K1P];
 #pragma unroll
     for (int i = 0; i < G::K1P; ++i) kf[i] = k1[i * 64];
@@ -1563,6 +1650,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
       stage4<NF, 65>(reinterpret_cast<const float4*>(a.mask2 + (size_t)blockIdx.x * 8 * NF * 64), reinterpret_cast<float4*>(mkl + 8 * NF * 64), c.w4, c.voff);
   }
   // im2col fragments of this lane's two pixels: k-step s holds k = 32 s + 8 kq + j (natural order), scaled and split
+  // (stacked forward conv1, RingS::STK: xh[s] / xl[s] = the B fragments of stacked k-steps 2 s / 2 s + 1)
   h8 xh[KS][2], xl[KS][2];
   float xmax = 0.0f;                 // range guard: largest |network input| (scaled) this lane gathers
   {
@@ -1592,6 +1680,8 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
           for (int j = 0; j < 8; ++j) v[s][j] *= fac;
           split8(v[s], xh[s][hf], xl[s][hf]);
         }
+      } else if constexpr (G::STK) {
+        xmax = gather_stacked<KIN, SGN, net_dir<MODE> == NET_FWD2, KS, G::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], kq, xh, xl, hf, xmax);
       } else {
 #pragma unroll
         for (int s = 0; s < KS; ++s) {

@@ -374,6 +374,17 @@ bool pack_step(const glowk_config& cfg, const Level& lv, int k, float* dst, doub
     uint16_t* dsth = reinterpret_cast<uint16_t*>(row_lane) + (size_t)hl * 64 * 8;
     dsth[j] = hl ? lo : hi;
   };
+  // ... and the form for layouts that do not keep a value's halves 64 lanes apart (the stacked conv1 operands): half `hl` of the
+  // element at half position j of this lane's 16 bytes, nothing else
+  auto put_half = [dst, f16_map](float* lane16, int j, int hl, float w, int S) {
+    if (f16_map) {
+      f16_map[(size_t)(lane16 - dst) * 2 + j] = (int)w ? ((int)w | (hl << 30)) : 0;
+      return;
+    }
+    const float ws = std::ldexp(w, S);
+    const uint16_t hi = f32_to_f16(ws);
+    reinterpret_cast<uint16_t*>(lane16)[j] = hl ? f32_to_f16(ws - f16_to_f32(hi)) : hi;
+  };
   if (L.slotH || L.slotS) {
     const int KS = (9 * CI + 1 + 15) / 16;
     // Every per-channel constant of the epilogues is folded into the weights (host, fp64):
@@ -502,6 +513,22 @@ bool pack_step(const glowk_config& cfg, const Level& lv, int k, float* dst, doub
       const int NCH = (NT + TPC - 1) / TPC;
       const size_t k1blkS = (size_t)KSS * 4 * 256;
       float* imgS = dst + L.RSp;
+      // conv1 operands.  Stacked (glowk_act_scale.h: glowk_conv1_stacked; c = 4, 8): per block [k-step s][row block][64 lanes] half8,
+      // slot p = 32 s + 8 kq + j of the stacked contraction = w_hi | w_hi | w_lo of row p mod K1 (segments p / K1 = 0, 1, 2), then
+      // b_hi, b_lo of the bias row, then zeros -- the same 4 KSS pieces per block as the three-term layout below
+      const int K1n = 9 * CI;
+      if (glowk_conv1_stacked(K1n)) {
+        for (int blk = 0; blk < NF; ++blk)
+          for (int s2 = 0; s2 < 2 * KSS; ++s2)
+            for (int rb = 0; rb < 2; ++rb)
+              for (int l = 0; l < 64; ++l)
+                for (int j = 0; j < 8; ++j) {
+                  const int i = l & 15, kq = l >> 4, p = 32 * s2 + 8 * kq + j;
+                  const int kk = p < 3 * K1n ? p % K1n : p <= 3 * K1n + 1 ? K1n : -1, hl = p < 3 * K1n ? (p / K1n == 2) : (p == 3 * K1n + 1);
+                  const float w = kk >= 0 ? K1f[(size_t)kk * F + blk * 32 + rb * 16 + i] : 0.0f;
+                  put_half(imgS + (size_t)blk * k1blkS + ((size_t)(s2 * 2 + rb) * 64 + l) * 4, j, hl, w, S1);
+                }
+      } else
       for (int blk = 0; blk < NF; ++blk)
         for (int s2 = 0; s2 < KSS; ++s2)
           for (int rb = 0; rb < 2; ++rb)

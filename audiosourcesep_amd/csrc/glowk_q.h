@@ -58,7 +58,7 @@ struct QSlots {
 
 // X batch B: conv1 + activation + split of hidden blocks B XB .. B XB + XB - 1 (operands in k[B & 1][*]).  The 2 XB accumulator chains
 // (block, row block) are interleaved term by term, so dependent MFMAs sit 2 XB apart; per chain the order (k-step, then lo.hi, hi.lo,
-// hi.hi) is that of h3s_X: bit for bit the same hidden activations.
+// hi.hi; stacked conv1, RingS::STK: one MFMA per stacked k-step) is that of h3s_X: bit for bit the same hidden activations.
 template <int KIN, int MOUT, int NF, int MODE, int PASS, int B>
 __device__ __forceinline__ void q_X_batch(const NetArgs& a, const H3Ctx& c, const QSlots& sl, const h8 (&xh)[(RingQ<KIN, MOUT, NF, MODE>::KS)][2],
                                           const h8 (&xl)[(RingQ<KIN, MOUT, NF, MODE>::KS)][2], int g, int lane, h8 (&bfh)[NF / 2], h8 (&bfl)[NF / 2]) {
@@ -96,8 +96,13 @@ __device__ __forceinline__ void q_X_batch(const NetArgs& a, const H3Ctx& c, cons
     for (int x = 0; x < XB; ++x)
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
-        A[buf][x][rb][0] = k1[x][((s * 2 + rb) * 2 + 0) * 64];
-        A[buf][x][rb][1] = k1[x][((s * 2 + rb) * 2 + 1) * 64];
+        if constexpr (S::STK) {      // stacked conv1: the operands of stacked k-steps 2 s, 2 s + 1 ([k-step][row block][64])
+          A[buf][x][rb][0] = k1[x][((2 * s) * 2 + rb) * 64];
+          A[buf][x][rb][1] = k1[x][((2 * s + 1) * 2 + rb) * 64];
+        } else {
+          A[buf][x][rb][0] = k1[x][((s * 2 + rb) * 2 + 0) * 64];
+          A[buf][x][rb][1] = k1[x][((s * 2 + rb) * 2 + 1) * 64];
+        }
       }
   };
   load(0, 0);
@@ -105,16 +110,26 @@ __device__ __forceinline__ void q_X_batch(const NetArgs& a, const H3Ctx& c, cons
   for (int s = 0; s < KS; ++s) {
     if (s + 1 < KS) load((s + 1) & 1, s + 1);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (S::STK) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < 2; ++t)      // stacked k-steps 2 s, 2 s + 1: one MFMA each, per chain in h3s_X's order
 #pragma unroll
-      for (int x = 0; x < XB; ++x)
+        for (int x = 0; x < XB; ++x)
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-          const h8& av = A[s & 1][x][rb][t == 0 ? 1 : 0];            // lo . hi, then hi . lo, hi . hi
-          const h8& bv = t == 1 ? xl[s][0] : xh[s][0];
-          h1[x][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, h1[x][rb], 0, 0, 0);
-        }
+          for (int rb = 0; rb < 2; ++rb)
+            if (2 * s + t < S::KSX) h1[x][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[s & 1][x][rb][t], t ? xl[s][0] : xh[s][0], h1[x][rb], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int x = 0; x < XB; ++x)
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb) {
+            const h8& av = A[s & 1][x][rb][t == 0 ? 1 : 0];            // lo . hi, then hi . lo, hi . hi
+            const h8& bv = t == 1 ? xl[s][0] : xh[s][0];
+            h1[x][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, h1[x][rb], 0, 0, 0);
+          }
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
@@ -324,6 +339,8 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
         for (int j = 0; j < 8; ++j) v[s][j] *= fac;
         split8(v[s], xh[s][0], xl[s][0]);
       }
+    } else if constexpr (S::STK) {      // (xh[s] / xl[s] = the B fragments of stacked k-steps 2 s / 2 s + 1)
+      xmax = gather_stacked<KIN, SGN, false, KS, S::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[0], kq, xh, xl, 0, xmax);
     } else {
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
