@@ -53,6 +53,7 @@ PRIOR_TENSOR_IDS = {"prior/loc": 100, "prior/log_scale": 101}
 PREC_F32, PREC_F16X3, PREC_F16X2 = 0, 1, 2
 OK, ERR, ERR_RANGE = 0, 1, 2                       # enum glowk_status
 RANGE_IGNORE, RANGE_ERROR, RANGE_FALLBACK = 0, 1, 2   # enum glowk_range_policy
+MIX_DB, MIX_MEAN = 0, 1                            # enum glowk_mixing
 
 _vp, _i, _fp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
 
@@ -105,6 +106,10 @@ SYMBOLS = {
     "glowk_basis_update": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, _vp, _vp,
                                 ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
     "glowk_basis_mix": (_i, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_basis_update_n": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_size_t, _i, ctypes.c_float, ctypes.c_float,
+                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
+    "glowk_basis_mix_n": (_i, [_vp, _i, _vp, ctypes.c_size_t, _i, _vp]),
+    "glowk_random_source": (_i, [_vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _i, _i, _i, ctypes.c_uint64, _vp]),
     "glowk_random": (_i, [_vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _i, _i, ctypes.c_uint64, _vp]),
     "glowk_add_noise": (_i, [_vp, _vp, ctypes.c_size_t, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _i, ctypes.c_uint64, _vp]),
     "glowk_mel_filterbank": (_i, [_fp]),

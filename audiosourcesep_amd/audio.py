@@ -15,6 +15,7 @@ Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) 
   ``GRIFFINLIM_STREAM`` of ``seed``), not from NumPy's global RNG, so librosa's own random start is not reproduced;
 * ``invert``: reuse the mixture's phase (or a single-channel Wiener filter over the sources) or Griffin-Lim, per tile
   (``method='frame'``) or on the tiles concatenated along time (``'whole'``);
+* ``separate_sources`` / ``separate_wav_sources``: ``separate_audio`` / ``separate_wav`` for a list of 2..16 priors;
 * ``resample`` / ``load_audio`` / ``save_audio`` / ``separate_wav``: PCM wavs of 8 to 32 bits at any rate in, 16-bit wavs at any
   rate out, around a band-limited sample-rate converter on the GPU (``csrc/glowk_resample.h``) -- what ``librosa.core.load(path,
   sr=16000)`` does for the reference (datasets/preprocessing.py:21).  The filter is the same design as librosa 0.7's default
@@ -440,3 +441,41 @@ def separate_wav(path, flow1, flow2, sigmas, out_rate="input", **kwargs):
     y1, y2, mixed, x1, x2 = separate_audio(y, flow1, flow2, sigmas, **kwargs)
     y1, y2 = resample(torch.stack([y1, y2]), SR, rate)
     return y1, y2, mixed, x1, x2, rate
+
+
+def separate_sources(mix, flows, sigmas, restores=None, T=100, delta=2e-5, seed=0, skip=0, n=None, wiener=False, top_db=80.0, iters=200,
+                     algorithm="reuse_phase", method="frame", n_iter=32, momentum=0.99, mixing="db"):
+    """``separate_audio`` for S = len(flows) priors, S in [2, 16]: front end, ``basis.basis_outer_loop_n`` from the uniform start
+    over [-100, 20] dB (source k: device RNG stream 14 + (k & 1) of source pair k >> 1, so the first two start where
+    ``separate_audio`` starts them), ``invert`` of the S tile batches.  ``restores``: as for ``basis_outer_loop_n``.  Returns
+    ``(ys, mixed, xs)``: the signals [S, N * 32256] ([S, (64 N - 1) * 512] for 'whole'), the mixture tiles [N, 96, 64, 1] and the
+    separated tiles [S, N, 96, 64, 1]."""
+    if algorithm not in ALGORITHMS:
+        raise ValueError("algorithm: expected one of %s, got %r" % (ALGORITHMS, algorithm))
+    _check_method(method)
+    if algorithm == "griffin":
+        _check_griffin(n_iter, momentum)
+    flows = list(flows)
+    if not 2 <= len(flows) <= basis.MAX_SOURCES:
+        raise ValueError("flows: expected 2..%d priors, got %d" % (basis.MAX_SOURCES, len(flows)))
+    y = read_wav(mix) if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__") else mix
+    mixed, X = mel_tiles(extracts(y, skip, n), top_db=top_db, return_stft=True)
+    xs = [-100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14 + (k & 1), uniform=True, pair=k >> 1)
+          for k in range(len(flows))]
+    xs, _ = basis.basis_outer_loop_n(mixed, xs, flows, sigmas, restores=restores, T=T, delta=delta, seed=seed, mixing=mixing)
+    out = invert(xs, X, wiener=wiener, iters=iters, algorithm=algorithm, method=method, n_iter=n_iter, momentum=momentum, seed=seed)
+    return out, mixed, torch.stack(xs)
+
+
+def separate_wav_sources(path, flows, sigmas, out_rate="input", **kwargs):
+    """``separate_wav`` for S priors: a PCM wav at any rate -> S separated signals at ``out_rate`` ('input', an integer rate, or
+    None for 16 kHz), all S resampled in one launch.  ``kwargs`` are ``separate_sources``' keyword arguments.  Returns
+    ``(ys [S, n'], mixed, xs, rate)``."""
+    if not (out_rate is None or (isinstance(out_rate, str) and out_rate == "input")):
+        if isinstance(out_rate, str):
+            raise ValueError("out_rate: expected 'input', None or an integer sampling rate, got %r" % (out_rate,))
+        out_rate = _check_rate(out_rate, "out_rate")
+    y, native = load_audio(path, sr=SR, mono=True)
+    rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
+    ys, mixed, xs = separate_sources(y, flows, sigmas, **kwargs)
+    return resample(ys, SR, rate), mixed, xs, rate

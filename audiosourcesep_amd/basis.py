@@ -1,4 +1,4 @@
-"""BASIS separation loop (annealed Langevin dynamics with two flow priors) on top of the glowk log_prob + gradient path.
+"""BASIS separation loop (annealed Langevin dynamics with flow priors) on top of the glowk log_prob + gradient path.
 
 Mirrors the glow branch of the reference's ``run_basis_sep.py``: ``get_sigmas`` (ncsn/utils.py:7-14), the dB mixing
 process ``g`` / ``grad_g`` (run_basis_sep.py:131-147), ``basis_inner_loop`` (:152-214) and ``basis_outer_loop`` (:217-260).
@@ -16,6 +16,14 @@ At the reference's 30 mixture tiles that alone cannot scale far (a step is a lat
 tile shard live on two ranks, each evaluates its own prior's gradient, ONE all-gather of the two gradient tensors per Langevin
 step (2 x 737 KB for 30 tiles of 96x64) makes both visible, and both ranks run the identical update kernel (same Philox counters:
 the replicated state stays bit-identical without a broadcast).
+
+Any number of sources: the ``*_n`` functions (``mixing`` / ``grad_mixing``, ``langevin_update_n``, ``basis_inner_loop_n``,
+``basis_outer_loop_n``, ``prior_parallel_layout_n`` / ``make_prior_group`` / ``exchange_prior_gradients_n``) take lists of S
+states, gradients and priors, S in [2, 16], and either mixing process of the reference (``"db"``: :131-147, ``"mean"``: :108-116;
+its power-scale branch is not offered).  The update is still one kernel (``glowk_basis_update_n``); source k draws the device RNG
+stream ``k & 1`` of source pair ``k >> 1``, so sources 0 and 1 see the two-source path's noise and no two sources share a draw.
+The S gradient evaluations go to at most four side streams, round-robin.  The two-source functions above them are kept as they
+were, on their own kernel.
 """
 import ctypes
 import math
@@ -58,12 +66,17 @@ def mixing_db(*sources):
     return (10.0 / math.log(10.0)) * (torch.logsumexp(s * (math.log(10.0) / 10.0), dim=0) - math.log(float(k)))
 
 
-def device_randn(shape, device, seed, step=0, which=0, uniform=False, offset=0):
+def device_randn(shape, device, seed, step=0, which=0, uniform=False, offset=0, pair=0):
     """Standard-normal (or U(0, 1)) tensor from the engine's Philox stream (seed, step, which): the draws
     ``glowk_basis_update`` makes itself when no noise is injected.  ``offset``: position of element 0 in the stream (a
     multiple of 4) -- a rank holding tiles [a, b) of a batch passes ``a * H * W * C`` and gets the draws one process would have
-    made for those tiles, so the noise a tile sees does not depend on how the batch is sharded."""
+    made for those tiles, so the noise a tile sees does not depend on how the batch is sharded.  ``pair``: the source pair of
+    the S-source update (``glowk_random_source``: source k draws ``which = k & 1``, ``pair = k >> 1``); 0 is the stream above."""
     out = torch.empty(shape, device=device, dtype=torch.float32)
+    if pair:
+        _lib.check(_lib.load().glowk_random_source(_p(out), out.numel(), int(seed), int(step), int(which), int(pair), int(bool(uniform)),
+                                                   int(offset), _s(out)))
+        return out
     _lib.check(_lib.load().glowk_random(_p(out), out.numel(), int(seed), int(step), int(which), int(bool(uniform)), int(offset), _s(out)))
     return out
 
@@ -286,3 +299,278 @@ def shard(tensor, world_size, rank):
     """This rank's contiguous slice of the ``n_mixed`` tiles (tiles are independent: no collective inside the loop)."""
     a, b = shard_bounds(tensor.shape[0], world_size, rank)
     return tensor[a:b]
+
+
+# ---- any number of sources (run_basis_sep.py:106-149: g(*sources), grad_g(*sources) for K = len(sources)) -------------------------
+MIXINGS = {"db": _lib.MIX_DB, "mean": _lib.MIX_MEAN}
+MAX_SOURCES = 16
+MAX_SIDE_STREAMS = 4
+
+
+def _mixing_id(process):
+    if process not in MIXINGS:
+        raise ValueError("mixing process: expected one of %s, got %r" % (tuple(MIXINGS), process))
+    return MIXINGS[process]
+
+
+def _ptrs(tensors):
+    """Host array of device pointers (None -> NULL) for the ``*_n`` entry points."""
+    arr = (ctypes.c_void_p * len(tensors))()
+    for k, t in enumerate(tensors):
+        arr[k] = t.data_ptr() if t is not None else None
+    return arr
+
+
+def mixing(sources, process="db"):
+    """``g(*sources)`` for S = len(sources): ``"db"`` sums in power (run_basis_sep.py:131-141), ``"mean"`` is the linear mean
+    (:108-111).  2..16 CUDA float32 tensors go through ``glowk_basis_mix_n``; anything else takes the torch formula."""
+    mid = _mixing_id(process)
+    sources = list(sources)
+    if not sources:
+        raise ValueError("mixing: expected at least one source")
+    if 2 <= len(sources) <= MAX_SOURCES and all(t.is_cuda and t.dtype == torch.float32 for t in sources):
+        if any(t.shape != sources[0].shape for t in sources):
+            raise ValueError("mixing: the sources must have one shape")
+        src = [t.contiguous() for t in sources]
+        out = torch.empty_like(src[0])
+        _lib.check(_lib.load().glowk_basis_mix_n(_ptrs(src), len(src), _p(out), out.numel(), mid, _s(out)))
+        return out
+    s = torch.stack(sources, dim=0)
+    if process == "mean":
+        return s.mean(dim=0)
+    return (10.0 / math.log(10.0)) * (torch.logsumexp(s * (math.log(10.0) / 10.0), dim=0) - math.log(float(len(sources))))
+
+
+def grad_mixing(sources, process="db"):
+    """``grad_g(*sources)`` -> list of S tensors: softmax over the sources of s ln10/10 (``"db"``, run_basis_sep.py:143-147) or
+    1/S (``"mean"``, :113-116).  Torch formulas: the update kernel computes these weights itself."""
+    _mixing_id(process)
+    s = torch.stack(list(sources), dim=0)
+    if process == "mean":
+        return list(torch.unbind(torch.full_like(s, 1.0 / s.shape[0]), dim=0))
+    return list(torch.unbind(torch.softmax(s * (math.log(10.0) / 10.0), dim=0), dim=0))
+
+
+def langevin_update_n(mixed, xs, gs, eta, lambda_recon, eps=None, seed=0, step=0, nonfinite=None, offset=0, mixing="db"):
+    """run_basis_sep.py:163-181 for S = len(xs) sources, IN PLACE on every xs[k] (contiguous float32 CUDA tensors, distinct
+    buffers): one kernel.  ``eps``: None, or a list of S entries, each a standard-normal tensor or None (that source draws from
+    the device RNG: stream ``k & 1`` of pair ``k >> 1`` at (seed, step), element ``offset`` onwards)."""
+    mid = _mixing_id(mixing)
+    S = len(xs)
+    if len(gs) != S or (eps is not None and len(eps) != S):
+        raise ValueError("langevin_update_n: %d states need %d gradients (and noise entries)" % (S, S))
+    for t in xs:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("langevin_update_n: the states are updated in place and must be contiguous float32 CUDA tensors")
+    n = xs[0].numel() if S else 0
+    ro = [mixed] + list(gs) + [e for e in (eps or []) if e is not None]
+    ro = [t.to(torch.float32).contiguous() for t in ro]
+    if any(t.numel() != n for t in list(xs) + ro):
+        raise ValueError("langevin_update_n: every tensor must hold as many elements as the states")
+    mixed_c, gs_c = ro[0], ro[1:1 + S]
+    eps_c, rest = None, iter(ro[1 + S:])
+    if eps is not None:
+        eps_c = [next(rest) if e is not None else None for e in eps]
+    _lib.check(_lib.load().glowk_basis_update_n(_ptrs(xs), _ptrs(gs_c), _ptrs(eps_c) if eps_c is not None else None, S, _p(mixed_c), n, mid,
+                                                float(eta), float(lambda_recon), int(seed), int(step), int(offset), _p(nonfinite),
+                                                _s(mixed_c)))
+
+
+def prior_parallel_layout_n(n_mixed, world_size, rank, n_sources):
+    """Prior-parallel BASIS for ``n_sources`` priors over ``world_size`` = n_sources * shards ranks: rank r holds prior
+    ``r % n_sources`` of tile shard ``r // n_sources``.  -> dict(prior, shard, n_shards, bounds=(a, b), group=(the ranks of this
+    shard, in prior order)).  ``make_prior_group`` creates the groups."""
+    if n_sources < 2 or n_sources > MAX_SOURCES:
+        raise ValueError("prior-parallel BASIS: the number of sources must be 2..%d, got %d" % (MAX_SOURCES, n_sources))
+    if world_size < n_sources or world_size % n_sources:
+        raise ValueError("prior-parallel BASIS with %d priors needs a multiple of %d ranks, got %d" % (n_sources, n_sources, world_size))
+    if not 0 <= rank < world_size:
+        raise ValueError("rank %d is outside the world of %d" % (rank, world_size))
+    shards = world_size // n_sources
+    s = rank // n_sources
+    return {"prior": rank % n_sources, "shard": s, "n_shards": shards, "bounds": shard_bounds(n_mixed, shards, s),
+            "group": tuple(range(n_sources * s, n_sources * (s + 1)))}
+
+
+def make_prior_group(world_size, rank, n_sources):
+    """The process group of this rank's tile shard (its ``n_sources`` priors).  Collective over the whole job: every rank creates
+    every group, in the same order, and keeps its own."""
+    import torch.distributed as dist
+    if world_size < n_sources or world_size % n_sources:
+        raise ValueError("prior-parallel BASIS with %d priors needs a multiple of %d ranks, got %d" % (n_sources, n_sources, world_size))
+    mine = None
+    for s in range(world_size // n_sources):
+        g = dist.new_group(list(range(n_sources * s, n_sources * (s + 1))))
+        if rank // n_sources == s:
+            mine = g
+    return mine
+
+
+def exchange_prior_gradients_n(g_mine, prior_index, group):
+    """-> list of the S priors' gradients: ONE all-gather over the shard's group (rank order within the group = prior order).
+    RCCL when the backend is nccl; under gloo device tensors go through the host, as in ``exchange_prior_gradients``."""
+    import torch.distributed as dist
+    S = dist.get_world_size(group)
+    g_mine = g_mine.contiguous()
+    if g_mine.is_cuda and dist.get_backend(group) == "gloo":
+        mine = g_mine.cpu()
+        parts = [torch.empty_like(mine) for _ in range(S)]
+        dist.all_gather(parts, mine, group=group)
+        parts = [p.to(g_mine.device) for p in parts]
+    else:
+        parts = [torch.empty_like(g_mine) for _ in range(S)]
+        dist.all_gather(parts, g_mine, group=group)
+    parts[prior_index] = g_mine
+    return parts
+
+
+def _grad_n(xs, models, streams):
+    """``_grad_pair`` for S priors: the gradient chains are independent, so they are enqueued on the given side streams, source k
+    on the stream of its model -- distinct models take the streams round-robin, a model that serves several sources runs them one
+    after the other on one stream (an engine is not re-entrant).  Range guard as in ``_grad_pair``: "ignore" while enqueuing, the
+    flags read afterwards, "fallback" re-runs that one model's gradients on the exact kernels, "error" raises."""
+    if not streams or xs[0].device.type != "cuda":
+        return [compute_grad_logprob(x, m) for x, m in zip(xs, models)]
+    cur = torch.cuda.current_stream(xs[0].device)
+    engines, of_engine = [], {}
+    for m in models:
+        if id(m.engine) not in of_engine:
+            of_engine[id(m.engine)] = len(engines)
+            engines.append(m.engine)
+    stream_of = [streams[of_engine[id(m.engine)] % len(streams)] for m in models]
+    used = list({id(st): st for st in stream_of}.values())
+    for st in used:
+        st.wait_stream(cur)
+    guarded = [e.get_precision() != _lib.PREC_F32 for e in engines]
+    saved = [int(e.lib.glowk_get_range_policy(e.h)) for e in engines]
+    for e, gd in zip(engines, guarded):
+        if gd:
+            e.set_range_policy("ignore")
+    try:
+        out = []
+        for x, m, st in zip(xs, models, stream_of):
+            with torch.cuda.stream(st):
+                out.append(compute_grad_logprob(x, m))
+        for i, e in enumerate(engines):
+            if not guarded[i] or saved[i] == _lib.RANGE_IGNORE:
+                continue
+            mine = [k for k, m in enumerate(models) if m.engine is e]
+            with torch.cuda.stream(stream_of[mine[0]]):
+                if e.range_status()[0]:       # the flag is sticky: one look covers every source this engine served
+                    if saved[i] == _lib.RANGE_ERROR:
+                        raise _lib.GlowkRangeError("BASIS: a prior's gradient left the fp16 range of the split arithmetic")
+                    prec = e.get_precision()
+                    e.set_precision(_lib.PREC_F32)
+                    for k in mine:
+                        out[k] = compute_grad_logprob(xs[k], models[k])
+                    e.set_precision(prec)
+    finally:
+        for e, gd, pol in zip(engines, guarded, saved):
+            if gd:
+                e.set_range_policy(pol)
+    for st in used:
+        cur.wait_stream(st)
+    for g in out:
+        g.record_stream(cur)
+    return out
+
+
+def basis_inner_loop_n(mixed, xs, models, sigma_idx, sigmas, delta=2e-5, T=100, noise_fn=None, debug=False, streams="auto", seed=0,
+                       step0=0, offset=0, prior_group=None, prior_index=None, mixing="db"):
+    """``basis_inner_loop`` for S = len(xs) sources -> list of S tensors.  ``noise_fn(t, k, shape)`` supplies source k's standard
+    normal draws of step t; without it the update kernel draws (seed, step0 + t), source k from stream ``k & 1`` of pair
+    ``k >> 1``.  ``streams``: "auto" (on the GPU, one side stream per distinct engine, at most four), None, or a sequence of
+    streams.  ``prior_group`` / ``prior_index``: prior-parallel mode -- this rank evaluates prior ``prior_index`` only (the other
+    models may be None), the group all-gathers the S gradients and every rank takes the same update."""
+    _mixing_id(mixing)
+    xs, models = list(xs), list(models)
+    S = len(xs)
+    if S < 2 or S > MAX_SOURCES:
+        raise ValueError("BASIS: the number of sources must be 2..%d, got %d" % (MAX_SOURCES, S))
+    if len(models) != S:
+        raise ValueError("BASIS: %d states need %d priors, got %d" % (S, S, len(models)))
+    pp = prior_group is not None
+    if pp and (not isinstance(prior_index, int) or not 0 <= prior_index < S):
+        raise ValueError("prior_index must be 0..%d in prior-parallel mode" % (S - 1))
+    on_gpu = xs[0].device.type == "cuda"
+    if pp:
+        streams = None
+    if isinstance(streams, str) and streams == "auto":
+        streams = None
+        distinct = len({id(getattr(m, "engine", m)) for m in models})
+        if on_gpu and distinct > 1:
+            streams = [torch.cuda.Stream(device=xs[0].device) for _ in range(min(distinct, MAX_SIDE_STREAMS))]
+    sigma = float(sigmas[sigma_idx])
+    sigma_l = float(sigmas[-1])
+    eta = float(np.float32(delta * (sigma / sigma_l) ** 2))
+    lambda_recon = 1.0 / (sigma ** 2)
+
+    def grads(cur):
+        if not pp:
+            return _grad_n(cur, models, streams)
+        return exchange_prior_gradients_n(compute_grad_logprob(cur[prior_index], models[prior_index]), prior_index, prior_group)
+
+    if not on_gpu:
+        return _inner_loop_host_n(mixed, xs, grads, eta, lambda_recon, T, noise_fn, debug, mixing)
+    mixed = mixed.to(torch.float32).contiguous()
+    xs = [x.to(torch.float32).clone().contiguous() for x in xs]   # (the update is in place)
+    flag = torch.zeros(1, dtype=torch.int32, device=xs[0].device) if debug else None
+    for t in range(T):
+        gs = grads(xs)
+        eps = [noise_fn(t, k, xs[k].shape) for k in range(S)] if noise_fn is not None else None
+        langevin_update_n(mixed, xs, gs, eta, lambda_recon, eps, seed=seed, step=step0 + t, nonfinite=flag, offset=offset, mixing=mixing)
+        if debug:
+            assert int(flag.item()) == 0, (sigma, t)   # run_basis_sep.py:183-191
+    return xs
+
+
+def _inner_loop_host_n(mixed, xs, grads, eta, lambda_recon, T, noise_fn, debug, process):
+    """The same loop on torch formulas (CPU tensors).  ``grads(xs) -> list of S gradients``."""
+    if noise_fn is None:
+        noise_fn = lambda t, k, shape: torch.randn(shape, dtype=torch.float32)  # noqa: E731
+    for t in range(T):
+        eps = [math.sqrt(2.0 * eta) * noise_fn(t, k, x.shape) for k, x in enumerate(xs)]
+        gs = grads(xs)
+        mix = mixing(xs, process)
+        ms = grad_mixing(xs, process)
+        xs = [x + eta * (g + lambda_recon * m * (mixed - mix)) + e for x, g, m, e in zip(xs, gs, ms, eps)]
+        if debug:
+            assert all(torch.isfinite(x).all() for x in xs), t
+    return xs
+
+
+def basis_outer_loop_n(mixed, xs, models, sigmas, restores=None, T=100, delta=2e-5, noise_fn=None, debug=False, seed=0, tile_offset=0,
+                       prior_group=None, prior_index=None, mixing="db"):
+    """``basis_outer_loop`` for S sources.  ``restores``: None, or a list of S entries, each None or ``{sigma: state_dict | path |
+    GlowFlow}`` for that prior (handled as ``restore_k`` there).  ``noise_fn(sigma_idx, t, k, shape)``.  Returns ``(xs, x_arr)``:
+    the list of S final states and the trajectory ``{"x1": [...], .., "xS": [...]}`` (start state and one entry per level).  In
+    prior-parallel mode only the own prior's model and restore map are used; the others may be None."""
+    xs, models = list(xs), list(models)
+    S = len(xs)
+    if len(models) != S or (restores is not None and len(restores) != S):
+        raise ValueError("BASIS: %d states need %d priors (and restore maps)" % (S, S))
+    restores = [None] * S if restores is None else list(restores)
+    elems_per_tile = int(np.prod(mixed.shape[1:]))
+    x_arr = {"x%d" % (k + 1): [x.cpu().numpy()] for k, x in enumerate(xs)}
+    for sigma_idx, sigma in enumerate(sigmas):
+        current = []
+        for k, (model, restore) in enumerate(zip(models, restores)):
+            if prior_group is not None and k != prior_index:
+                current.append(None)          # another rank of the group owns this prior
+                continue
+            if restore is not None:
+                state = restore[float(sigma)] if float(sigma) in restore else restore[sigma]
+                if hasattr(state, "log_prob"):
+                    model = state
+                elif isinstance(state, str):
+                    model.restore(state)
+                else:
+                    model.load_state_dict(state)
+            current.append(model)
+        nf = None if noise_fn is None else (lambda t, k, shape, _s=sigma_idx: noise_fn(_s, t, k, shape))
+        xs = basis_inner_loop_n(mixed, xs, current, sigma_idx, sigmas, delta=delta, T=T, noise_fn=nf, debug=debug, seed=seed,
+                                step0=sigma_idx * T, offset=int(tile_offset) * elems_per_tile, prior_group=prior_group,
+                                prior_index=prior_index, mixing=mixing)
+        for k, x in enumerate(xs):
+            x_arr["x%d" % (k + 1)].append(x.cpu().numpy())
+    return xs, x_arr

@@ -50,8 +50,93 @@ int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int whi
   DeviceGuard dg(ptr_device(out_dev));
   const size_t threads = (n + 3) / 4;
   hipLaunchKernelGGL(k_basis_noise, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out_dev, n, seed, step,
-                     (uint32_t)which, uniform, offset / 4);
+                     (uint32_t)which, uniform, offset / 4, 0u);
   LAUNCHCHK("k_basis_noise");
+  return 0;
+}
+
+int glowk_random_source(float* out_dev, size_t n, uint64_t seed, uint64_t step, int which, int pair, int uniform, uint64_t offset,
+                        void* stream) {
+  if (!out_dev) return fail("null tensor");
+  if (which < 0 || which > 15) return fail("random_source: stream id must be 0..15");
+  if (pair < 0 || pair > 65535) return fail("random_source: the source pair must be 0..65535");
+  if (pair && step >= ((uint64_t)1 << 48)) return fail("random_source: step must be below 2^48 (a source pair shares its counter word)");
+  if (offset % 4) return fail("random_source: the stream offset must be a multiple of 4 elements");
+  if (n == 0) return 0;
+  DeviceGuard dg(ptr_device(out_dev));
+  const size_t threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_basis_noise, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out_dev, n, seed, step,
+                     (uint32_t)which, uniform, offset / 4, (uint32_t)pair);
+  LAUNCHCHK("k_basis_noise");
+  return 0;
+}
+
+namespace glowk_eng {
+// [a, a + n) and [b, b + n) floats share an element
+static bool basis_overlap(const float* a, const float* b, size_t n) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return (p > q ? p - q : q - p) < n * sizeof(float);
+}
+
+#define GLOWK_BASIS_EACH_S(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+}  // namespace glowk_eng
+
+int glowk_basis_update_n(float* const* x, const float* const* g, const float* const* eps, int nsrc, const float* mixed_dev, size_t n,
+                         int mixing, float eta, float lambda_recon, uint64_t seed, uint64_t step, uint64_t offset,
+                         int* nonfinite_dev, void* stream) {
+  if (nsrc < 2 || nsrc > GLOWK_BASIS_MAX_SOURCES) return fail("basis_update_n: the number of sources must be 2..16");
+  if (mixing != GLOWK_MIX_DB && mixing != GLOWK_MIX_MEAN) return fail("basis_update_n: unknown mixing process");
+  if (!x || !g || !mixed_dev) return fail("null tensor");
+  for (int k = 0; k < nsrc; ++k)
+    if (!x[k] || !g[k]) return fail("null tensor");
+  if (offset % 4) return fail("basis_update_n: the stream offset must be a multiple of 4 elements");
+  if (step >= ((uint64_t)1 << 48)) return fail("basis_update_n: step must be below 2^48 (the source pair shares its counter word)");
+  if (n > ((size_t)1 << 40)) return fail("basis_update_n: too many elements");
+  if (!(eta >= 0.0f)) return fail("basis_update_n: eta must be non-negative");
+  for (int k = 0; k < nsrc; ++k) {
+    if (basis_overlap(x[k], mixed_dev, n ? n : 1)) return fail("basis_update_n: a source state aliases the mixture");
+    for (int l = 0; l < k; ++l)
+      if (basis_overlap(x[k], x[l], n ? n : 1)) return fail("basis_update_n: the source states must be distinct buffers");
+  }
+  if (n == 0) return 0;
+  DeviceGuard dg(ptr_device(x[0]));
+  BasisNArgs a = {};
+  uintptr_t bits = (uintptr_t)mixed_dev;
+  for (int k = 0; k < nsrc; ++k) {
+    a.x[k] = x[k]; a.g[k] = g[k]; a.eps[k] = eps ? eps[k] : nullptr;
+    bits |= (uintptr_t)a.x[k] | (uintptr_t)a.g[k] | (uintptr_t)a.eps[k];
+  }
+  a.mixed = mixed_dev; a.n = n; a.eta = eta; a.lambda_recon = lambda_recon; a.noise_scale = std::sqrt(2.0f * eta);
+  a.ln_s = (float)std::log((double)nsrc); a.inv_s = 1.0f / (float)nsrc; a.mixing = mixing; a.vec = (bits & 15) == 0;
+  a.seed = seed; a.step = step; a.q0 = offset / 4; a.nonfinite = nonfinite_dev;
+  const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
+  switch (nsrc) {
+#define GLOWK_CASE(s) case s: hipLaunchKernelGGL(k_basis_update_n<s>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
+    GLOWK_BASIS_EACH_S(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_basis_update_n");
+  return 0;
+}
+
+int glowk_basis_mix_n(const float* const* x, int nsrc, float* out_dev, size_t n, int mixing, void* stream) {
+  if (nsrc < 2 || nsrc > GLOWK_BASIS_MAX_SOURCES) return fail("basis_mix_n: the number of sources must be 2..16");
+  if (mixing != GLOWK_MIX_DB && mixing != GLOWK_MIX_MEAN) return fail("basis_mix_n: unknown mixing process");
+  if (!x || !out_dev) return fail("null tensor");
+  for (int k = 0; k < nsrc; ++k)
+    if (!x[k]) return fail("null tensor");
+  if (n == 0) return 0;
+  DeviceGuard dg(ptr_device(out_dev));
+  BasisMixNArgs a = {};
+  for (int k = 0; k < nsrc; ++k) a.x[k] = x[k];
+  a.out = out_dev; a.n = n; a.ln_s = (float)std::log((double)nsrc); a.inv_s = 1.0f / (float)nsrc; a.mixing = mixing;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  switch (nsrc) {
+#define GLOWK_CASE(s) case s: hipLaunchKernelGGL(k_basis_mix_n<s>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
+    GLOWK_BASIS_EACH_S(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_basis_mix_n");
   return 0;
 }
 

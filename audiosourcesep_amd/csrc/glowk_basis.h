@@ -1,6 +1,7 @@
 // glowk device code, part 3: the BASIS Langevin update (run_basis_sep.py:131-181, dB branch, two sources) as ONE elementwise
 // kernel with its own counter-based RNG.  HBM-bound and tiny next to the two log_prob_grad calls of a step; what matters at
 // the reference's 30 tiles is that it is one launch instead of the dozen elementwise/reduction launches of a tensor library.
+// k_basis_update is the two-source dB update; k_basis_update_n<S> further down takes 2..16 sources and either mixing process.
 //
 //   eps_k  = sqrt(2 eta) N(0, I)                                                 :163-164
 //   mix    = 10/ln10 (logsumexp_k(x_k ln10/10) - ln 2)                            :133-141  (g, sum in power)
@@ -27,9 +28,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
   }
 }
 
-// four standard normals for elements 4 q .. 4 q + 3 of (seed, step, which): two Box-Muller pairs
-__device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t which, uint64_t q, float (&z)[4]) {
-  uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32) ^ (which << 28), (uint32_t)step, (uint32_t)(step >> 32)};
+// four standard normals for elements 4 q .. 4 q + 3 of (seed, step, which, pair): two Box-Muller pairs.  `pair` (the S-source
+// update: source k draws which = k & 1, pair = k >> 1) goes into bits 16.. of the word that holds step >> 32, which is zero for
+// every step < 2^32 and below bit 16 for step < 2^48; pair = 0 is the two-source stream.
+__device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t which, uint64_t q, float (&z)[4], uint32_t pair = 0u) {
+  uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32) ^ (which << 28), (uint32_t)step, (uint32_t)(step >> 32) ^ (pair << 16)};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
@@ -92,6 +95,149 @@ __global__ __launch_bounds__(256) void k_basis_update(BasisArgs a) {
   if (bad && a.nonfinite) *a.nonfinite = 1;
 }
 
+// ---- any number of sources (run_basis_sep.py:106-149: g(*sources), grad_g(*sources) for K = len(sources)) ---------------------
+//   GLOWK_MIX_DB   (:131-147)  mix = 10/ln10 (logsumexp_k(x_k ln10/10) - ln S),  m_k = softmax_k(x_k ln10/10)
+//   GLOWK_MIX_MEAN (:108-116)  mix = mean_k x_k,                                 m_k = 1/S
+//   x_k <- x_k + eta (g_k + lambda m_k (mixed - mix)) + sqrt(2 eta) z_k          for k = 0..S-1
+// The pointers travel by value in the kernel arguments.  S is a template parameter so that a thread's 4 S state values stay in
+// registers between the reduction over the sources and the update: every x_k, g_k and mixed element is read from HBM once and
+// every x_k written once, (3 S + 1) * 4 bytes per element.
+#define GLOWK_BASIS_MAX_SOURCES 16
+
+struct BasisNArgs {
+  float* x[GLOWK_BASIS_MAX_SOURCES];           // [n] each, in place
+  const float* g[GLOWK_BASIS_MAX_SOURCES];     // [n] grad log p_k(x_k)
+  const float* eps[GLOWK_BASIS_MAX_SOURCES];   // optional [n] standard-normal draws of source k; null: device RNG (k & 1, pair k >> 1)
+  const float* mixed;   // [n]
+  size_t n;
+  float eta, lambda_recon, noise_scale;        // noise_scale = sqrt(2 eta)
+  float ln_s, inv_s;    // ln S, 1 / S
+  int mixing;           // enum glowk_mixing
+  int vec;              // every pointer is 16-byte aligned: whole quads move as float4
+  uint64_t seed, step, q0;
+  int* nonfinite;
+};
+
+// mix and the weights m_k of one element from its S source values; v[k] holds x_k on entry and m_k on return
+template <int S>
+__device__ __forceinline__ float basis_mix_terms(float (&v)[S], int mixing, float ln_s, float inv_s) {
+  const float L10 = 0.23025850929940457f;   // ln 10 / 10
+  if (mixing == 1) {                        // GLOWK_MIX_MEAN
+    float sum = v[0];
+#pragma unroll
+    for (int k = 1; k < S; ++k) sum += v[k];
+#pragma unroll
+    for (int k = 0; k < S; ++k) v[k] = inv_s;
+    return sum * inv_s;
+  }
+  float mx = v[0] * L10;
+#pragma unroll
+  for (int k = 1; k < S; ++k) mx = fmaxf(mx, v[k] * L10);
+  float den = 0.0f;
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    v[k] = expf(v[k] * L10 - mx);
+    den += v[k];
+  }
+#pragma unroll
+  for (int k = 0; k < S; ++k) v[k] = v[k] / den;
+  return (1.0f / L10) * (mx + logf(den) - ln_s);
+}
+
+// one thread = four consecutive elements of every source (one Philox call per source)
+template <int S>
+__global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
+  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t e0 = (size_t)q * 4;
+  if (e0 >= a.n) return;
+  const bool quad = a.vec && e0 + 4 <= a.n;   // the tail quad and unaligned pointers move element by element
+  float x[S][4], mixed[4];
+  if (quad) {
+    const float4 t = *reinterpret_cast<const float4*>(a.mixed + e0);
+    mixed[0] = t.x; mixed[1] = t.y; mixed[2] = t.z; mixed[3] = t.w;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+      const float4 u = *reinterpret_cast<const float4*>(a.x[k] + e0);
+      x[k][0] = u.x; x[k][1] = u.y; x[k][2] = u.z; x[k][3] = u.w;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool in = e0 + j < a.n;           // lanes past n compute on zeros and are never stored
+      mixed[j] = in ? a.mixed[e0 + j] : 0.0f;
+#pragma unroll
+      for (int k = 0; k < S; ++k) x[k][j] = in ? a.x[k][e0 + j] : 0.0f;
+    }
+  }
+  float m[S][4], r[4];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float v[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) v[k] = x[k][j];
+    const float mix = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s);
+#pragma unroll
+    for (int k = 0; k < S; ++k) m[k][j] = v[k];
+    r[j] = a.lambda_recon * (mixed[j] - mix);
+    bad |= basis_bad(mix);
+  }
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    float g[4], z[4];
+    const float* eps = a.eps[k];
+    if (quad) {
+      const float4 t = *reinterpret_cast<const float4*>(a.g[k] + e0);
+      g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = e0 + j < a.n ? a.g[k][e0 + j] : 0.0f;
+    }
+    if (!eps) {
+      normal4(a.seed, a.step, (uint32_t)(k & 1), a.q0 + q, z, (uint32_t)(k >> 1));
+    } else if (quad) {
+      const float4 t = *reinterpret_cast<const float4*>(eps + e0);
+      z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) z[j] = e0 + j < a.n ? eps[e0 + j] : 0.0f;
+    }
+    float y[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      y[j] = x[k][j] + a.eta * (g[j] + m[k][j] * r[j]) + a.noise_scale * z[j];
+      bad |= basis_bad(g[j]) | basis_bad(y[j]);
+    }
+    if (quad) {
+      *reinterpret_cast<float4*>(a.x[k] + e0) = make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < a.n) a.x[k][e0 + j] = y[j];
+    }
+  }
+  if (bad && a.nonfinite) *a.nonfinite = 1;
+}
+
+struct BasisMixNArgs {
+  const float* x[GLOWK_BASIS_MAX_SOURCES];
+  float* out;
+  size_t n;
+  float ln_s, inv_s;
+  int mixing;
+};
+
+// g(x_0 .. x_{S-1}) alone
+template <int S>
+__global__ __launch_bounds__(256) void k_basis_mix_n(BasisMixNArgs a) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.n) return;
+  float v[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) v[k] = a.x[k][e];
+  a.out[e] = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s);
+}
+
 // g(x1, x2) alone (the mixture of two sources in dB, sum in power)
 __global__ __launch_bounds__(256) void k_basis_mix(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ out, size_t n) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -105,19 +251,19 @@ __global__ __launch_bounds__(256) void k_basis_mix(const float* __restrict__ x1,
 // the standard-normal draws k_basis_update makes for (seed, step, which); also the engine's general device RNG
 // (uniform = 1: U(0, 1) instead -- the reference starts the chain from uniform noise, run_basis_sep.py:360-361)
 __global__ __launch_bounds__(256) void k_basis_noise(float* __restrict__ out, size_t n, uint64_t seed, uint64_t step, uint32_t which, int uniform,
-                                                    uint64_t q0) {
+                                                    uint64_t q0, uint32_t pair) {
   const uint64_t ql = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const size_t e0 = (size_t)ql * 4;
   if (e0 >= n) return;
   const uint64_t q = q0 + ql;     // position in the logical stream: a shard draws what the whole batch would have drawn for its elements
   float z[4];
   if (uniform) {
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32) ^ (which << 28), (uint32_t)step, (uint32_t)(step >> 32)};
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32) ^ (which << 28), (uint32_t)step, (uint32_t)(step >> 32) ^ (pair << 16)};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = ((float)(c[j] >> 8) + 0.5f) * (1.0f / 16777216.0f);
   } else {
-    normal4(seed, step, which, q, z);
+    normal4(seed, step, which, q, z, pair);
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 460
+#define GLOWK_VERSION 470
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -268,7 +268,9 @@ int glowk_param_grad(glowk_handle* h, const float* x_dev, int N, float scale, fl
  * glowk_get_tensor / flow.variables see the new values. */
 int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer, float lr, void* stream);
 
-/* --- BASIS: the annealed-Langevin update around two log_prob_grad calls (run_basis_sep.py:152-181, dB branch) ------------- */
+/* --- BASIS: the annealed-Langevin update around the log_prob_grad calls of a step (run_basis_sep.py:152-181) --------------- */
+/* Two entry points: glowk_basis_update is the two-source dB update the package started with and keeps bit for bit;
+ * glowk_basis_update_n (further down) takes 2..16 sources and either mixing process of the reference (:106-149). */
 /* One step of basis_inner_loop for two sources, in place, as ONE kernel:
  *     mix = g(x1, x2) (:133-141),  (m1, m2) = grad_g(x1, x2) (:143-147),
  *     x_k <- x_k + eta (g_k + lambda_recon m_k (mixed - mix)) + sqrt(2 eta) N(0, I)        (:163-164, :180-181)
@@ -284,10 +286,36 @@ int glowk_basis_update(float* x1_dev, float* x2_dev, const float* g1_dev, const 
                        uint64_t offset, int* nonfinite_dev, void* stream);
 /* g(x1, x2) alone: the mixture of two sources in dB, sum in power (:133-141) */
 int glowk_basis_mix(const float* x1_dev, const float* x2_dev, float* out_dev, size_t n, void* stream);
+/* The mixing processes g(*sources) / grad_g(*sources) of run_basis_sep.py for S = len(sources).  (Its scale == 'power' branch is
+ * not offered: its grad_g is not the derivative of its g, and nothing here lives in power scale.) */
+enum glowk_mixing {
+  GLOWK_MIX_DB = 0,   /* :131-147  g = 10/ln10 (logsumexp_k(x_k ln10/10) - ln S),  grad_g = softmax_k(x_k ln10/10) */
+  GLOWK_MIX_MEAN = 1  /* :108-116  g = mean_k x_k,                                 grad_g = 1/S */
+};
+/* One step of basis_inner_loop for nsrc sources, in place, as ONE kernel (since version 470):
+ *     mix = g(x_0 .. x_{S-1}),  (m_k) = grad_g(x_0 .. x_{S-1}),
+ *     x_k <- x_k + eta (g_k + lambda_recon m_k (mixed - mix)) + sqrt(2 eta) N(0, I)         for k = 0 .. S-1
+ * x, g, eps: HOST arrays of nsrc DEVICE pointers, each to n floats (the pointers travel in the kernel arguments; the arrays are
+ * not read after the call returns).  eps may be NULL, and so may any entry of it: that source draws from the device RNG, stream
+ * `which` = k & 1 with source pair k >> 1 (glowk_random_source), so sources 0 and 1 draw what glowk_basis_update draws and no two
+ * sources share a draw.  nsrc in [2, 16]; the x buffers must not overlap each other or `mixed`; `offset` a multiple of 4, as
+ * for glowk_basis_update; step < 2^48 (the pair shares the counter word of step >> 32); mixing: enum glowk_mixing.  A thread
+ * moves four consecutive elements of every source as 16-byte accesses when every pointer is 16-byte aligned; the last partial
+ * quad and unaligned pointers go element by element.  GLOWK_ERR on any violated condition, before anything is launched. */
+int glowk_basis_update_n(float* const* x, const float* const* g, const float* const* eps, int nsrc, const float* mixed_dev, size_t n,
+                         int mixing, float eta, float lambda_recon, uint64_t seed, uint64_t step, uint64_t offset,
+                         int* nonfinite_dev, void* stream);
+/* g(x_0 .. x_{nsrc-1}) alone; x as above, nsrc in [2, 16] */
+int glowk_basis_mix_n(const float* const* x, int nsrc, float* out_dev, size_t n, int mixing, void* stream);
 /* the device RNG itself: out[e] = the draw glowk_basis_update makes for element e of (seed, step, which); uniform != 0 gives
  * U(0, 1) from the same stream instead of N(0, 1) (the chain's initial state, run_basis_sep.py:360-361); `offset` (a multiple
  * of 4): out[0] is element `offset` of the stream, as for glowk_basis_update */
 int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int which, int uniform, uint64_t offset, void* stream);
+/* the draw source k of glowk_basis_update_n makes: glowk_random with the source pair k >> 1 folded into the counter (XORed as
+ * pair << 16 into the word that holds step >> 32) and which = k & 1; pair = 0 is glowk_random itself.  pair in [0, 65535]; a
+ * non-zero pair needs step < 2^48. */
+int glowk_random_source(float* out_dev, size_t n, uint64_t seed, uint64_t step, int which, int pair, int uniform, uint64_t offset,
+                        void* stream);
 /* out = x + sigma * N(0, I), the draws being those of glowk_random(seed, step, which, offset): the input noise of the
  * noise-conditioned training step (train_noisy_glow.py:31, X + tf.random.normal(X.shape) * noise).  out_dev may equal x_dev. */
 int glowk_add_noise(const float* x_dev, float* out_dev, size_t n, float sigma, uint64_t seed, uint64_t step, int which, uint64_t offset,
