@@ -128,6 +128,7 @@ SYMBOLS = {
     "glowk_oracle_mask": (_i, [_vp, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp]),
     "glowk_mwf": (_i, [_vp, _i, _i, _vp]),
     "glowk_oracle_mel": (_i, [_vp, _vp, _i, ctypes.c_int64, _i, _i, ctypes.c_double, _vp, _vp]),
+    "glowk_mwf_em": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

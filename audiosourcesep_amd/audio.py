@@ -21,8 +21,11 @@ Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) 
   sr=16000)`` does for the reference (datasets/preprocessing.py:21).  The filter is the same design as librosa 0.7's default
   (resampy's ``kaiser_best``), evaluated at the exact position of every tap; it is not bit-compatible with resampy, whose samples
   cannot be observed here (derived, not observed).  ``read_wav`` / ``write_wav`` / ``separate_audio`` keep to 16 kHz.
+* ``multichannel_wiener`` / ``istft`` / ``separate_stereo`` / ``separate_wav_stereo``: stereo in, stereo stems out.  The priors
+  stay mono (they see the downmix); the stems come from a multichannel Wiener filter under the local Gaussian model whose
+  spatial covariances are fitted by EM from the priors' PSDs (Duong, Vincent, Gribonval 2010; ``csrc/glowk_stereo.h``, one launch).
 
-Not covered: IEEE-float and WAVE_FORMAT_EXTENSIBLE wavs, the power-scale flows (``scale='power'``) and stereo separation.
+Not covered: IEEE-float and WAVE_FORMAT_EXTENSIBLE wavs and the power-scale flows (``scale='power'``).
 """
 import ctypes
 import math
@@ -43,6 +46,7 @@ NMEL = MEL_FRONTEND["n_mels"]
 EXTRACT = int(SR * MEL_FRONTEND["length_sec"])          # 32 640 samples (datasets/preprocessing.py:9-26)
 GRIFFINLIM_STREAM = 13      # device RNG stream of init='random' (stream ids are 0..15; 0-3 serve the flows, 14 / 15 separate_audio)
 GRIFFINLIM_MAX_FRAMES = 1 << 20                          # glowk_griffinlim's cap: 9.3 h of 16 kHz audio in one signal
+MWF_EM_MAX_ITER = 1000                                   # glowk_mwf_em's cap on its EM iterations
 MIN_RATE, MAX_RATE = 1000, 768000                        # glowk_resample's sampling rates, at most a factor 64 apart
 ALGORITHMS = ("reuse_phase", "griffin")
 METHODS = ("frame", "whole")
@@ -478,4 +482,120 @@ def separate_wav_sources(path, flows, sigmas, out_rate="input", **kwargs):
     y, native = load_audio(path, sr=SR, mono=True)
     rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
     ys, mixed, xs = separate_sources(y, flows, sigmas, **kwargs)
+    return resample(ys, SR, rate), mixed, xs, rate
+
+
+# ---- stereo: multichannel Wiener filter with EM-fitted spatial covariances ----------------------------------------------------------
+def _check_em_iter(n_iter, what="n_iter"):
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= n_iter <= MWF_EM_MAX_ITER:
+        raise ValueError("%s: expected an integer in [0, %d], got %r" % (what, MWF_EM_MAX_ITER, n_iter))
+
+
+def multichannel_wiener(powers, stft_mixture, n_iter=2, return_model=False):
+    """Source PSDs [S, N, 1025, F] (>= 0) + stereo mixture STFTs [N, 2, 1025, F] (complex) -> the sources' stereo STFTs
+    [S, N, 2, 1025, F] (complex64): the multichannel Wiener filter Y_j = v_j R_j (sum_k v_k R_k + eps I)^-1 x under the local
+    Gaussian model, after ``n_iter`` EM iterations on the PSDs v_j(f, t) and the 2 x 2 spatial covariances R_j(f) from R_j = I
+    (``glowk_mwf_em``: one launch, one model per problem n, fp64 arithmetic, bitwise reproducible; formulas in include/glowk.h).
+    ``n_iter`` = 0 is the single-channel Wiener mask v_j / (sum_k v_k + 1e-10) on each channel.  S in [1, 16], F in [1, 2^20].
+    With ``return_model`` also the fitted v [S, N, 1025, F] (float32) and R [S, N, 1025, 2, 2] (complex128).  ``powers`` is not
+    modified."""
+    p, X = _tensor(powers, "powers"), _tensor(stft_mixture, "stft_mixture")
+    if p.dim() != 4 or p.shape[2] != NBIN or not 1 <= p.shape[0] <= basis.MAX_SOURCES or not 1 <= p.shape[3] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("powers: expected [S, N, 1025, F] with 1 <= S <= %d and 1 <= F <= %d, got %s"
+                         % (basis.MAX_SOURCES, GRIFFINLIM_MAX_FRAMES, tuple(p.shape)))
+    if tuple(X.shape) != (p.shape[1], 2, NBIN, p.shape[3]):
+        raise ValueError("stft_mixture: expected [N, 2, 1025, F] = %s to match the powers, got %s"
+                         % ((p.shape[1], 2, NBIN, p.shape[3]), tuple(X.shape)))
+    if p.shape[1] > 1 << 20:
+        raise ValueError("powers: expected at most 2^20 problems, got %d" % p.shape[1])
+    _check_em_iter(n_iter)
+    dev = _device(p, X)
+    v = p.to(device=dev, dtype=torch.float32).contiguous()
+    if v.data_ptr() == p.data_ptr():
+        v = v.clone()                                               # the kernel fits the PSDs in place
+    X = torch.view_as_real(X.to(device=dev, dtype=torch.complex64)).contiguous()
+    S, N, _, F = v.shape
+    Y = torch.empty((S, N, 2, NBIN, F, 2), device=dev, dtype=torch.float32)
+    r = torch.empty((S, N, NBIN, 4), device=dev, dtype=torch.float64) if return_model else None
+    _lib.check(_lib.load().glowk_mwf_em(_p(X), _p(v), S, N, F, int(n_iter), _p(Y), _p(r), _s(v)))
+    Y = torch.view_as_complex(Y)
+    if not return_model:
+        return Y
+    c = torch.complex(r[..., 2], r[..., 3])
+    R = torch.stack([torch.complex(r[..., 0], torch.zeros_like(r[..., 0])), c, c.conj(),
+                     torch.complex(r[..., 1], torch.zeros_like(r[..., 1]))], dim=-1).reshape(S, N, NBIN, 2, 2)
+    return Y, v, R
+
+
+def istft(Y):
+    """Complex STFTs [..., 1025, F] in the front end's convention -> audio [..., (F - 1) * 512] (librosa.istft, center=True),
+    through ``griffinlim(|Y|, n_iter=0, init=exp(i angle(Y)))`` as ``invert``'s 'whole' branch.  Needs 4 <= F <= 2^20."""
+    if not torch.is_tensor(Y):
+        Y = torch.as_tensor(np.asarray(Y))
+    if not Y.is_complex() or Y.dim() < 2 or Y.shape[-2] != NBIN or not 4 <= Y.shape[-1] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("Y: expected [..., 1025, F] complex STFTs with 4 <= F <= %d, got %s %s" % (GRIFFINLIM_MAX_FRAMES, Y.dtype, tuple(Y.shape)))
+    Y = Y.to(device=_device(Y), dtype=torch.complex64)
+    lead, F = tuple(Y.shape[:-2]), Y.shape[-1]
+    Y = Y.reshape(-1, NBIN, F)
+    phase = torch.polar(torch.ones_like(Y.real), Y.angle())                         # exp(i angle(Y)), angle(0) = 0
+    return griffinlim(Y.abs(), n_iter=0, init=phase).reshape(lead + ((F - 1) * HOP,))
+
+
+def _basis_tiles(y, flows, sigmas, restores, T, delta, seed, skip, n, top_db, mixing):
+    """The tiles ``separate_sources`` finds for the mono signal y: its front end, start states, RNG streams and loop."""
+    mixed, _ = mel_tiles(extracts(y, skip, n), top_db=top_db, return_stft=True)
+    xs = [-100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14 + (k & 1), uniform=True, pair=k >> 1)
+          for k in range(len(flows))]
+    xs, _ = basis.basis_outer_loop_n(mixed, xs, flows, sigmas, restores=restores, T=T, delta=delta, seed=seed, mixing=mixing)
+    return mixed, xs
+
+
+def separate_stereo(mix, flows, sigmas, restores=None, em_iter=2, method="frame", T=100, delta=2e-5, seed=0, skip=0, n=None, top_db=80.0,
+                    iters=200, mixing="db"):
+    """A stereo mixture (wav path, read by ``load_audio(path, sr=16000, mono=False)``, or [2, n] 16 kHz samples) -> S =
+    len(flows) stereo stems.  The priors see the downmix (L + R) / 2: the tiles are those ``separate_sources`` returns for it (same
+    start states, RNG streams and ``basis_outer_loop_n``; ``restores``, ``T``, ``delta``, ``seed``, ``skip``, ``n``, ``top_db``,
+    ``iters`` and ``mixing`` as there).  Their ``mel_to_power`` spectra are the PSDs ``multichannel_wiener`` starts from, with
+    ``em_iter`` EM iterations on the two channels' STFTs, and ``istft`` gives the signals.  ``method='frame'`` fits one model per
+    extract and concatenates the signals -> [S, 2, N * 32256]; ``'whole'`` lays tiles and STFTs side by side along time and fits
+    one model for the signal -> [S, 2, (64 N - 1) * 512].  Returns ``(ys, mixed, xs)`` with the mixture tiles [N, 96, 64, 1] and
+    the separated tiles [S, N, 96, 64, 1] of the downmix."""
+    _check_method(method)
+    _check_em_iter(em_iter, "em_iter")
+    flows = list(flows)
+    if not 2 <= len(flows) <= basis.MAX_SOURCES:
+        raise ValueError("flows: expected 2..%d priors, got %d" % (basis.MAX_SOURCES, len(flows)))
+    y = load_audio(mix, sr=SR, mono=False)[0] if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__") else _tensor(mix, "mix")
+    if y.dim() != 2 or y.shape[0] != 2:
+        raise ValueError("mix: expected [2, n] stereo audio, got %s" % (tuple(y.shape),))
+    y = y.to(torch.float32)
+    mixed, xs = _basis_tiles((y[0] + y[1]) / 2, flows, sigmas, restores, T, delta, seed, skip, n, top_db, mixing)
+    S, N = len(xs), mixed.shape[0]
+    _check_frames(N, mixed.shape[2], method)
+    powers = mel_to_power(torch.cat([x.reshape(N, NMEL, -1) for x in xs]), iters).reshape(S, N, NBIN, -1)
+    _, X = mel_tiles(torch.cat([extracts(y[0], skip, n), extracts(y[1], skip, n)]), top_db=top_db, return_stft=True)
+    X = X.reshape(2, N, NBIN, -1).permute(1, 0, 2, 3)                                # [N, 2, 1025, F]
+    if method == "whole":
+        powers = torch.cat([_whole(p) for p in powers])[:, None]                    # [S, 1, 1025, N F]
+        X = _whole(X)                                                                # [1, 2, 1025, N F]
+    out = istft(multichannel_wiener(powers, X, n_iter=em_iter))                    # [S, N or 1, 2, samples]
+    return out.permute(0, 2, 1, 3).reshape(S, 2, -1), mixed, torch.stack(xs)
+
+
+def separate_wav_stereo(path, flows, sigmas, out_rate="input", **kwargs):
+    """``separate_wav_sources`` for a two-channel PCM wav at any rate -> S stereo stems at ``out_rate`` ('input', an integer rate,
+    or None for 16 kHz), all 2 S signals resampled in one launch.  ``kwargs`` are ``separate_stereo``'s keyword arguments.
+    Returns ``(ys [S, 2, n'], mixed, xs, rate)``."""
+    if not (out_rate is None or (isinstance(out_rate, str) and out_rate == "input")):
+        if isinstance(out_rate, str):
+            raise ValueError("out_rate: expected 'input', None or an integer sampling rate, got %r" % (out_rate,))
+        out_rate = _check_rate(out_rate, "out_rate")
+    y, native = load_audio(path, sr=None, mono=False)
+    if y.shape[0] != 2:
+        raise ValueError("%s: expected a two-channel wav, got %d channel(s); separate_wav_sources takes any channel count and "
+                         "averages the channels" % (path, y.shape[0]))
+    if native != SR:
+        y = resample(y, _check_rate(native, "%s: sampling rate" % (path,)), SR)
+    rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
+    ys, mixed, xs = separate_stereo(y, flows, sigmas, **kwargs)
     return resample(ys, SR, rate), mixed, xs, rate

@@ -1,12 +1,13 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
-// systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h)
+// systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
 #include "glowk_bsseval.h"
 #include "glowk_oracle.h"
 #include "glowk_resample.h"
+#include "glowk_stereo.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -790,6 +791,38 @@ int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64
     hipLaunchKernelGGL(k_oracle_mel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, mix_dev, (const float*)src_dev, nsrc, n,
                        irm ? 1 : 0, theta, (float*)out_dev);
   LAUNCHCHK("k_oracle_mel");
+  return 0;
+}
+
+// ---- stereo separation: the multichannel Wiener filter with EM-fitted spatial covariances (glowk_stereo.h) ------------------------
+int glowk_mwf_em(const float* x_dev, float* v_dev, int nsrc, int nprob, int frames, int n_iter, float* y_dev, double* r_dev, void* stream) {
+  using namespace glowk_stereo;
+  if (nsrc < 1 || nsrc > MAX_SRC) return fail("mwf_em: nsrc must be in [1, 16]");
+  if (nprob < 0 || nprob > (1 << 20)) return fail("mwf_em: nprob must be in [0, 2^20]");
+  if (frames < 1 || frames > (1 << 20)) return fail("mwf_em: frames must be in [1, 2^20]");
+  if (n_iter < 0 || n_iter > 1000) return fail("mwf_em: n_iter must be in [0, 1000]");
+  if (nprob == 0) return 0;                    // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!x_dev || !v_dev || !y_dev) return fail("null tensor");
+  int dev;
+  if (int rc = audio_device({x_dev, v_dev, y_dev, r_dev}, &dev, "mwf_em")) return rc;
+  DeviceGuard dg(dev);
+  EmArgs a;
+  a.x = reinterpret_cast<const float2*>(x_dev); a.v = v_dev; a.y = reinterpret_cast<float2*>(y_dev); a.r = r_dev;
+  a.S = nsrc; a.P = nprob; a.T = frames; a.n_iter = n_iter;
+  const int nt = em_threads(frames);
+  const size_t staged = em_stage_bytes(nsrc, frames);
+  const bool stage = staged <= STAGE_MAX;
+  const size_t lds = em_state_bytes(nt) + (stage ? staged : 0);
+  const dim3 grid((unsigned)((int64_t)nprob * NBIN));          // <= 2^20 x 1025 workgroups: within one launch
+  hipStream_t s = (hipStream_t)stream;
+#define GLOWK_EM_LAUNCH(NT) \
+  if (stage) hipLaunchKernelGGL((k_mwf_em<NT, true>), grid, dim3(NT), lds, s, a); \
+  else hipLaunchKernelGGL((k_mwf_em<NT, false>), grid, dim3(NT), lds, s, a)
+  if (nt == 64) { GLOWK_EM_LAUNCH(64); }
+  else if (nt == 128) { GLOWK_EM_LAUNCH(128); }
+  else { GLOWK_EM_LAUNCH(256); }
+#undef GLOWK_EM_LAUNCH
+  LAUNCHCHK("k_mwf_em");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 470
+#define GLOWK_VERSION 480
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -435,6 +435,27 @@ int glowk_mwf(float* spec_dev, int nsrc, int frames, void* stream);
  * product in double; one rounding to the output type.  0 <= n <= 2^40. */
 int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64_t n, int src_f64, int irm, double theta, void* out_dev,
                      void* stream);
+
+/* --- stereo separation: the multichannel Wiener filter with EM-fitted spatial covariances (Duong, Vincent, Gribonval 2010) --- */
+/* Handle-free, in the front end's STFT convention (hop 512, [.., 1025, T], frame fastest, complex re/im interleaved), batched over
+ * nprob problems (extracts).  A problem has the stereo mixture STFT x(f,t) in C^2, nsrc source PSDs v_j(f,t) >= 0 and the 2 x 2
+ * Hermitian spatial covariances R_j(f), R_j = I at the start.  With eps = 1e-10, one iteration (the old v, R on every right-hand
+ * side):
+ *   Cx = sum_k v_k R_k + eps I,  W_j = v_j R_j Cx^-1,  y_j = W_j x,  C_j = y_j y_j^H + (I - W_j) v_j R_j,
+ *   v_j' = max(0, Re tr(R_j^-1 C_j) / 2),  R_j'(f) = (1/T) sum_t C_j / (v_j' + eps) + eps I,
+ * and after n_iter iterations Y_j = v_j R_j Cx^-1 x with the final v, R; n_iter = 0 is v_j / (sum_k v_k + eps) x per channel, the
+ * single-channel Wiener mask of glowk_masked_istft on each channel.  (Unlike glowk_mwf, the reference's oracle: no true source
+ * spectra, no np.trace normalisation.)
+ *   x [nprob][2][1025][T] complex, v [nsrc][nprob][1025][T] float (in: the PSDs; out: the fitted ones, untouched when n_iter = 0),
+ *   y [nsrc][nprob][2][1025][T] complex, r (nullable) [nsrc][nprob][1025][4] double = (r00, r11, Re r01, Im r01) of the final R_j(f).
+ * One launch on `stream` for the whole call, all iterations included: one workgroup owns one (problem, bin) and runs the loop; no
+ * host synchronisation, no atomics, no allocation.  fp64 arithmetic in registers, v held in fp32 between iterations; 2 x 2
+ * determinants as det M + eps tr M + eps^2 with det M clamped at 0, so they stay >= 1e-20.  The time sums are added in one fixed
+ * order that depends on T alone: bitwise reproducible, and a (problem, bin)'s results depend on nothing outside it.  nsrc in
+ * [1, 16], nprob in [0, 2^20] (0 is a successful no-op), frames in [1, 2^20], n_iter in [0, 1000]; anything else is GLOWK_ERR;
+ * a host pointer is refused.  v_dev is the only input written. */
+int glowk_mwf_em(const float* x_dev, float* v_dev, int nsrc, int nprob, int frames, int n_iter, float* y_dev, double* r_dev,
+                 void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
