@@ -129,6 +129,9 @@ SYMBOLS = {
     "glowk_mwf": (_i, [_vp, _i, _i, _vp]),
     "glowk_oracle_mel": (_i, [_vp, _vp, _i, ctypes.c_int64, _i, _i, ctypes.c_double, _vp, _vp]),
     "glowk_mwf_em": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "glowk_mel_frames": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp]),
+    "glowk_tile_cut": (_i, [_vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
+    "glowk_tile_stitch": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

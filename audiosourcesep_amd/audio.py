@@ -24,6 +24,12 @@ Replaces the reference's ``get_song_extract`` (datasets/data_loader.py:113-164) 
 * ``multichannel_wiener`` / ``istft`` / ``separate_stereo`` / ``separate_wav_stereo``: stereo in, stereo stems out.  The priors
   stay mono (they see the downmix); the stems come from a multichannel Wiener filter under the local Gaussian model whose
   spatial covariances are fitted by EM from the priors' PSDs (Duong, Vincent, Gribonval 2010; ``csrc/glowk_stereo.h``, one launch).
+* ``separate_long`` / ``separate_wav_long``: a whole file in, stems exactly as long as it and aligned with it out (mono or
+  stereo).  The per-extract paths above follow the reference, which only ever cuts disjoint 2.04 s extracts: they drop the trailing
+  partial extract and shift extract k by 384 k ('frame') or 128 k ('whole') samples.  Here one STFT covers the whole signal
+  (``mel_frames``), the priors see tiles cut every ``tile_hop`` frames (``frame_tiles``), their estimates are cross-faded back into
+  frames (``stitch_tiles``: sin^2 weights, a weighted mean in dB) and one inversion of the whole signal is trimmed to the input's
+  length (``invert_frames``, ``mask_istft_long``).  Kernels in ``csrc/glowk_longform.h``; not in the reference.
 
 Not covered: IEEE-float and WAVE_FORMAT_EXTENSIBLE wavs and the power-scale flows (``scale='power'``).
 """
@@ -599,3 +605,214 @@ def separate_wav_stereo(path, flows, sigmas, out_rate="input", **kwargs):
     rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
     ys, mixed, xs = separate_stereo(y, flows, sigmas, **kwargs)
     return resample(ys, SR, rate), mixed, xs, rate
+
+
+# ---- whole signals: one STFT, overlapping tiles for the priors, stems as long as the input ------------------------------------------
+LONG_MAX_SAMPLES = (GRIFFINLIM_MAX_FRAMES - 1) * HOP     # glowk_mel_frames' cap: 2^20 frames
+MAX_TILE_WIDTH = 128                                     # glowk_tile_cut / glowk_tile_stitch: a tile is at most mel_to_power's 128 frames
+
+
+def _long_audio(y, what="y"):
+    """[n] or [C, n] audio with 1024 < n <= LONG_MAX_SAMPLES as a [C, n] tensor where it is."""
+    x = _tensor(y, what)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or not 1 <= x.shape[0] <= 1 << 20 or not 1024 < x.shape[1] <= LONG_MAX_SAMPLES:
+        raise ValueError("%s: expected [n] or [C, n] audio with 1024 < n <= %d, got %s" % (what, LONG_MAX_SAMPLES, tuple(x.shape)))
+    return x
+
+
+def _check_tiling(width, tile_hop):
+    for name, v in (("width", width), ("tile_hop", tile_hop)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: expected an integer, got %r" % (name, v))
+    if not 2 <= width <= MAX_TILE_WIDTH:
+        raise ValueError("width: expected a tile width in [2, %d], got %d" % (MAX_TILE_WIDTH, width))
+    if not 1 <= tile_hop <= width:
+        raise ValueError("tile_hop: expected an integer in [1, width = %d], got %d" % (width, tile_hop))
+
+
+def _check_long_frames(f, what):
+    if f.dim() != 3 or f.shape[1] != NMEL or not 1 <= f.shape[2] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("%s: expected [C, 96, F] dB frames with 1 <= F <= %d, got %s" % (what, GRIFFINLIM_MAX_FRAMES, tuple(f.shape)))
+
+
+def tile_count(n_frames, width=64, tile_hop=32):
+    """Tiles of ``width`` frames every ``tile_hop`` frames that cover ``n_frames``: 1 if they fit one tile, else
+    1 + ceil((n_frames - width) / tile_hop)."""
+    return 1 if n_frames <= width else 1 + -(-(n_frames - width) // tile_hop)
+
+
+def mel_frames(y, return_stft=False):
+    """[n] or [C, n] 16 kHz audio of any length n > 1024 -> dB mel frames [C, 96, F] of the whole signal, zero-padded to
+    n' = ceil(n / 512) * 512 samples (F = 1 + n' / 512); with ``return_stft`` also its complex STFT [C, 1025, F] (complex64).
+    ``mel_tiles``' convention and arithmetic without the per-extract ``top_db`` floor and without its 128-frame limit
+    (``glowk_mel_frames``); frame f is centred on sample 512 f of the signal."""
+    x = _long_audio(y)
+    x = x.to(device=_device(x), dtype=torch.float32)
+    C, n = x.shape
+    x = torch.nn.functional.pad(x, (0, -n % HOP)).contiguous()
+    F = 1 + x.shape[1] // HOP
+    mel = torch.empty((C, NMEL, F), device=x.device, dtype=torch.float32)
+    X = torch.empty((C, NBIN, F, 2), device=x.device, dtype=torch.float32) if return_stft else None
+    _lib.check(_lib.load().glowk_mel_frames(_p(x), C, x.shape[1], _p(mel), _p(X), _s(x)))
+    return (mel, torch.view_as_complex(X)) if return_stft else mel
+
+
+def frame_tiles(frames, width=64, tile_hop=32, top_db=80.0):
+    """dB frames [C, 96, F] (or [96, F]) -> overlapping tiles [C, N, 96, width, 1], N = ``tile_count(F, width, tile_hop)``: tile k
+    holds frames [k tile_hop, k tile_hop + width), -100 dB past the end.  ``top_db`` (None or 0: none): ``mel_tiles``' floor per
+    tile, max over the padded tile - top_db; every cell is clipped to [-100, 20] (``glowk_tile_cut``)."""
+    f = _tensor(frames, "frames")
+    if f.dim() == 2:
+        f = f[None]
+    _check_long_frames(f, "frames")
+    _check_tiling(width, tile_hop)
+    if not (top_db is None or (isinstance(top_db, (int, float, np.integer, np.floating)) and math.isfinite(top_db))):
+        raise ValueError("top_db: expected None or a finite number, got %r" % (top_db,))
+    f = f.to(device=_device(f), dtype=torch.float32).contiguous()
+    C, _, F = f.shape
+    out = torch.empty((C, tile_count(F, width, tile_hop), NMEL, width, 1), device=f.device, dtype=torch.float32)
+    _lib.check(_lib.load().glowk_tile_cut(_p(f), C, F, int(width), int(tile_hop), float(top_db or 0.0), _p(out), _s(f)))
+    return out
+
+
+def stitch_tiles(tiles, n_frames, tile_hop=32):
+    """Overlapping tiles [C, N, 96, width(, 1)] -> frames [C, 96, n_frames]: each frame the mean, in dB, of the tiles that cover
+    it, weighted by w[j] = sin^2(pi (j + 1/2) / width) at its position j in each (``glowk_tile_stitch``; the weights of a frame sum
+    to 1 at tile_hop = width / 2).  A frame one tile covers is that tile's value, bit for bit.  n_frames <= (N - 1) tile_hop +
+    width.  Inverse of ``frame_tiles(..., top_db=None)`` on frames within [-100, 20]."""
+    t = _tensor(tiles, "tiles")
+    if t.dim() == 5 and t.shape[4] == 1:
+        t = t[..., 0]
+    if t.dim() != 4 or t.shape[2] != NMEL or not 1 <= t.shape[1] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("tiles: expected [C, N, 96, width] or [C, N, 96, width, 1] dB tiles, got %s" % (tuple(tiles.shape),))
+    C, N, _, width = t.shape
+    _check_tiling(width, tile_hop)
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or not 1 <= n_frames <= min(GRIFFINLIM_MAX_FRAMES, (N - 1) * tile_hop + width):
+        raise ValueError("n_frames: expected an integer in [1, (N - 1) tile_hop + width = %d], got %r" % ((N - 1) * tile_hop + width, n_frames))
+    t = t.to(device=_device(t), dtype=torch.float32).contiguous()
+    out = torch.empty((C, NMEL, int(n_frames)), device=t.device, dtype=torch.float32)
+    _lib.check(_lib.load().glowk_tile_stitch(_p(t), C, N, width, int(tile_hop), int(n_frames), _p(out), _s(t)))
+    return out
+
+
+def _check_long_inversion(S, F, X, n, wiener, what):
+    """The mixture STFT [1025, F] (mono) or [2, 1025, F] (stereo) of S sources' F frames and the output length n; True if stereo."""
+    if tuple(X.shape) not in ((NBIN, F), (2, NBIN, F)):
+        raise ValueError("stft_mixture: expected [1025, F] or [2, 1025, F] with F = %d to match the %s, got %s" % (F, what, tuple(X.shape)))
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= (F - 1) * HOP:
+        raise ValueError("n: expected an integer in [1, (F - 1) * 512 = %d], got %r" % ((F - 1) * HOP, n))
+    if X.dim() == 2 and wiener and S < 2:
+        raise ValueError("the Wiener filter needs at least 2 sources, got %d" % S)
+    return X.dim() == 3
+
+
+def mask_istft_long(powers, stft_mixture, n, wiener=False, em_iter=2):
+    """Power spectra [S, 1025, F] of S sources + the whole mixture's STFT -> their signals, trimmed to the first n samples.
+    Mono, ``stft_mixture`` [1025, F]: the mixture's phase reused, or with ``wiener`` (S >= 2) the single-channel Wiener filter, as
+    ``invert``'s 'whole' branch -> [S, n].  Stereo, [2, 1025, F]: ``multichannel_wiener(..., n_iter=em_iter)`` as one problem, then
+    ``istft`` -> [S, 2, n] (always a Wiener filter; ``wiener`` is not consulted).  4 <= F <= 2^20, n <= (F - 1) * 512."""
+    p, X = _tensor(powers, "powers"), _tensor(stft_mixture, "stft_mixture")
+    if p.dim() != 3 or p.shape[1] != NBIN or not 1 <= p.shape[0] <= basis.MAX_SOURCES or not 4 <= p.shape[2] <= GRIFFINLIM_MAX_FRAMES:
+        raise ValueError("powers: expected [S, 1025, F] with 1 <= S <= %d and 4 <= F <= %d, got %s"
+                         % (basis.MAX_SOURCES, GRIFFINLIM_MAX_FRAMES, tuple(p.shape)))
+    stereo = _check_long_inversion(p.shape[0], p.shape[2], X, n, wiener, "powers")
+    _check_em_iter(em_iter, "em_iter")
+    dev = _device(p, X)
+    P, Xw = p.to(device=dev, dtype=torch.float32), X.to(device=dev, dtype=torch.complex64)
+    if stereo:
+        y = istft(multichannel_wiener(P[:, None], Xw[None], n_iter=em_iter)[:, 0])       # [S, 2, (F - 1) * 512]
+    else:
+        S = P / (P.sum(0) + 1e-10) * Xw.abs() if wiener else torch.sqrt(P)
+        phase = torch.polar(torch.ones_like(Xw.real), Xw.angle())                       # exp(i angle(X)), angle(0) = 0
+        y = griffinlim(S, n_iter=0, init=phase.expand(S.shape))
+    return y[..., :int(n)].contiguous()
+
+
+def invert_frames(frames, stft_mixture, n, wiener=False, iters=200, em_iter=2):
+    """dB frames [S, 96, F] of S sources of one signal + the mixture's STFT ([1025, F], or [2, 1025, F] for stereo) -> their
+    signals [S, n] ([S, 2, n]): ``mel_to_power`` (per frame; the frames go through it as tiles of at most 128), then
+    ``mask_istft_long``.  n <= (F - 1) * 512: the samples ``mel_frames`` padded are trimmed."""
+    f, X = _tensor(frames, "frames"), _tensor(stft_mixture, "stft_mixture")
+    _check_long_frames(f, "frames")
+    if not 1 <= f.shape[0] <= basis.MAX_SOURCES or f.shape[2] < 4:
+        raise ValueError("frames: expected [S, 96, F] with 1 <= S <= %d and F >= 4, got %s" % (basis.MAX_SOURCES, tuple(f.shape)))
+    _check_long_inversion(f.shape[0], f.shape[2], X, n, wiener, "frames")
+    _check_em_iter(em_iter, "em_iter")
+    f = f.to(device=_device(f, X), dtype=torch.float32)
+    S, _, F = f.shape
+    nt = -(-F // MAX_TILE_WIDTH)
+    w = -(-F // nt)                                                                       # nt tiles of w <= 128 frames hold F
+    t = torch.nn.functional.pad(f, (0, nt * w - F), value=-100.0).reshape(S, NMEL, nt, w).permute(0, 2, 1, 3).reshape(S * nt, NMEL, w)
+    p = mel_to_power(t, iters).reshape(S, nt, NBIN, w).permute(0, 2, 1, 3).reshape(S, NBIN, nt * w)[:, :, :F]
+    return mask_istft_long(p, X, n, wiener=wiener, em_iter=em_iter)
+
+
+def _tile_width(flows):
+    """The tile width W the priors share: every flow's data shape must be [96, W, 1] with 2 <= W <= 128."""
+    shapes = [tuple(int(d) for d in getattr(fl, "event_shape", ())) for fl in flows]
+    s0 = shapes[0]
+    if len(s0) != 3 or s0[0] != NMEL or s0[2] != 1 or not 2 <= s0[1] <= MAX_TILE_WIDTH or any(s != s0 for s in shapes):
+        raise ValueError("flows: expected priors of one data shape [96, W, 1] with 2 <= W <= %d, got %s" % (MAX_TILE_WIDTH, shapes))
+    return s0[1]
+
+
+def separate_long(mix, flows, sigmas, restores=None, tile_hop=32, T=100, delta=2e-5, seed=0, top_db=80.0, iters=200, wiener=True,
+                  em_iter=2, mixing="db"):
+    """A whole mixture (wav path, [n] mono or [2, n] stereo 16 kHz samples, n > 1024) -> S = len(flows) stems exactly as long as
+    it and aligned with it, S in [2, 16].  One STFT of the signal (``mel_frames``; stereo: of both channels and of the downmix
+    (L + R) / 2, which is what the priors see); tiles of the priors' width W every ``tile_hop`` frames with the per-tile ``top_db``
+    floor (``frame_tiles``); ``basis.basis_outer_loop_n`` on them from ``separate_sources``' start states and RNG streams;
+    the separated tiles cross-faded into frames (``stitch_tiles``); ``invert_frames`` (``wiener``, ``iters``; stereo: ``em_iter``
+    EM iterations of the multichannel Wiener filter, one model for the signal).  The priors see independent tiles: only their
+    estimates are cross-faded.  Returns ``(ys, mixed_frames, source_frames)``: [S, n] (stereo [S, 2, n]), the mixture's (downmix's)
+    unfloored frames [96, F] and the separated frames [S, 96, F], F = 1 + ceil(n / 512)."""
+    flows = list(flows)
+    if not 2 <= len(flows) <= basis.MAX_SOURCES:
+        raise ValueError("flows: expected 2..%d priors, got %d" % (basis.MAX_SOURCES, len(flows)))
+    W = _tile_width(flows)
+    _check_tiling(W, tile_hop)
+    _check_em_iter(em_iter, "em_iter")
+    if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__"):
+        y = load_audio(mix, sr=SR, mono=False)[0]
+        y = y[0] if y.shape[0] == 1 else y
+    else:
+        y = _tensor(mix, "mix")
+    if not (y.dim() == 1 or (y.dim() == 2 and y.shape[0] == 2)) or not 1024 < y.shape[-1] <= LONG_MAX_SAMPLES:
+        raise ValueError("mix: expected [n] mono or [2, n] stereo audio with 1024 < n <= %d, got %s" % (LONG_MAX_SAMPLES, tuple(y.shape)))
+    stereo, n = y.dim() == 2, y.shape[-1]
+    y = y.to(device=_device(y), dtype=torch.float32)
+    mel, X = mel_frames(torch.stack([y[0], y[1], (y[0] + y[1]) / 2]) if stereo else y, return_stft=True)
+    mixed_frames = mel[-1]
+    mixed = frame_tiles(mixed_frames, W, tile_hop, top_db)[0]                             # [N, 96, W, 1]
+    xs = [-100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14 + (k & 1), uniform=True, pair=k >> 1)
+          for k in range(len(flows))]
+    xs, _ = basis.basis_outer_loop_n(mixed, xs, flows, sigmas, restores=restores, T=T, delta=delta, seed=seed, mixing=mixing)
+    source_frames = stitch_tiles(torch.stack(xs), mixed_frames.shape[1], tile_hop)
+    ys = invert_frames(source_frames, X[:2] if stereo else X[0], n, wiener=wiener, iters=iters, em_iter=em_iter)
+    return ys, mixed_frames, source_frames
+
+
+def separate_wav_long(path, flows, sigmas, out_rate="input", mono=False, **kwargs):
+    """``separate_long`` for a PCM wav at any rate -> S stems at ``out_rate`` ('input', an integer rate, or None for 16 kHz), all
+    resampled in one launch.  A two-channel file gives stereo stems unless ``mono``; any other channel count is averaged.  With
+    ``out_rate='input'`` the stems have exactly the file's sample count (the round trip through 16 kHz gives at least as many;
+    the excess is trimmed).  ``kwargs`` are ``separate_long``'s keyword arguments.  Returns ``(ys [S, n'] or [S, 2, n'],
+    mixed_frames, source_frames, rate)``."""
+    if not (out_rate is None or (isinstance(out_rate, str) and out_rate == "input")):
+        if isinstance(out_rate, str):
+            raise ValueError("out_rate: expected 'input', None or an integer sampling rate, got %r" % (out_rate,))
+        out_rate = _check_rate(out_rate, "out_rate")
+    y, native = load_audio(path, sr=None, mono=False)
+    n_file = y.shape[1]
+    if y.shape[0] != 2 or mono:
+        y = y.mean(0)
+    if native != SR:
+        y = resample(y, _check_rate(native, "%s: sampling rate" % (path,)), SR)
+    rate = SR if out_rate is None else native if isinstance(out_rate, str) else out_rate
+    ys, mixed_frames, source_frames = separate_long(y, flows, sigmas, **kwargs)
+    ys = resample(ys, SR, rate)
+    if isinstance(out_rate, str):
+        ys = ys[..., :n_file].contiguous()
+    return ys, mixed_frames, source_frames, rate

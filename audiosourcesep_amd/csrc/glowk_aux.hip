@@ -1,6 +1,7 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
-// systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h)
+// systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h),
+// whole-signal mel frames and overlapping tiles (glowk_longform.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -8,6 +9,7 @@
 #include "glowk_oracle.h"
 #include "glowk_resample.h"
 #include "glowk_stereo.h"
+#include "glowk_longform.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -823,6 +825,84 @@ int glowk_mwf_em(const float* x_dev, float* v_dev, int nsrc, int nprob, int fram
   else { GLOWK_EM_LAUNCH(256); }
 #undef GLOWK_EM_LAUNCH
   LAUNCHCHK("k_mwf_em");
+  return 0;
+}
+
+// ---- whole-signal separation: mel frames of any length, overlapping tiles out and back (glowk_longform.h) -------------------------
+namespace {
+// the geometry glowk_tile_cut and glowk_tile_stitch share
+int tile_geometry(const char* who, int nsig, int width, int hop) {
+  if (nsig < 0 || nsig > (1 << 20)) return fail(std::string(who) + ": nsig must be in [0, 2^20]");
+  if (width < 2 || width > glowk_long::MAX_WIDTH) return fail(std::string(who) + ": width must be in [2, 128]");
+  if (hop < 1 || hop > width) return fail(std::string(who) + ": hop must be in [1, width]");
+  return 0;
+}
+}  // namespace
+
+int glowk_mel_frames(const float* audio_dev, int nsig, int64_t n_samples, float* mel_db_dev, float* stft_dev, void* stream) {
+  using namespace glowk_audio;
+  if (nsig < 0 || nsig > (1 << 20)) return fail("mel_frames: nsig must be in [0, 2^20]");
+  if (n_samples < 3 * HOP || n_samples > (int64_t)(glowk_long::MAX_FRAMES - 1) * HOP || n_samples % HOP)
+    return fail("mel_frames: n_samples must be a multiple of 512 in [1536, (2^20 - 1) * 512]");
+  const int F = 1 + (int)(n_samples / HOP), ftiles = (F + 31) / 32, fblocks = (F + 255) / 256;
+  if ((int64_t)nsig * ftiles > INT32_MAX) return fail("mel_frames: too many signals x frames for one launch");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!audio_dev || !mel_db_dev) return fail("null tensor");
+  int dev;
+  if (int rc = audio_device({audio_dev, mel_db_dev, stft_dev}, &dev, "mel_frames")) return rc;
+  DeviceGuard dg(dev);
+  AudioConsts c;
+  if (int rc = audio_consts(dev, &c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Scratch<float> power(HipFreeAsync{s});       // |X|^2 scratch, only when the caller does not take the complex STFT
+  if (!stft_dev) HIPCHK(scratch_alloc(power, (size_t)nsig * NBIN * F * sizeof(float)));
+  hipLaunchKernelGGL(k_stft, dim3((unsigned)(nsig * ftiles), (NBIN + 127) / 128), dim3(256), 0, s, audio_dev, (int)n_samples, F, ftiles, c, power,
+                     stft_dev);
+  LAUNCHCHK("k_stft");
+  hipLaunchKernelGGL(glowk_long::k_mel_frames, dim3((unsigned)(nsig * fblocks), NMEL), dim3(256), 0, s, (const float*)power,
+                     (const float2*)stft_dev, F, fblocks, c, mel_db_dev);
+  LAUNCHCHK("k_mel_frames");
+  return 0;
+}
+
+int glowk_tile_cut(const float* frames_dev, int nsig, int frames, int width, int hop, float top_db, float* tiles_dev, void* stream) {
+  using namespace glowk_long;
+  if (int rc = tile_geometry("tile_cut", nsig, width, hop)) return rc;
+  if (frames < 1 || frames > MAX_FRAMES) return fail("tile_cut: frames must be in [1, 2^20]");
+  if (!(std::fabs(top_db) < 1e30f)) return fail("tile_cut: top_db must be finite");
+  const int N = frames <= width ? 1 : 1 + (frames - width + hop - 1) / hop;
+  if ((int64_t)nsig * N > INT32_MAX) return fail("tile_cut: too many signals x tiles for one launch");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!frames_dev || !tiles_dev) return fail("null tensor");
+  int dev;
+  if (int rc = audio_device({frames_dev, tiles_dev}, &dev, "tile_cut")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_tile_cut, dim3((unsigned)(nsig * N)), dim3(256), 0, (hipStream_t)stream, frames_dev, frames, N, width, hop, top_db, tiles_dev);
+  LAUNCHCHK("k_tile_cut");
+  return 0;
+}
+
+int glowk_tile_stitch(const float* tiles_dev, int nsig, int N, int width, int hop, int frames, float* frames_dev, void* stream) {
+  using namespace glowk_long;
+  if (int rc = tile_geometry("tile_stitch", nsig, width, hop)) return rc;
+  if (N < 1 || N > MAX_FRAMES) return fail("tile_stitch: N must be in [1, 2^20]");
+  if (frames < 1 || frames > MAX_FRAMES || frames > (int64_t)(N - 1) * hop + width)
+    return fail("tile_stitch: frames must be in [1, min(2^20, (N - 1) * hop + width)]: every frame needs a tile");
+  const int fblocks = (frames + 255) / 256;
+  if ((int64_t)nsig * fblocks > INT32_MAX) return fail("tile_stitch: too many signals x frames for one launch");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!tiles_dev || !frames_dev) return fail("null tensor");
+  int dev;
+  if (int rc = audio_device({tiles_dev, frames_dev}, &dev, "tile_stitch")) return rc;
+  DeviceGuard dg(dev);
+  StitchWindow win;                            // sin^2(pi (j + 1/2) / width) in fp64, rounded once; zero past the width (never read)
+  for (int j = 0; j < MAX_WIDTH; ++j) {
+    const double sn = std::sin(3.14159265358979323846 * (j + 0.5) / width);
+    win.w[j] = j < width ? (float)(sn * sn) : 0.0f;
+  }
+  hipLaunchKernelGGL(k_tile_stitch, dim3((unsigned)(nsig * fblocks), glowk_audio::NMEL), dim3(256), 0, (hipStream_t)stream, tiles_dev, N, width,
+                     hop, frames, fblocks, win, frames_dev);
+  LAUNCHCHK("k_tile_stitch");
   return 0;
 }
 

@@ -457,6 +457,33 @@ int glowk_oracle_mel(const double* mix_dev, const void* src_dev, int nsrc, int64
 int glowk_mwf_em(const float* x_dev, float* v_dev, int nsrc, int nprob, int frames, int n_iter, float* y_dev, double* r_dev,
                  void* stream);
 
+/* --- whole-signal separation: mel frames of a signal of any length, overlapping tiles out and back --------------------------- */
+/* Handle-free, the project's own (the reference only cuts disjoint 2.04 s extracts): one STFT of the whole signal, overlapping
+ * tiles of its dB frames for the priors, the separated tiles cross-faded back into frames.  The front end's constants are
+ * compiled in (see the audio section).  Every tensor is float32 device memory on one device (a host pointer is refused); each
+ * call enqueues on `stream`, synchronises nothing with the host and uses no atomics; every sum runs in a fixed order: bitwise
+ * reproducible.  nsig in [0, 2^20], nsig == 0 is a successful no-op; anything outside the stated ranges is GLOWK_ERR.  Added to
+ * version 480 without a new number: nothing that existed changed; a library without them lacks the symbols.
+ */
+/* audio [nsig][n_samples] 16 kHz -> mel_db [nsig][96][F], F = 1 + n_samples / 512, and (nullable) the complex STFT stft
+ * [nsig][1025][F]: glowk_mel_frontend's convention (center, reflect padding, periodic Hann, |X|^2, Slaney mel,
+ * 10 log10(max(1e-10, .)), clip to [-100, 20]) and arithmetic, without its per-extract top_db floor and without its bound on F.
+ * n_samples: a multiple of 512 in [1536, (2^20 - 1) * 512].  Two launches; without stft_dev the call takes an [nsig][1025][F]
+ * float scratch from the stream-ordered allocator for |X|^2. */
+int glowk_mel_frames(const float* audio_dev, int nsig, int64_t n_samples, float* mel_db_dev, float* stft_dev, void* stream);
+/* frames [nsig][96][F] (dB) -> tiles [nsig][N][96][width], N = 1 if F <= width, else 1 + ceil((F - width) / hop): tile k holds
+ * frames [k hop, k hop + width), -100 dB (silence) at and beyond F.  top_db > 0: each cell becomes max(cell, tile_max - top_db),
+ * the maximum taken over the padded tile (glowk_mel_frontend's floor, per tile); then every cell is clipped to [-100, 20].
+ * width in [2, 128], hop in [1, width], frames = F in [1, 2^20], top_db finite.  One launch, one workgroup per tile. */
+int glowk_tile_cut(const float* frames_dev, int nsig, int frames, int width, int hop, float top_db, float* tiles_dev, void* stream);
+/* tiles [nsig][N][96][width] -> frames [nsig][96][F], F <= (N - 1) hop + width: the weighted mean, in dB, of the tiles that
+ * cover a frame,  out[f] = sum_k w[f - k hop] t_k[f - k hop] / sum_k w[f - k hop],  w[j] = sin^2(pi (j + 1/2) / width)
+ * (strictly positive; w[j] + w[j + width / 2] = 1, so the denominator is 1 at hop = width / 2), built in fp64 and rounded once;
+ * k ascends, fp32 fused multiply-adds.  A frame that exactly one tile covers is that tile's value, bit for bit.  The tiles are
+ * not clipped (BASIS states may leave [-100, 20]).  width in [2, 128], hop in [1, width], N in [1, 2^20], frames = F in
+ * [1, 2^20].  One launch, one thread per output cell, no allocation. */
+int glowk_tile_stitch(const float* tiles_dev, int nsig, int N, int width, int hop, int frames, float* frames_dev, void* stream);
+
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
  * checkpoint bundles (train_utils.py:62-75), whose tensors are too large for an interpreted byte loop */
