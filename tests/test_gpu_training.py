@@ -25,11 +25,12 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
-def oracle_param_grads(x, params, cfg, scale):
-    """d (scale * sum_n log_prob(x_n)) / d theta for every trainable tensor, fp64 reverse mode over oracle/glowref_torch.py."""
-    p = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=k.split("/", 2)[-1] in TRAINABLE or k in TRAINABLE)
+def oracle_param_grads(x, params, cfg, scale, dtype=torch.float64):
+    """d (scale * sum_n log_prob(x_n)) / d theta for every trainable tensor, fp64 reverse mode over oracle/glowref_torch.py
+    (dtype=torch.float32: the same oracle in float32, the yardstick of what a plain fp32 implementation delivers)."""
+    p = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=k.split("/", 2)[-1] in TRAINABLE or k in TRAINABLE)
          for k, v in params.items()}
-    lp, _ = RT.log_prob(torch.from_numpy(x.astype(np.float64)), p, cfg.as_dict())
+    lp, _ = RT.log_prob(torch.from_numpy(x).to(dtype), p, cfg.as_dict())
     names = [k for k, v in p.items() if v.requires_grad]
     grads = torch.autograd.grad(scale * lp.sum(), [p[k] for k in names], allow_unused=True)
     return lp.detach().numpy(), {k: (g.numpy() if g is not None else np.zeros_like(params[k], dtype=np.float64)) for k, g in zip(names, grads)}
