@@ -158,10 +158,11 @@ __device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.0e3
 // gather conv3 (9 taps), split + tanh (flow_tfk_layers.py:80-84), affine coupling
 // (flow_tfp_bijectors.py:134-148), per-sample log-det (:150-153), then the following per-pixel affine
 // QUAD: four lanes per pixel (small batches: the per-sample workgroups cannot fill the chip, so parallelism has to come from
-// inside the pixel); otherwise one lane per pixel (large batches: fewer, fully used lanes -- 47 vs 80 us at 1024 tiles)
+// inside the pixel); otherwise one lane per pixel (large batches: fewer, fully used lanes -- 47 vs 80 us at 1024 tiles when
+// the form was introduced; not re-measured against the four-lane form since)
 // one pixel of k_couple: gather the nine taps (QUAD: this lane's three, then the quad sum), bias, tanh / exp, coupling, the
 // following affine, store.  Returns the pixel's sum of log_s on the lane that finished it (lane 0 of a quad), 0 elsewhere.
-// LPP lanes per pixel: 1, 4 (lane r: taps r, r + 4, r + 8 of every partial) or 16 (the (tap, partial) pairs dealt round robin: the
+// LPP lanes per pixel: 1 (the same sums in the same order as 4, on one lane), 4 (lane r: taps r, r + 4, r + 8 of every partial) or 16 (the (tap, partial) pairs dealt round robin: the
 // deep levels at small batches, where 64 pixels x 16 channels x 4 partials are ~200 dependent loads per lane of a 4-lane kernel)
 template <int C, int LPP>
 __device__ __forceinline__ float couple_pixel(const CoupleArgs& a, int q, int i, int j, bool live, int r4) {
@@ -181,10 +182,50 @@ __device__ __forceinline__ float couple_pixel(const CoupleArgs& a, int q, int i,
         for (int c = 0; c < C; ++c) o[c] += src[(size_t)c * a.Q];
       }
     }
+  } else if constexpr (LPP == 1) {
+    // one lane per pixel, adding in the ORDER of the four-lane form: the sums of taps r, r + 4, r + 8 (every partial) for r = 0 .. 3,
+    // then (s0 + s1) + (s2 + s3) -- what the quad's butterfly leaves on its lane 0.  A pixel's result is then bit for bit the same
+    // whether its batch is large enough for this form or not (a tile alone against the tile inside 2 x CUs tiles or more).
+    // (four independent chains: 121 / 160 registers at 16 / 32 channels, 73 / 99 in tap order, which is why k_couple<C, false> is bounded to the 256 threads it is
+    //  launched with.  k_couple<C, false> at 1024 tiles, C = 4 / 8 / 16 / 32 on 1024 / 256 / 64 / 16 pixels a tile (scripts/couple_time.py,
+    //  rocprofv3 kernel trace): 29.4 / 17.4 / 13.2 / 40.5 us, against 29.6 / 17.4 / 13.7 / 23.1 us when the taps were added in tap order --
+    //  the 32-channel level pays for the order; rolling the loop over r cost more: 17.5 / 59.6 us at 16 / 32 channels)
+    float s23[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s23[c] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float t[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) t[c] = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        const int tap = r + 4 * u;
+        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+        const int ii = i + dy, jj = j + dx;
+        if (tap < 9 && ii >= 0 && ii < a.h && jj >= 0 && jj < a.w) {
+          const size_t off = (size_t)(tap * C) * a.Q + (q + dy * a.w + dx);
+#pragma unroll
+          for (int part = 0; part < 4; ++part)
+            if (part < a.np) {
+              const float* src = a.P + (size_t)part * a.pstride + off;
+#pragma unroll
+              for (int c = 0; c < C; ++c) t[c] += src[(size_t)c * a.Q];
+            }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        if (r < 2) o[c] += t[c];
+        else s23[c] += t[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] += s23[c];
   } else {
 #pragma unroll
-  for (int u = 0; u < (QUAD ? 3 : 9); ++u) {
-    const int tap = QUAD ? r4 + 4 * u : u;
+  for (int u = 0; u < 3; ++u) {
+    const int tap = r4 + 4 * u;
     const int dy = tap / 3 - 1, dx = tap % 3 - 1;
     const int ii = i + dy, jj = j + dx;
     if (tap < 9 && ii >= 0 && ii < a.h && jj >= 0 && jj < a.w) {
@@ -315,7 +356,7 @@ __device__ __forceinline__ float couple_pixel(const CoupleArgs& a, int q, int i,
 }
 
 template <int C, bool QUAD>
-__global__ __launch_bounds__(1024) void k_couple(CoupleArgs a) {   // 256 .. 1024 threads
+__global__ __launch_bounds__(QUAD ? 1024 : 256) void k_couple(CoupleArgs a) {   // QUAD: 256 .. 1024 threads; else 256
   __shared__ double red[16];
   const int n = blockIdx.x;
   const int hw = a.h * a.w;
