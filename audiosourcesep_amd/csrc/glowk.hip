@@ -26,7 +26,7 @@ int num_cus() {
 void launch_fail(const std::string& m) { fail(m); }
 static EnvSwitches read_env() {
   auto on = [](const char* n) { return getenv(n) != nullptr; };
-  return EnvSwitches{on("GLOWK_BWD_LIGHT_4"), on("GLOWK_NO_FUSE"), on("GLOWK_WGRAD_PLAIN"), on("GLOWK_CO_OFF"), on("GLOWK_Q_OFF"), on("GLOWK_CO_TRAIN_OFF"),
+  return EnvSwitches{on("GLOWK_BWD_LIGHT_4"), on("GLOWK_NO_FUSE"), on("GLOWK_WGRAD_PLAIN"), on("GLOWK_CO_OFF"), on("GLOWK_CO_RING3"), on("GLOWK_Q_OFF"), on("GLOWK_CO_TRAIN_OFF"),
                      on("GLOWK_TRAIN_RECOMPUTE"), on("GLOWK_TRAIN_PERSTEP"), on("GLOWK_PG_JOIN")};
 }
 static EnvSwitches g_env = read_env();

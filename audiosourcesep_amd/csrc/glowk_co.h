@@ -31,6 +31,33 @@
 // their hidden tensors planar (NetArgs::st1 / st2) -- lane n of a wave then holds the ADJACENT pixels 2 n, 2 n + 1 (not n, 16 + n), so
 // that the values leave as 8-byte pairs, one full 128-byte line per hidden row and instruction; the stores are counted into the op-end
 // waits (they stay in flight across a barrier), which is why the host takes the form only where every wave is full (Q % 128 == 0).
+//
+// DOUBLE-BUFFERED ring (RingC::DB: the fused plain forward launches, MODE | NET_FUSE with NET_FWD / NET_FWD2 and 36 output rows, both
+// passes in one workgroup; every NF).  The three-slot ring above is that shallow, with three barriers per hidden block, only because
+// the fused form also held an LDS copy of P (36 x CO_PSTR floats), which is written in the very last ops alone.  Here P goes into unit
+// slots that are dead by then, a fourth slot fits beside two workgroups per CU, and the ring is a plain double buffer of PAIRS:
+// block i reads (S0, S1) when i is even and (S2, S3) when i is odd; S0 / S2 hold first halves.  Per pass
+//     X_i         reads K[i & 1]    issues nothing                                              ends: vmcnt(0) lgkmcnt(0), barrier
+//     Y_i         reads its pair    the two units of block i + 1 -> the other pair, one piece per MFMA group;
+//                 (Ya_i then Yb_i,  conv1 operands of block i + 2 -> K[i & 1]                   ends: nothing
+//                  no barrier)      Y_{NF-1}: conv3 units 0, 1 -> S0, S1                        ends: vmcnt(0) lgkmcnt(0), barrier
+//     Z_0         reads S0          conv3 unit 2 -> S2                                          ends: lgkmcnt(0), barrier
+//     Z_1         reads S1          pass 0: the next pass's unit 0 -> S0                        ends: vmcnt(PPW or 0) lgkmcnt(0), barrier
+//     Z_2         reads S2          pass 0: the next pass's unit 1 -> S1                        ends: lgkmcnt(0), barrier (last pass: the
+//                                                                                                     barrier in front of fused_couple)
+// One barrier per hidden block, no counted wait in the loop, and a unit has the rest of its Y and the next X to land.  The per-wave
+// MFMA order is that of the three-slot ring: results are bit for bit the same (GLOWK_CO_RING3=1 launches the three-slot instance,
+// which stays compiled as k_net_h3c<..., RING3 = true>).
+// P: the last pass's closing tiles write row tile 0 (rows 0-15) to S0, tile 1 to S1, tile 2 (rows 32-35) to S3, [16][CO_PSTR] floats
+// each.  By then S0 was last read in Z_0, S1 in Z_1, S3 in Y_{NF-1}, each behind a barrier, and a last pass issues no DMA into them
+// (its Z_1 ends with vmcnt(0)).  A slot is therefore max(unit, P tile) bytes: 16 KiB at F = 512, 9 KiB at F <= 256.
+// Invariants:
+//   - a DMA into a slot is issued only after a barrier that every wave passes after its last read of that slot;
+//   - a slot is read only after a barrier that every wave passes after its own wait for that slot's pieces;
+//   - every op end that precedes a refill is s_waitcnt ... lgkmcnt(0) + the raw s_barrier (an LDS read still in
+//     flight when the wave passes the barrier would race the refill);
+//   - no memory operation with a VGPR destination while a DMA is in flight (glowk_kernels.h, rule 2): the im2col gather and the
+//     vstash / epl loads stay in the prologue.
 #pragma once
 #include "glowk_kernels.h"
 
@@ -58,6 +85,11 @@ struct RingC {
   static constexpr int MASKN = BWD ? 2 * 4 * NF * 64 : 0;   // backward: LDS copy of the masks [mask1 | mask2][wave][hidden block][lane], entries
   static constexpr size_t LDS_BYTES = (size_t)3 * UNIT4 * 16 + (size_t)2 * S::K14 * 16 + (size_t)EPN * 4 + (size_t)MASKN * 2 +
                                       (FUSE ? (size_t)36 * CO_PSTR * 4 + CO_PX * 16 : 0);
+  // the double-buffered ring (header): four slots, each a unit or a 16-row tile of P, whichever is larger (whole 1-KiB pieces)
+  static constexpr bool DB = FUSE && (MODE7 == NET_FWD || MODE7 == NET_FWD2) && MOUT == 36;
+  static constexpr int PTILE4 = (16 * CO_PSTR * 4 + 1023) / 1024 * 64;
+  static constexpr int DBSLOT4 = UNIT4 > PTILE4 ? UNIT4 : PTILE4;
+  static constexpr size_t LDS_BYTES_DB = (size_t)4 * DBSLOT4 * 16 + (size_t)2 * S::K14 * 16 + (size_t)EPN * 4 + CO_PX * 16;
   static constexpr bool FITS = (MODE7 == NET_FWD || MODE7 == NET_FWD2 || SAVE || BWD) && !(MODE & NET_HALF) && (!STORE || ((SAVE || BWD) && !FUSE)) && S::NGRP == 1 && (NMT == 2 || NMT == 3 || (NMT == 5 && !STORE && !BWD)) &&
                                (!FUSE || (MOUT == 36 && !BWD)) && KS <= 3 && NF % 4 == 0 && NFH >= 2 && NFH % 2 == 0 && UNITP % 4 == 0 && PPW == NG &&
                                2 * LDS_BYTES <= 160 * 1024 + 1;   // (diagnostic paddings aside)
@@ -292,7 +324,158 @@ __device__ __forceinline__ void co_pass(const NetArgs& a, const H3Ctx& hc, const
   if constexpr (G::NMT >= 5) co_Z<KIN, MOUT, NF, MODE, PASS, SOLO, 4>(a, hc, c, epl, pl, acc2, acc3, bh, bl, q, qok, lane, kq, keep);
 }
 
-template <int KIN, int MOUT, int NF, int MODE, bool SPLIT>
+// ---- the double-buffered ring (RingC::DB; header comment) ----------------------------------------------------------------------
+struct CoCtxDB {
+  float4 *s0, *s1, *s2, *s3;   // unit slots (distinct static __shared__ arrays): block i reads (s0, s1) when i is even, (s2, s3) when odd
+  const float4* img;
+  int w4;
+  unsigned voff;
+};
+
+// Y of one hidden block: co_Y's two halves back to back (row blocks 0 .. NFH-1 from `sa`, NFH .. 2 NFH - 1 from `sb`), the A-fragment
+// prefetch running across the boundary; one piece of this wave's share of the next block's units per group (first half: srca -> dsta,
+// second: srcb -> dstb) and the conv1 operands of a later block in the first group
+template <int NFH, int MODE7, int TAG, int K1P>
+__device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const h8 (&bh)[2], const h8 (&bl)[2], f32x4 (&acc2)[2 * NFH][2], int lane,
+                                       const float4* srca, float4* dsta, const float4* srcb, float4* dstb, const float4* k1src, float4* k1dst,
+                                       int w4, unsigned voff) {
+  const h8* bufa = reinterpret_cast<const h8*>(sa) + lane;
+  const h8* bufb = reinterpret_cast<const h8*>(sb) + lane;
+  const char* uba = uniform_ptr(srca);
+  const char* ubb = uniform_ptr(srcb);
+  constexpr int NG = NFH / 2;
+  h8 A[2][4];
+  auto load = [&](h8 (&d)[4], int g) {
+    const h8* buf = g < NG ? bufa : bufb;
+    const int gi = g % NG;
+    d[0] = buf[((2 * gi) * 2 + 0) * 64];            // row block 2gi hi, lo; row block 2gi+1 hi, lo
+    d[1] = buf[((2 * gi) * 2 + 1) * 64];
+    d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
+    d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
+  };
+  load(A[0], 0);
+#pragma unroll
+  for (int g = 0; g < 2 * NG; ++g) {
+    const int gi = g % NG;
+    const int o0 = (g / NG) * NFH + 2 * gi, o1 = o0 + 1;
+    if (g + 1 < 2 * NG) load(A[(g + 1) & 1], g + 1);
+    const int piece = gi * 4 + w4;
+    if (g < NG) glds16(reinterpret_cast<const float4*>(uba + (size_t)piece * 1024 + voff), dsta + piece * 64);
+    else glds16(reinterpret_cast<const float4*>(ubb + (size_t)piece * 1024 + voff), dstb + piece * 64);
+    asm volatile("; dma site %0" ::"n"(TAG * 16 + g));
+    if (g == 0) stage4<K1P, TAG * 16 + 15>(k1src, k1dst, w4, voff);
+    __builtin_amdgcn_sched_barrier(0);
+    const h8 (&af)[4] = A[g & 1];
+    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], acc2[o0][0], 0, 0, 0);
+    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
+    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
+    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
+    if (MODE7 != NET_FWD2) {
+      acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
+      acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
+      acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], acc2[o1][0], 0, 0, 0);
+      acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[1], acc2[o1][1], 0, 0, 0);
+    }
+    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[0], acc2[o0][0], 0, 0, 0);
+    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[1], acc2[o0][1], 0, 0, 0);
+    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[0], acc2[o1][0], 0, 0, 0);
+    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Z: conv3 unit Z of a pass (co_Z's tiles and arithmetic; three units, merged passes, fused).  Pass 0 keeps its sums in `keep`; the
+// last pass writes P's row tile ml into the dead slot S0 / S1 / S3.
+template <int KIN, int MOUT, int NF, int MODE, int PASS, int Z>
+__device__ __forceinline__ void co_Zdb(const NetArgs& a, const CoCtxDB& c, const float* epl, f32x4 (&acc2)[(RingC<KIN, MOUT, NF, MODE>::NRB)][2],
+                                       f32x4 (&acc3)[3][2], h8 (&bh)[2], h8 (&bl)[2], int lane, int kq, f32x4 (&keep)[3][2]) {
+  using G = RingC<KIN, MOUT, NF, MODE>;
+  constexpr int NFH = G::NFH, NMT = G::NMT, M3 = MOUT, MODE7 = G::MODE7;
+  static_assert(NMT == 3 && G::MERGE && G::FUSE, "the double-buffered ring: three conv3 units, merged passes, fused coupling");
+  constexpr bool NEXT = PASS == 0;                     // another pass follows in this workgroup
+  if constexpr (Z == 0) stage4<G::UNITP, 90>(G::out_unit(c.img, PASS, 2), c.s2, c.w4, c.voff);
+  if constexpr (Z == 1 && NEXT) stage4<G::UNITP, 91>(G::main_unit(c.img, PASS + 1, 0, 0), c.s0, c.w4, c.voff);
+  if constexpr (Z == 2 && NEXT) stage4<G::UNITP, 92>(G::main_unit(c.img, PASS + 1, 0, 1), c.s1, c.w4, c.voff);
+  const float4* slot = Z == 0 ? c.s0 : Z == 1 ? c.s1 : c.s2;
+  const h8* buf = reinterpret_cast<const h8*>(slot) + lane;
+  const float* pb = epl + NF * 32;
+#pragma unroll
+  for (int tp = 0; tp < NFH; ++tp) {
+    const int t = Z * NFH + tp;
+    const int fo = t / NMT, ml = t % NMT;
+    if (ml == 0) {
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, 0u, bh[hf], bl[hf]);
+    }
+    if (fo == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { acc3[ml][0][r] = 0.0f; acc3[ml][1][r] = 0.0f; }
+    }
+    const h8 ah = buf[(tp * 2 + 0) * 64], al = buf[(tp * 2 + 1) * 64];
+    acc3[ml][0] = mfma3s<MODE7 == NET_FWD2>(ah, al, bh[0], bl[0], acc3[ml][0]);
+    acc3[ml][1] = mfma3s<MODE7 == NET_FWD2>(ah, al, bh[1], bl[1], acc3[ml][1]);
+    if (fo == NFH - 1) {
+      float* pt = reinterpret_cast<float*>(ml == 0 ? c.s0 : ml == 1 ? c.s1 : c.s3);      // (NFH = 2: tile 0 closes in Z_1, behind Z_0's barrier)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = ml * 16 + 4 * kq + r;
+          const float part = PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[m]) : acc3[ml][hf][r] * a.sc3;
+          if constexpr (NEXT) { keep[ml][hf][r] = part; continue; }
+          const float val = part + keep[ml][hf][r];
+          if (m < M3) pt[(4 * kq + r) * CO_PSTR + (int)(threadIdx.x >> 6) * 32 + 16 * hf + (lane & 15)] = val;
+        }
+    }
+  }
+  if constexpr (Z == 0) co_bar();                      // (conv3 unit 2 is Z_2's: it has Z_1 to land)
+  if constexpr (Z == 1) co_end<(NEXT ? G::PPW : 0)>();  // conv3 unit 2 landed; the next pass's unit 0 may still be in flight
+  if constexpr (Z == 2 && NEXT) co_bar();              // (last pass: the barrier in front of fused_couple)
+}
+
+template <int KIN, int MOUT, int NF, int MODE, int PASS>
+__device__ __forceinline__ void co_pass_db(const NetArgs& a, const H3Ctx& hc, const CoCtxDB& c, const float* epl,
+                                           const h8 (&xh)[(RingC<KIN, MOUT, NF, MODE>::KS)][2], const h8 (&xl)[(RingC<KIN, MOUT, NF, MODE>::KS)][2],
+                                           int lane, int kq, f32x4 (&keep)[3][2]) {
+  using G = RingC<KIN, MOUT, NF, MODE>;
+  using S = typename G::S;
+  constexpr int NRB = G::NRB, NFH = G::NFH, MODE7 = G::MODE7;
+  constexpr int f2base = PASS * NFH * 32;
+  f32x4 acc2[NRB][2];
+#pragma unroll
+  for (int ob = 0; ob < NRB; ++ob)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float b = epl[f2base + ob * 16 + 4 * kq + r];   // conv2 bias (scaled)
+      acc2[ob][0][r] = b;
+      acc2[ob][1][r] = b;
+    }
+  h8 bh[2], bl[2];
+#pragma nounroll
+  for (int i0 = 0; i0 < NF; i0 += 2) {
+    // ---- hidden block i0: conv1 operands in K0, units in (S0, S1) -- the prologue's, or the previous pass's Z_1 / Z_2's
+    h3s_X<KIN, MOUT, NF, G::MODEX, 2, 0, PASS, false>(a, hc, i0, xh, xl, lane, bh, bl);
+    co_end<0>();                                        // this wave's pieces of block i0's units and of K1 have landed; its reads of (S2, S3), K0 retired
+    co_Ydb<NFH, MODE7, 1, S::K1P>(c.s0, c.s1, bh, bl, acc2, lane, G::main_unit(c.img, PASS, i0 + 1, 0), c.s2, G::main_unit(c.img, PASS, i0 + 1, 1), c.s3,
+                                  hc.k1img + (size_t)((i0 + 2) % NF) * S::K14, hc.k1s0, c.w4, c.voff);
+    // ---- hidden block i0 + 1: conv1 operands in K1, units in (S2, S3)
+    h3s_X<KIN, MOUT, NF, G::MODEX, 2, 1, PASS, false>(a, hc, i0 + 1, xh, xl, lane, bh, bl);
+    co_end<0>();
+    // (after the last block: conv3 units 0, 1 take the place of "block NF")
+    const bool more = i0 + 2 < NF;
+    co_Ydb<NFH, MODE7, 2, S::K1P>(c.s2, c.s3, bh, bl, acc2, lane, more ? G::main_unit(c.img, PASS, i0 + 2, 0) : G::out_unit(c.img, PASS, 0), c.s0,
+                                  more ? G::main_unit(c.img, PASS, i0 + 2, 1) : G::out_unit(c.img, PASS, 1), c.s1,
+                                  hc.k1img + (size_t)((i0 + 3) % NF) * S::K14, hc.k1s1, c.w4, c.voff);
+  }
+  co_end<0>();                                          // Y_{NF-1}: conv3 units 0, 1 landed
+  f32x4 acc3[3][2];
+  co_Zdb<KIN, MOUT, NF, MODE, PASS, 0>(a, c, epl, acc2, acc3, bh, bl, lane, kq, keep);
+  co_Zdb<KIN, MOUT, NF, MODE, PASS, 1>(a, c, epl, acc2, acc3, bh, bl, lane, kq, keep);
+  co_Zdb<KIN, MOUT, NF, MODE, PASS, 2>(a, c, epl, acc2, acc3, bh, bl, lane, kq, keep);
+}
+
+// RING3: the three-slot ring where the instance also has the double-buffered one (GLOWK_CO_RING3: parity tests, in-process A/B)
+template <int KIN, int MOUT, int NF, int MODE, bool SPLIT, bool RING3 = false>
 __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   using G = RingC<KIN, MOUT, NF, MODE>;
   using S = typename G::S;
@@ -300,26 +483,37 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   constexpr int SGN = G::BWD ? -1 : 1;                 // backward gathers at q - d(tap)
   static_assert(G::FITS, "shape");
   static_assert(!(G::FUSE && SPLIT), "the fused coupling needs both passes in one workgroup");
+  constexpr bool DB = G::DB && !SPLIT && !RING3;       // the double-buffered ring
+  static_assert(!RING3 || G::DB, "RING3 names the three-slot form of an instance that has both");
+  static_assert(!DB || 2 * G::LDS_BYTES_DB <= 160 * 1024, "two workgroups per CU");
 
   const int tid = threadIdx.x;
   // (aligned 1024: the LDS layout is sorted by alignment first, so the DMA targets take the lowest addresses and the fused form's
   //  copy of P the highest)
-  __shared__ __attribute__((aligned(1024))) float4 slotM0[G::UNIT4];
-  __shared__ __attribute__((aligned(1024))) float4 slotM1[G::UNIT4];
-  __shared__ __attribute__((aligned(1024))) float4 slotD[G::UNIT4];
+  CoCtx c;
+  CoCtxDB cd;
+  if constexpr (DB) {
+    __shared__ __attribute__((aligned(1024))) float4 slotS0[G::DBSLOT4];
+    __shared__ __attribute__((aligned(1024))) float4 slotS1[G::DBSLOT4];
+    __shared__ __attribute__((aligned(1024))) float4 slotS2[G::DBSLOT4];
+    __shared__ __attribute__((aligned(1024))) float4 slotS3[G::DBSLOT4];
+    cd.s0 = slotS0; cd.s1 = slotS1; cd.s2 = slotS2; cd.s3 = slotS3;
+  } else {
+    __shared__ __attribute__((aligned(1024))) float4 slotM0[G::UNIT4];
+    __shared__ __attribute__((aligned(1024))) float4 slotM1[G::UNIT4];
+    __shared__ __attribute__((aligned(1024))) float4 slotD[G::UNIT4];
+    c.m0 = slotM0; c.m1 = slotM1; c.d = slotD;
+  }
   __shared__ __attribute__((aligned(1024))) float4 k1slot0[S::K14];
   __shared__ __attribute__((aligned(1024))) float4 k1slot1[S::K14];
   float* epl = nullptr;                                 // conv2 accumulator init | per-row constants of P (forward modes)
   if constexpr (!G::BWD) { __shared__ float epl_arr[S::EPN]; epl = epl_arr; }
   unsigned short* mkl = nullptr;                        // backward: the forward pass's ReLU decisions of the workgroup's four 32-pixel blocks
   if constexpr (G::BWD) { __shared__ __attribute__((aligned(1024))) unsigned short mkl_arr[G::MASKN]; mkl = mkl_arr; }
-  float* plds = nullptr;                                // fused coupling: the workgroup's per-tap outputs ...
+  float* plds = nullptr;                                // fused coupling: the workgroup's per-tap outputs (double-buffered ring: in dead slots) ...
   float4* vstash = nullptr;                             // ... and its pixels' four input channels
-  if constexpr (G::FUSE) {
-    __shared__ float plds_arr[36 * CO_PSTR];
-    __shared__ float4 vstash_arr[CO_PX];
-    plds = plds_arr; vstash = vstash_arr;
-  }
+  if constexpr (G::FUSE && !DB) { __shared__ float plds_arr[36 * CO_PSTR]; plds = plds_arr; }
+  if constexpr (G::FUSE) { __shared__ float4 vstash_arr[CO_PX]; vstash = vstash_arr; }
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = lane & 15;
@@ -336,12 +530,17 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   hc.wblk = (size_t)blockIdx.x * 4 + wave;             // this wave's 32-pixel block: the unit of the ReLU-mask arrays
   hc.wok = (long)hc.wblk * 32 < a.Q;
   hc.w4 = wave; hc.voff = (unsigned)lane * 16u; hc.ub[0] = hc.ub[1] = 1.0f;
-  CoCtx c;
-  c.m0 = slotM0; c.m1 = slotM1; c.d = slotD; c.img = a.RSp; c.w4 = wave; c.voff = (unsigned)lane * 16u;
+  c.img = a.RSp; c.w4 = wave; c.voff = (unsigned)lane * 16u;
+  cd.img = a.RSp; cd.w4 = wave; cd.voff = (unsigned)lane * 16u;
 
-  stage4<G::UNITP, 60>(G::main_unit(c.img, pass0, 0, 0), slotM0, c.w4, c.voff);
-  stage4<G::UNITP, 61>(G::main_unit(c.img, pass0, 0, 1), slotM1, c.w4, c.voff);
-  stage4<G::UNITP, 62>(G::out_unit(c.img, pass0, 0), slotD, c.w4, c.voff);
+  if constexpr (DB) {          // block 0's pair
+    stage4<G::UNITP, 58>(G::main_unit(cd.img, 0, 0, 0), cd.s0, c.w4, c.voff);
+    stage4<G::UNITP, 59>(G::main_unit(cd.img, 0, 0, 1), cd.s1, c.w4, c.voff);
+  } else {
+    stage4<G::UNITP, 60>(G::main_unit(c.img, pass0, 0, 0), c.m0, c.w4, c.voff);
+    stage4<G::UNITP, 61>(G::main_unit(c.img, pass0, 0, 1), c.m1, c.w4, c.voff);
+    stage4<G::UNITP, 62>(G::out_unit(c.img, pass0, 0), c.d, c.w4, c.voff);
+  }
   stage4<S::K1P, 63>(hc.k1img, k1slot0, c.w4, c.voff);
   stage4<S::K1P, 64>(hc.k1img + S::K14, k1slot1, c.w4, c.voff);
   if constexpr (G::BWD) {      // [mask1 | mask2][wave][hidden block][lane]: 4 NF 64 entries = NF / 2 pieces each
@@ -408,14 +607,19 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
   __syncthreads();
 
   f32x4 keep[G::NMT][2];
-  if constexpr (SPLIT) {
+  if constexpr (DB) {
+    co_pass_db<KIN, MOUT, NF, MODE, 0>(a, hc, cd, epl, xh, xl, lane, kq, keep);
+    co_pass_db<KIN, MOUT, NF, MODE, 1>(a, hc, cd, epl, xh, xl, lane, kq, keep);
+    __syncthreads();       // every wave's LDS writes of P are complete and visible (lgkmcnt(0) + barrier)
+    fused_couple<CO_PX, CO_PSTR>(a, reinterpret_cast<const float*>(cd.s0), reinterpret_cast<const float*>(cd.s1), reinterpret_cast<const float*>(cd.s3), vstash, tid);
+  } else if constexpr (SPLIT) {
     if (pass0 == 0) co_pass<KIN, MOUT, NF, MODE, 0, true>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
     else co_pass<KIN, MOUT, NF, MODE, 1, true>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
   } else {
     co_pass<KIN, MOUT, NF, MODE, 0, false>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
     co_pass<KIN, MOUT, NF, MODE, 1, false>(a, hc, c, epl, plds, xh, xl, q, qok, lane, kq, keep);
   }
-  if constexpr (G::FUSE) {
+  if constexpr (G::FUSE && !DB) {
     __syncthreads();       // every wave's LDS writes of P are complete and visible (lgkmcnt(0) + barrier)
     fused_couple<CO_PX, CO_PSTR>(a, plds, vstash, tid);
   }

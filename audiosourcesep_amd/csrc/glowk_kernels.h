@@ -1512,8 +1512,11 @@ __device__ __forceinline__ void h3s_passes(const NetArgs& a, const H3Ctx& c, con
 __device__ __forceinline__ bool fz_not_finite(float v) { return !(fabsf(v) <= 3.0e38f); }
 
 // PXW = pixels per workgroup (256: k_net_h3s; 128: the co-resident form k_net_h3c, glowk_co.h), PSTR = floats per LDS row of P
+// pl0 / pl1 / pl2: the 16-row tiles of P (rows 0-15, 16-31, 32-35), each [rows][PSTR] -- one array, or (k_net_h3c's double-buffered ring)
+// three weight slots that are dead by then.  Channel rows 4 tap + {k, 2 + k} lie in tile tap / 4: static in the unrolled tap loop.
+__device__ __forceinline__ const float* fz_tile(const float* pl0, const float* pl1, const float* pl2, int tile) { return tile == 0 ? pl0 : tile == 1 ? pl1 : pl2; }
 template <int PXW = 256, int PSTR = FUSE_PSTR>
-__device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, const float4* vst, int tid) {
+__device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl0, const float* pl1, const float* pl2, const float4* vst, int tid) {
   const int wave = tid >> 6, lane = tid & 63;
   const int px = wave * 32 + (lane & 31), k = lane >> 5;
   const int q = (int)blockIdx.x * PXW + px;
@@ -1531,8 +1534,9 @@ __device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, 
     const int rr = r + dy;
     if (rr < 0 || rr >= nrows) { missing = true; continue; }      // that row belongs to another workgroup
     const int spx = px + dy * w + dx;
-    ols += pl[(tap * 4 + k) * PSTR + spx];
-    ot += pl[(tap * 4 + 2 + k) * PSTR + spx];
+    const float* pt = fz_tile(pl0, pl1, pl2, tap / 4) + (tap % 4) * 4 * PSTR;
+    ols += pt[k * PSTR + spx];
+    ot += pt[(2 + k) * PSTR + spx];
   }
   ols += a.fz_b3[k];
   ot += a.fz_b3[2 + k];
@@ -1580,7 +1584,7 @@ __device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, 
       const int js = jt + dx;
       if (js < 0 || js >= w) continue;
       const int tap = (which ? 0 : 6) + dx + 1;
-      hsum += pl[(tap * 4 + ch) * PSTR + (which ? (nrows - 1) * w : 0) + js];
+      hsum += fz_tile(pl0, pl1, pl2, tap / 4)[((tap % 4) * 4 + ch) * PSTR + (which ? (nrows - 1) * w : 0) + js];
     }
     a.fz_edge[(((size_t)blockIdx.x * 4 + 2 + which) * FUSE_EW + jt) * 4 + ch] = hsum;
   }
@@ -1592,6 +1596,11 @@ __device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, 
     for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o, 64);
     if (lane == 0) a.fz_ldpart[(size_t)blockIdx.x * (PXW / 32) + wave] = d;
   }
+}
+
+template <int PXW = 256, int PSTR = FUSE_PSTR>
+__device__ __forceinline__ void fused_couple(const NetArgs& a, const float* pl, const float4* vst, int tid) {
+  fused_couple<PXW, PSTR>(a, pl, pl + 16 * PSTR, pl + 32 * PSTR, vst, tid);
 }
 
 template <int KIN, int MOUT, int NF, int MODE, int NP, bool SPLIT>

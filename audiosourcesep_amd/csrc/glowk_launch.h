@@ -50,6 +50,7 @@ struct EnvSwitches {
   bool no_fuse;             // GLOWK_NO_FUSE: network + coupling as two kernels at the 4-channel level
   bool wgrad_plain;         // GLOWK_WGRAD_PLAIN: the weight-gradient GEMM's plain (not fenced) round
   bool co_off;              // GLOWK_CO_OFF: never the co-resident (two workgroups per CU) form of the forward network
+  bool co_ring3;            // GLOWK_CO_RING3: the fused co-resident launches keep the three-slot weight ring (glowk_co.h: RingC::DB)
   bool q_off;               // GLOWK_Q_OFF: never the all-conv1-first small-grid form (glowk_q.h)
   bool co_train_off;        // GLOWK_CO_TRAIN_OFF: the training sweep stays on the 32x32x16 family
   bool train_recompute;     // GLOWK_TRAIN_RECOMPUTE: the training sweep recomputes each step's forward pass instead of keeping it
@@ -145,6 +146,13 @@ NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
         if constexpr (RingC<KIN, MOUT, NF, MODE | NET_FUSE>::FITS) {
           // (the form only pays with TWO workgroups per CU -- 2 x 78.8 KB of LDS, 2 x 4 x 248 VGPRs: ask the runtime once per instance, and
           //  keep the eight-wave kernel where a driver / device leaves room for one)
+          // (plain forward directions: the double-buffered ring, RingC::DB, unless GLOWK_CO_RING3 asks for the three-slot instance)
+          if constexpr (RingC<KIN, MOUT, NF, MODE | NET_FUSE>::DB) {
+            if (a.fuse && env().co_ring3 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false, true>)) {
+              if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false, true>), dim3(wgc), dim3(256), 0, s, a);
+              return {0, FAM_FUSED, true, false, CO_PX};
+            }
+          }
           if (a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>)) {
             if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>), dim3(wgc), dim3(256), 0, s, a);
             return {0, FAM_FUSED, true, false, CO_PX};

@@ -116,7 +116,7 @@ enum glowk_range_policy { GLOWK_RANGE_IGNORE = 0, GLOWK_RANGE_ERROR = 1, GLOWK_R
 
 int glowk_version(void);
 const char* glowk_last_error(void);
-/* Diagnostic switches (environment variables GLOWK_NO_FUSE, GLOWK_CO_OFF, GLOWK_BWD_LIGHT_4, ...: one launch form forced for a
+/* Diagnostic switches (environment variables GLOWK_NO_FUSE, GLOWK_CO_OFF, GLOWK_CO_RING3, GLOWK_BWD_LIGHT_4, ...: one launch form forced for a
  * form-against-form parity test; none is needed for normal use) are read when the library is loaded, not per launch; a process
  * that changes its environment afterwards calls this to have them read again.  (No reference counterpart.) */
 void glowk_reload_env(void);
