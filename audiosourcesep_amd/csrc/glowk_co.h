@@ -37,17 +37,32 @@
 // the fused form also held an LDS copy of P (36 x CO_PSTR floats), which is written in the very last ops alone.  Here P goes into unit
 // slots that are dead by then, a fourth slot fits beside two workgroups per CU, and the ring is a plain double buffer of PAIRS:
 // block i reads (S0, S1) when i is even and (S2, S3) when i is odd; S0 / S2 hold first halves.  Per pass
-//     X_i         reads K[i & 1]    issues nothing                                              ends: vmcnt(0) lgkmcnt(0), barrier
-//     Y_i         reads its pair    the two units of block i + 1 -> the other pair, one piece per MFMA group;
-//                 (Ya_i then Yb_i,  conv1 operands of block i + 2 -> K[i & 1]                   ends: nothing
-//                  no barrier)      Y_{NF-1}: conv3 units 0, 1 -> S0, S1                        ends: vmcnt(0) lgkmcnt(0), barrier
+//     X_i         conv1 MFMAs on operands that are already in registers (kf), then vmcnt(0) lgkmcnt(0) + the block's barrier, then the reads
+//                 of Y_i's first A group from the block's pair, then ReLU + split -- the block's VALU work -- while those reads return;
+//                 issues nothing.  kf of block 0 is read in front of the pass (K0 was published long before)
+//     Y_i         reads its pair (Ya_i then Yb_i, no barrier between; the A-fragment prefetch runs across).  Each group of 12 MFMAs issues the
+//                 next group's reads BEHIND its first four MFMAs -- the last group reads kf of block i + 1 from K[(i + 1) & 1] instead.
+//                 Issues, in the groups of its FIRST half, one piece of each of the two units of block i + 1 -> the other pair, and in
+//                 group 0 the conv1 operands of block i + 2 -> K[i & 1]; Y_{NF-1}: conv3 units 0, 1 -> S0, S1.      ends: nothing
+//                                                                                    (Y_{NF-1}: vmcnt(0) lgkmcnt(0), barrier)
 //     Z_0         reads S0          conv3 unit 2 -> S2                                          ends: lgkmcnt(0), barrier
 //     Z_1         reads S1          pass 0: the next pass's unit 0 -> S0                        ends: vmcnt(PPW or 0) lgkmcnt(0), barrier
 //     Z_2         reads S2          pass 0: the next pass's unit 1 -> S1                        ends: lgkmcnt(0), barrier (last pass: the
 //                                                                                                     barrier in front of fused_couple)
-// One barrier per hidden block, no counted wait in the loop, and a unit has the rest of its Y and the next X to land.  The per-wave
-// MFMA order is that of the three-slot ring: results are bit for bit the same (GLOWK_CO_RING3=1 launches the three-slot instance,
-// which stays compiled as k_net_h3c<..., RING3 = true>).
+// One barrier per hidden block, no counted wait in the loop.  No LDS read is waited for right after it is issued: while a DMA is in
+// flight the compiler's wait in front of an MFMA that needs LDS data is always lgkmcnt(0), so every read is issued eight MFMAs (two-term
+// mode: four), or the activation (group 0), in front of the MFMA that needs it, and nothing younger is outstanding at that wait.  A unit's last
+// piece leaves in the middle of Y_{i-1} and has its second half and X_i's MFMAs to land.  The per-wave MFMA order is that of the
+// three-slot ring: results are bit for bit the same (GLOWK_CO_RING3=1 launches the three-slot instance, which stays compiled as
+// k_net_h3c<..., RING3 = true>).
+// The block's barrier, checked against the invariants below:
+//   - it follows every wave's last read of the other pair (Y_{i-1}: consumed by that Y's MFMAs) and of K[i & 1] (kf: consumed by X_i's
+//     MFMAs); lgkmcnt(0) retires them;
+//   - Y_i's DMAs into the other pair and into K[i & 1] come behind it (behind group 0's first four MFMAs);
+//   - the reads of pair i (X_i's A group, Y_i) come behind it, and it follows each wave's own vmcnt(0) for the pieces of pair i and of
+//     K[(i + 1) & 1] (issued in Y_{i-1}); K[(i + 1) & 1] is read at the end of Y_i and not written again before Y_{i+1}, behind the
+//     next barrier.  Block 0: the prologue's (pass 1: Z_1 / Z_2's and Y_{NF-1}'s) pieces, waited for at the same place;
+//   - the last Y of a pass reads K0 (block 0's operands, valid) into kf and drops them.
 // P: the last pass's closing tiles write row tile 0 (rows 0-15) to S0, tile 1 to S1, tile 2 (rows 32-35) to S3, [16][CO_PSTR] floats
 // each.  By then S0 was last read in Z_0, S1 in Z_1, S3 in Y_{NF-1}, each behind a barrier, and a last pass issues no DMA into them
 // (its Z_1 ends with vmcnt(0)).  A slot is therefore max(unit, P tile) bytes: 16 KiB at F = 512, 9 KiB at F <= 256.
@@ -333,18 +348,20 @@ struct CoCtxDB {
 };
 
 // Y of one hidden block: co_Y's two halves back to back (row blocks 0 .. NFH-1 from `sa`, NFH .. 2 NFH - 1 from `sb`), the A-fragment
-// prefetch running across the boundary; one piece of this wave's share of the next block's units per group (first half: srca -> dsta,
-// second: srcb -> dstb) and the conv1 operands of a later block in the first group
-template <int NFH, int MODE7, int TAG, int K1P>
+// prefetch running across the boundary.  Group 0's fragments arrive in A[0] (read by the X in front, behind its barrier); the last group,
+// which has no next group to read, reads the NEXT block's conv1 operands from `kslot` into kf instead.  This wave's share of the next
+// block's units goes out in the first half, one piece of each unit per group (srca -> dsta, srcb -> dstb), so that the last piece has
+// the second half of Y and the next X's MFMAs to land; the conv1 operands of a later block in the first group
+template <int NFH, int MODE7, int TAG, int K1P, int NKF>
 __device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const h8 (&bh)[2], const h8 (&bl)[2], f32x4 (&acc2)[2 * NFH][2], int lane,
-                                       const float4* srca, float4* dsta, const float4* srcb, float4* dstb, const float4* k1src, float4* k1dst,
-                                       int w4, unsigned voff) {
+                                       h8 (&A)[2][4], h8 (&kf)[NKF], const float4* kslot, const float4* srca, float4* dsta, const float4* srcb,
+                                       float4* dstb, const float4* k1src, float4* k1dst, int w4, unsigned voff) {
   const h8* bufa = reinterpret_cast<const h8*>(sa) + lane;
   const h8* bufb = reinterpret_cast<const h8*>(sb) + lane;
+  const h8* kbuf = reinterpret_cast<const h8*>(kslot) + lane;
   const char* uba = uniform_ptr(srca);
   const char* ubb = uniform_ptr(srcb);
   constexpr int NG = NFH / 2;
-  h8 A[2][4];
   auto load = [&](h8 (&d)[4], int g) {
     const h8* buf = g < NG ? bufa : bufb;
     const int gi = g % NG;
@@ -353,23 +370,33 @@ __device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const
     d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
     d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
   };
-  load(A[0], 0);
 #pragma unroll
   for (int g = 0; g < 2 * NG; ++g) {
     const int gi = g % NG;
     const int o0 = (g / NG) * NFH + 2 * gi, o1 = o0 + 1;
-    if (g + 1 < 2 * NG) load(A[(g + 1) & 1], g + 1);
-    const int piece = gi * 4 + w4;
-    if (g < NG) glds16(reinterpret_cast<const float4*>(uba + (size_t)piece * 1024 + voff), dsta + piece * 64);
-    else glds16(reinterpret_cast<const float4*>(ubb + (size_t)piece * 1024 + voff), dstb + piece * 64);
-    asm volatile("; dma site %0" ::"n"(TAG * 16 + g));
-    if (g == 0) stage4<K1P, TAG * 16 + 15>(k1src, k1dst, w4, voff);
-    __builtin_amdgcn_sched_barrier(0);
     const h8 (&af)[4] = A[g & 1];
     acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], acc2[o0][0], 0, 0, 0);
     acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
     acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
     acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
+    // the reads and DMA of this group go out BEHIND its first four MFMAs: the wait the compiler puts in front of a group's first MFMA is
+    // always lgkmcnt(0) while a DMA is in flight, so reads issued in front of it would be waited for at once -- now it only finds reads
+    // that have had the rest of the previous group to return
+    __builtin_amdgcn_sched_barrier(0);
+    if (g + 1 < 2 * NG) load(A[(g + 1) & 1], g + 1);
+    else {
+#pragma unroll
+      for (int i = 0; i < NKF; ++i) kf[i] = kbuf[i * 64];
+    }
+    if (g < NG) {                                   // (PPW = NG pieces per wave and unit)
+      const int piece = g * 4 + w4;
+      glds16(reinterpret_cast<const float4*>(uba + (size_t)piece * 1024 + voff), dsta + piece * 64);
+      asm volatile("; dma site %0" ::"n"(TAG * 16 + g));
+      glds16(reinterpret_cast<const float4*>(ubb + (size_t)piece * 1024 + voff), dstb + piece * 64);
+      asm volatile("; dma site %0" ::"n"(TAG * 16 + NG + g));
+    }
+    if (g == 0) stage4<K1P, TAG * 16 + 15>(k1src, k1dst, w4, voff);
+    __builtin_amdgcn_sched_barrier(0);
     if (MODE7 != NET_FWD2) {
       acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
       acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
@@ -382,6 +409,28 @@ __device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const
     acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
+}
+
+// X of one hidden block in the double-buffered ring: the conv1 MFMAs on operands that are already in registers (kf: read under the end of
+// the previous Y, or in front of the pass), the block's wait and barrier, the reads of Y's first A group from the block's pair (`sa`),
+// and the activation -- the block's VALU work -- while those reads are in flight
+template <int KIN, int MOUT, int NF, int MODE>
+__device__ __forceinline__ void co_Xdb(const NetArgs& a, const h8 (&xh)[(RingC<KIN, MOUT, NF, MODE>::KS)][2], const h8 (&xl)[(RingC<KIN, MOUT, NF, MODE>::KS)][2],
+                                       int lane, const h8 (&kf)[(RingC<KIN, MOUT, NF, MODE>::S::KSX * 2)], const float4* sa, h8 (&A0)[4], h8 (&bh)[2],
+                                       h8 (&bl)[2]) {
+  using G = RingC<KIN, MOUT, NF, MODE>;
+  f32x4 h1[2][2];
+  h3s_X_mma<typename G::S>(kf, xh, xl, h1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(h1[i >> 1][i & 1]));      // (the MFMAs stay in front of the barrier: their results are only used behind it)
+  __builtin_amdgcn_sched_barrier(0);
+  co_end<0>();      // this wave's pieces of this block's units and of the other K slot have landed; its reads of the other pair and of kf retired
+  const h8* buf = reinterpret_cast<const h8*>(sa) + lane;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) A0[j] = buf[j * 64];      // row blocks 0, 1 (hi, lo): co_Ydb's group 0
+  __builtin_amdgcn_sched_barrier(0);
+  h3s_X_act<G::MODE7>(h1, a.sc1, bh, bl);
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 // Z: conv3 unit Z of a pass (co_Z's tiles and arithmetic; three units, merged passes, fused).  Pass 0 keeps its sums in `keep`; the
@@ -451,21 +500,24 @@ __device__ __forceinline__ void co_pass_db(const NetArgs& a, const H3Ctx& hc, co
       acc2[ob][1][r] = b;
     }
   h8 bh[2], bl[2];
+  constexpr int NKF = S::KSX * 2;      // conv1 operands: one register fragment per stacked k-step and row block
+  h8 A[2][4];        // co_Ydb's A fragments; [0] is filled by the X in front
+  h8 kf[NKF];        // conv1 operands of the next X: block 0's are read here (K0 was published long before), the others under the end of Y
+  h3s_X_load<S, 0>(hc, lane, kf);
+  __builtin_amdgcn_sched_barrier(0);
 #pragma nounroll
   for (int i0 = 0; i0 < NF; i0 += 2) {
-    // ---- hidden block i0: conv1 operands in K0, units in (S0, S1) -- the prologue's, or the previous pass's Z_1 / Z_2's
-    h3s_X<KIN, MOUT, NF, G::MODEX, 2, 0, PASS, false>(a, hc, i0, xh, xl, lane, bh, bl);
-    co_end<0>();                                        // this wave's pieces of block i0's units and of K1 have landed; its reads of (S2, S3), K0 retired
-    co_Ydb<NFH, MODE7, 1, S::K1P>(c.s0, c.s1, bh, bl, acc2, lane, G::main_unit(c.img, PASS, i0 + 1, 0), c.s2, G::main_unit(c.img, PASS, i0 + 1, 1), c.s3,
-                                  hc.k1img + (size_t)((i0 + 2) % NF) * S::K14, hc.k1s0, c.w4, c.voff);
-    // ---- hidden block i0 + 1: conv1 operands in K1, units in (S2, S3)
-    h3s_X<KIN, MOUT, NF, G::MODEX, 2, 1, PASS, false>(a, hc, i0 + 1, xh, xl, lane, bh, bl);
-    co_end<0>();
-    // (after the last block: conv3 units 0, 1 take the place of "block NF")
+    // ---- hidden block i0: conv1 operands from K0, units in (S0, S1) -- the prologue's, or the previous pass's Z_1 / Z_2's
+    co_Xdb<KIN, MOUT, NF, MODE>(a, xh, xl, lane, kf, c.s0, A[0], bh, bl);
+    co_Ydb<NFH, MODE7, 1, S::K1P, NKF>(c.s0, c.s1, bh, bl, acc2, lane, A, kf, hc.k1s1, G::main_unit(c.img, PASS, i0 + 1, 0), c.s2,
+                                       G::main_unit(c.img, PASS, i0 + 1, 1), c.s3, hc.k1img + (size_t)((i0 + 2) % NF) * S::K14, hc.k1s0, c.w4, c.voff);
+    // ---- hidden block i0 + 1: conv1 operands from K1, units in (S2, S3)
+    co_Xdb<KIN, MOUT, NF, MODE>(a, xh, xl, lane, kf, c.s2, A[0], bh, bl);
+    // (after the last block: conv3 units 0, 1 take the place of "block NF"; the operands read from K0 are those of block 0 and go unused)
     const bool more = i0 + 2 < NF;
-    co_Ydb<NFH, MODE7, 2, S::K1P>(c.s2, c.s3, bh, bl, acc2, lane, more ? G::main_unit(c.img, PASS, i0 + 2, 0) : G::out_unit(c.img, PASS, 0), c.s0,
-                                  more ? G::main_unit(c.img, PASS, i0 + 2, 1) : G::out_unit(c.img, PASS, 1), c.s1,
-                                  hc.k1img + (size_t)((i0 + 3) % NF) * S::K14, hc.k1s1, c.w4, c.voff);
+    co_Ydb<NFH, MODE7, 2, S::K1P, NKF>(c.s2, c.s3, bh, bl, acc2, lane, A, kf, hc.k1s0, more ? G::main_unit(c.img, PASS, i0 + 2, 0) : G::out_unit(c.img, PASS, 0),
+                                       c.s0, more ? G::main_unit(c.img, PASS, i0 + 2, 1) : G::out_unit(c.img, PASS, 1), c.s1,
+                                       hc.k1img + (size_t)((i0 + 3) % NF) * S::K14, hc.k1s1, c.w4, c.voff);
   }
   co_end<0>();                                          // Y_{NF-1}: conv3 units 0, 1 landed
   f32x4 acc3[3][2];

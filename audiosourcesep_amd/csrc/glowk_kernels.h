@@ -1321,6 +1321,41 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
   if (net_dir<MODE> == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
 }
 
+// X of the plain forward network with stacked conv1 (G::STK), in three pieces, for a caller that puts other work between them (k_net_h3c's
+// double-buffered ring, glowk_co.h: the operands are read under the end of the previous Y and the block's barrier sits in front of the
+// activation).  The same reads, MFMAs and epilogue in the same order as h3s_X, which stays as it is: composing it from these pieces changed
+// the register / LDS allocation of five training instances (docs/EXPERIMENTS.md).
+// h3s_X_load: the block's conv1 operand fragments kf[] from its K slot; h3s_X_mma: the MFMAs into h1[row block][pixel half], from zero;
+// h3s_X_act: scale, ReLU, split into bh / bl (no mask, no stores: NET_FWD / NET_FWD2).
+template <class G, int KP>
+__device__ __forceinline__ void h3s_X_load(const H3Ctx& c, int lane, h8 (&kf)[G::KSX * 2]) {
+  static_assert(G::STK && G::KSX <= 6, "stacked conv1; operand reads in flight");
+  const h8* k1 = reinterpret_cast<const h8*>(KP ? c.k1s1 : c.k1s0) + lane;   // [s][row block][64]
+#pragma unroll
+  for (int i = 0; i < G::KSX * 2; ++i) kf[i] = k1[i * 64];
+}
+template <class G>
+__device__ __forceinline__ void h3s_X_mma(const h8 (&kf)[G::KSX * 2], const h8 (&xh)[G::KS][2], const h8 (&xl)[G::KS][2], f32x4 (&h1)[2][2]) {
+  static_assert(G::STK && G::PXH == 2, "stacked conv1, two pixel halves per wave");
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h1[i >> 1][i & 1][r] = 0.0f;
+#pragma unroll
+  for (int s = 0; s < G::KSX; ++s)
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+        h1[rb][hf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s * 2 + rb], x_frag(xh, xl, s, hf), h1[rb][hf], 0, 0, 0);
+}
+template <int MODE7>
+__device__ __forceinline__ void h3s_X_act(const f32x4 (&h1)[2][2], float sc1, h8 (&bh)[2], h8 (&bl)[2]) {
+  static_assert(MODE7 == NET_FWD || MODE7 == NET_FWD2, "plain forward network");
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false>(h1[0][hf], h1[1][hf], sc1, 0u, bh[hf], bl[hf]);
+}
+
 // Y: conv2 contribution of one hidden block (one k-step of 32) to the pass's NRB x 2 accumulator tiles; same pipelining and
 // DMA duties as h3_Y (groups of 12 MFMAs = two row blocks x two pixel halves x three split terms)
 template <int KIN, int MOUT, int NF, int MODE, int NP, int TAG>
