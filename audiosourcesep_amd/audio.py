@@ -417,24 +417,14 @@ def invert(tile_batches, stft_mixture=None, wiener=False, iters=200, algorithm="
 
 def separate_audio(mix, flow1, flow2, sigmas, restore_1=None, restore_2=None, T=100, delta=2e-5, seed=0, skip=0, n=None, wiener=False,
                    top_db=80.0, iters=200, algorithm="reuse_phase", method="frame", n_iter=32, momentum=0.99):
-    """A mixture (wav path or 16 kHz samples) -> two separated signals: front end, ``basis.basis_outer_loop`` from the reference's
-    uniform start over [-100, 20] dB (run_basis_sep.py:360-361; device RNG streams 14 / 15 of ``seed``, apart from the Langevin
-    noise's 0 / 1), inversion (``invert``'s ``algorithm``, ``method``, ``n_iter`` and ``momentum``; Griffin-Lim's phases from
-    ``seed``).  Returns ``(y1, y2, mixed, x1, x2)``: the signals ([N * 32256] per tile, [(64 N - 1) * 512] for 'whole') and the
-    tiles [N, 96, 64, 1].  ``run_basis_sep.py --inverse`` is ``algorithm='griffin', method='whole'``."""
-    if algorithm not in ALGORITHMS:
-        raise ValueError("algorithm: expected one of %s, got %r" % (ALGORITHMS, algorithm))
-    _check_method(method)
-    if algorithm == "griffin":
-        _check_griffin(n_iter, momentum)
-    y = read_wav(mix) if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__") else mix
-    mixed, X = mel_tiles(extracts(y, skip, n), top_db=top_db, return_stft=True)
-    x1 = -100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14, uniform=True)
-    x2 = -100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=15, uniform=True)
-    x1, x2, _ = basis.basis_outer_loop(mixed, x1, x2, flow1, flow2, sigmas, restore_1=restore_1, restore_2=restore_2, T=T, delta=delta,
-                                       seed=seed)
-    out = invert([x1, x2], X, wiener=wiener, iters=iters, algorithm=algorithm, method=method, n_iter=n_iter, momentum=momentum, seed=seed)
-    return out[0], out[1], mixed, x1, x2
+    """A mixture (wav path or 16 kHz samples) -> two separated signals: ``separate_sources`` with the two flows and the dB mixture
+    (start states from device RNG streams 14 / 15 of ``seed``).  Returns ``(y1, y2, mixed, x1, x2)``: the signals ([N * 32256]
+    per tile, [(64 N - 1) * 512] for 'whole') and the tiles [N, 96, 64, 1].  ``run_basis_sep.py --inverse`` is
+    ``algorithm='griffin', method='whole'``."""
+    ys, mixed, xs = separate_sources(mix, [flow1, flow2], sigmas, restores=[restore_1, restore_2], T=T, delta=delta, seed=seed, skip=skip,
+                                     n=n, wiener=wiener, top_db=top_db, iters=iters, algorithm=algorithm, method=method, n_iter=n_iter,
+                                     momentum=momentum)
+    return ys[0], ys[1], mixed, xs[0], xs[1]
 
 
 def separate_wav(path, flow1, flow2, sigmas, out_rate="input", **kwargs):
@@ -455,11 +445,12 @@ def separate_wav(path, flow1, flow2, sigmas, out_rate="input", **kwargs):
 
 def separate_sources(mix, flows, sigmas, restores=None, T=100, delta=2e-5, seed=0, skip=0, n=None, wiener=False, top_db=80.0, iters=200,
                      algorithm="reuse_phase", method="frame", n_iter=32, momentum=0.99, mixing="db"):
-    """``separate_audio`` for S = len(flows) priors, S in [2, 16]: front end, ``basis.basis_outer_loop_n`` from the uniform start
-    over [-100, 20] dB (source k: device RNG stream 14 + (k & 1) of source pair k >> 1, so the first two start where
-    ``separate_audio`` starts them), ``invert`` of the S tile batches.  ``restores``: as for ``basis_outer_loop_n``.  Returns
-    ``(ys, mixed, xs)``: the signals [S, N * 32256] ([S, (64 N - 1) * 512] for 'whole'), the mixture tiles [N, 96, 64, 1] and the
-    separated tiles [S, N, 96, 64, 1]."""
+    """A mixture (wav path or 16 kHz samples) -> S = len(flows) separated signals, S in [2, 16]: front end,
+    ``basis.basis_outer_loop_n`` from the reference's uniform start over [-100, 20] dB (run_basis_sep.py:360-361; source k: device
+    RNG stream 14 + (k & 1) of source pair k >> 1 of ``seed``, apart from the Langevin noise's 0 / 1), ``invert`` of the S tile
+    batches (its ``algorithm``, ``method``, ``n_iter`` and ``momentum``; Griffin-Lim's phases from ``seed``).  ``restores``: as
+    for ``basis_outer_loop_n``.  Returns ``(ys, mixed, xs)``: the signals [S, N * 32256] ([S, (64 N - 1) * 512] for 'whole'), the
+    mixture tiles [N, 96, 64, 1] and the separated tiles [S, N, 96, 64, 1]."""
     if algorithm not in ALGORITHMS:
         raise ValueError("algorithm: expected one of %s, got %r" % (ALGORITHMS, algorithm))
     _check_method(method)

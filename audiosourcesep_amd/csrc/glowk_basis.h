@@ -1,10 +1,11 @@
-// glowk device code, part 3: the BASIS Langevin update (run_basis_sep.py:131-181, dB branch, two sources) as ONE elementwise
-// kernel with its own counter-based RNG.  HBM-bound and tiny next to the two log_prob_grad calls of a step; what matters at
-// the reference's 30 tiles is that it is one launch instead of the dozen elementwise/reduction launches of a tensor library.
-// k_basis_update is the two-source dB update; k_basis_update_n<S> further down takes 2..16 sources and either mixing process.
+// glowk device code, part 3: the BASIS Langevin update (run_basis_sep.py:106-181) for 2..16 sources as ONE elementwise kernel
+// with its own counter-based RNG.  HBM-bound and tiny next to the S log_prob_grad calls of a step; what matters at the
+// reference's 30 tiles is that it is one launch instead of the dozen elementwise/reduction launches of a tensor library.
+// k_basis_update_n<S> is the only update kernel: the two-source entry points (glowk_basis_update, glowk_basis_mix) launch its
+// S = 2 instance.  For the dB mixing process (:131-147; the linear mean of :108-116 is the other):
 //
 //   eps_k  = sqrt(2 eta) N(0, I)                                                 :163-164
-//   mix    = 10/ln10 (logsumexp_k(x_k ln10/10) - ln 2)                            :133-141  (g, sum in power)
+//   mix    = 10/ln10 (logsumexp_k(x_k ln10/10) - ln S)                            :133-141  (g, sum in power)
 //   m_k    = softmax_k(x_k ln10/10)                                               :143-147  (grad_g)
 //   x_k   <- x_k + eta (grad_logprob_k + lambda m_k (mixed - mix)) + eps_k        :180-181
 #pragma once
@@ -46,54 +47,7 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t w
   }
 }
 
-struct BasisArgs {
-  float* x1;            // [n] in place
-  float* x2;
-  const float* g1;      // [n] grad log p_1(x1), grad log p_2(x2) (compute_grad_logprob, :174-175)
-  const float* g2;
-  const float* mixed;   // [n] the observed mixture
-  const float* eps1;    // optional [n] standard-normal draws supplied by the caller (tests replay the oracle's); null: device RNG
-  const float* eps2;
-  size_t n;
-  float eta, lambda_recon, noise_scale;   // noise_scale = sqrt(2 eta)
-  uint64_t seed, step;
-  uint64_t q0;          // index of x[0] in the logical noise stream, in groups of four elements (shards: the global element offset / 4)
-  int* nonfinite;       // optional: set to 1 if a gradient, a mixing term or an updated value is not finite (the reference's asserts, :183-191)
-};
-
 __device__ __forceinline__ bool basis_bad(float v) { return !(fabsf(v) <= 3.0e38f); }
-
-// one thread = four consecutive elements (one Philox call per source)
-__global__ __launch_bounds__(256) void k_basis_update(BasisArgs a) {
-  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t e0 = (size_t)q * 4;
-  if (e0 >= a.n) return;
-  float z1[4], z2[4];
-  if (!a.eps1) normal4(a.seed, a.step, 0u, a.q0 + q, z1);
-  if (!a.eps2) normal4(a.seed, a.step, 1u, a.q0 + q, z2);
-  const float L10 = 0.23025850929940457f;   // ln 10 / 10
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const size_t e = e0 + j;
-    if (e >= a.n) break;
-    const float x1 = a.x1[e], x2 = a.x2[e], g1 = a.g1[e], g2 = a.g2[e];
-    const float n1 = a.eps1 ? a.eps1[e] : z1[j], n2 = a.eps2 ? a.eps2[e] : z2[j];
-    const float s1 = x1 * L10, s2 = x2 * L10;
-    const float mx = fmaxf(s1, s2);
-    const float e1 = expf(s1 - mx), e2 = expf(s2 - mx);
-    const float den = e1 + e2;
-    const float mix = (1.0f / L10) * (mx + logf(den) - 0.69314718055994531f);
-    const float m1 = e1 / den, m2 = e2 / den;
-    const float r = a.lambda_recon * (a.mixed[e] - mix);
-    const float y1 = x1 + a.eta * (g1 + m1 * r) + a.noise_scale * n1;
-    const float y2 = x2 + a.eta * (g2 + m2 * r) + a.noise_scale * n2;
-    bad |= basis_bad(g1) | basis_bad(g2) | basis_bad(mix) | basis_bad(y1) | basis_bad(y2);
-    a.x1[e] = y1;
-    a.x2[e] = y2;
-  }
-  if (bad && a.nonfinite) *a.nonfinite = 1;
-}
 
 // ---- any number of sources (run_basis_sep.py:106-149: g(*sources), grad_g(*sources) for K = len(sources)) ---------------------
 //   GLOWK_MIX_DB   (:131-147)  mix = 10/ln10 (logsumexp_k(x_k ln10/10) - ln S),  m_k = softmax_k(x_k ln10/10)
@@ -118,9 +72,13 @@ struct BasisNArgs {
   int* nonfinite;
 };
 
-// mix and the weights m_k of one element from its S source values; v[k] holds x_k on entry and m_k on return
+// The mixture and the weights m_k of one element from its S source values: v[k] holds x_k on entry and m_k on return, and
+// mix = scale * t with t returned.  Wherever a product meets a sum the rounding is written out (__fmul_rn / fmaf) instead of
+// left to the compiler's contraction, here and in the callers: it is the rounding of the two-source kernel this one replaced,
+// whose results are pinned bit for bit (tests/golden/basis_two_source.npz).  The maximum is taken over the rounded products
+// x_k L10; each difference x_k L10 - mx is one fma; the callers form mixed - mix as fmaf(-scale, t, mixed).
 template <int S>
-__device__ __forceinline__ float basis_mix_terms(float (&v)[S], int mixing, float ln_s, float inv_s) {
+__device__ __forceinline__ float basis_mix_terms(float (&v)[S], int mixing, float ln_s, float inv_s, float& scale) {
   const float L10 = 0.23025850929940457f;   // ln 10 / 10
   if (mixing == 1) {                        // GLOWK_MIX_MEAN
     float sum = v[0];
@@ -128,20 +86,21 @@ __device__ __forceinline__ float basis_mix_terms(float (&v)[S], int mixing, floa
     for (int k = 1; k < S; ++k) sum += v[k];
 #pragma unroll
     for (int k = 0; k < S; ++k) v[k] = inv_s;
-    return sum * inv_s;
+    scale = inv_s;
+    return sum;
   }
-  float mx = v[0] * L10;
+  float mx = __fmul_rn(v[0], L10);
 #pragma unroll
-  for (int k = 1; k < S; ++k) mx = fmaxf(mx, v[k] * L10);
-  float den = 0.0f;
+  for (int k = 1; k < S; ++k) mx = fmaxf(mx, __fmul_rn(v[k], L10));
 #pragma unroll
-  for (int k = 0; k < S; ++k) {
-    v[k] = expf(v[k] * L10 - mx);
-    den += v[k];
-  }
+  for (int k = 0; k < S; ++k) v[k] = expf(fmaf(v[k], L10, -mx));
+  float den = v[0];
+#pragma unroll
+  for (int k = 1; k < S; ++k) den += v[k];
 #pragma unroll
   for (int k = 0; k < S; ++k) v[k] = v[k] / den;
-  return (1.0f / L10) * (mx + logf(den) - ln_s);
+  scale = 1.0f / L10;
+  return mx + logf(den) - ln_s;
 }
 
 // one thread = four consecutive elements of every source (one Philox call per source)
@@ -176,11 +135,12 @@ __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
     float v[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) v[k] = x[k][j];
-    const float mix = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s);
+    float scale;
+    const float t = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s, scale);
 #pragma unroll
     for (int k = 0; k < S; ++k) m[k][j] = v[k];
-    r[j] = a.lambda_recon * (mixed[j] - mix);
-    bad |= basis_bad(mix);
+    r[j] = a.lambda_recon * fmaf(-scale, t, mixed[j]);
+    bad |= basis_bad(__fmul_rn(scale, t));
   }
 #pragma unroll
   for (int k = 0; k < S; ++k) {
@@ -205,7 +165,7 @@ __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
     float y[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      y[j] = x[k][j] + a.eta * (g[j] + m[k][j] * r[j]) + a.noise_scale * z[j];
+      y[j] = fmaf(a.noise_scale, z[j], fmaf(a.eta, fmaf(m[k][j], r[j], g[j]), x[k][j]));
       bad |= basis_bad(g[j]) | basis_bad(y[j]);
     }
     if (quad) {
@@ -235,20 +195,12 @@ __global__ __launch_bounds__(256) void k_basis_mix_n(BasisMixNArgs a) {
   float v[S];
 #pragma unroll
   for (int k = 0; k < S; ++k) v[k] = a.x[k][e];
-  a.out[e] = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s);
+  float scale;
+  const float t = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s, scale);
+  a.out[e] = __fmul_rn(scale, t);
 }
 
-// g(x1, x2) alone (the mixture of two sources in dB, sum in power)
-__global__ __launch_bounds__(256) void k_basis_mix(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ out, size_t n) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const float L10 = 0.23025850929940457f;
-  const float s1 = x1[e] * L10, s2 = x2[e] * L10;
-  const float mx = fmaxf(s1, s2);
-  out[e] = (1.0f / L10) * (mx + logf(expf(s1 - mx) + expf(s2 - mx)) - 0.69314718055994531f);
-}
-
-// the standard-normal draws k_basis_update makes for (seed, step, which); also the engine's general device RNG
+// the standard-normal draws k_basis_update_n makes for (seed, step, which); also the engine's general device RNG
 // (uniform = 1: U(0, 1) instead -- the reference starts the chain from uniform noise, run_basis_sep.py:360-361)
 __global__ __launch_bounds__(256) void k_basis_noise(float* __restrict__ out, size_t n, uint64_t seed, uint64_t step, uint32_t which, int uniform,
                                                     uint64_t q0, uint32_t pair) {

@@ -269,8 +269,9 @@ int glowk_param_grad(glowk_handle* h, const float* x_dev, int N, float scale, fl
 int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer, float lr, void* stream);
 
 /* --- BASIS: the annealed-Langevin update around the log_prob_grad calls of a step (run_basis_sep.py:152-181) --------------- */
-/* Two entry points: glowk_basis_update is the two-source dB update the package started with and keeps bit for bit;
- * glowk_basis_update_n (further down) takes 2..16 sources and either mixing process of the reference (:106-149). */
+/* One kernel, two argument lists: glowk_basis_update_n (further down) takes 2..16 sources and either mixing process of the
+ * reference (:106-149); glowk_basis_update is its call for two sources and the dB mixture under the argument list the package
+ * started with.  Its results are pinned bit for bit (tests/golden/basis_two_source.npz). */
 /* One step of basis_inner_loop for two sources, in place, as ONE kernel:
  *     mix = g(x1, x2) (:133-141),  (m1, m2) = grad_g(x1, x2) (:143-147),
  *     x_k <- x_k + eta (g_k + lambda_recon m_k (mixed - mix)) + sqrt(2 eta) N(0, I)        (:163-164, :180-181)
@@ -280,11 +281,13 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
  * `offset` (a multiple of 4) is the position of element 0 in that stream: a rank that holds tiles [a, b) of the mixture passes
  * a * H * W * C and draws exactly what one process would have drawn for those tiles, so a sharded run is the unsharded one.
  * nonfinite_dev (optional, one int on the device): set to 1 when a gradient, the mixture or an updated value is not finite --
- * the reference's debug asserts (:183-191). */
+ * the reference's debug asserts (:183-191).
+ * The conditions of glowk_basis_update_n hold here too: step < 2^48, and x1, x2 are distinct buffers that do not overlap
+ * `mixed` (a state updated in place under an alias never had a meaning: each element's update reads both states). */
 int glowk_basis_update(float* x1_dev, float* x2_dev, const float* g1_dev, const float* g2_dev, const float* mixed_dev, size_t n,
                        float eta, float lambda_recon, const float* eps1_dev, const float* eps2_dev, uint64_t seed, uint64_t step,
                        uint64_t offset, int* nonfinite_dev, void* stream);
-/* g(x1, x2) alone: the mixture of two sources in dB, sum in power (:133-141) */
+/* g(x1, x2) alone: the mixture of two sources in dB, sum in power (:133-141); glowk_basis_mix_n for two sources */
 int glowk_basis_mix(const float* x1_dev, const float* x2_dev, float* out_dev, size_t n, void* stream);
 /* The mixing processes g(*sources) / grad_g(*sources) of run_basis_sep.py for S = len(sources).  (Its scale == 'power' branch is
  * not offered: its grad_g is not the derivative of its g, and nothing here lives in power scale.) */

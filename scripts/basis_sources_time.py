@@ -1,10 +1,10 @@
 """Times of the S-source BASIS step on one GPU (HIP events), for S in {2, 3, 4} (the update kernel also for S = 16):
   * the update kernel alone (``glowk_basis_update_n``, device RNG) at 30 tiles of 96x64 and at 64 times as many, with the bandwidth
-    its time implies against the (3 S + 1) * 4 bytes per element it has to move, and the two-source kernel (``glowk_basis_update``)
-    beside it;
+    its time implies against the (3 S + 1) * 4 bytes per element it has to move, and the two-source entry point
+    (``glowk_basis_update``: the same S = 2 instance behind the two-source argument list) beside it;
   * one Langevin step (S gradient evaluations + the update) with config-B-geometry priors (64x64, L = 3, n_filters 512) of K = 32
     on 30 tiles, the gradients on side streams (created once; and "auto": created per call) and one after the other, alternated in
-    one process; for S = 2 the same through the two-source path (``basis_inner_loop``), which this package leaves as it was.
+    one process; for S = 2 the same through the two-source signature (``basis_inner_loop``), an adapter over the same loop.
 Synthetic weights and tiles.  Prints one JSON object and writes it to --out.
     python scripts/basis_sources_time.py --out profiles/basis_sources_time.json [--reps 7] [--K 32]
     rocprofv3 --kernel-trace --stats --output-format csv -- python scripts/basis_sources_time.py --update-only    (kernel times)
@@ -73,7 +73,7 @@ def main():
             def upd2():
                 basis.langevin_update(mixed, xs[0], xs[1], gs[0], gs[1], 1e-9, 1.0, seed=1, step=step[0])
                 step[0] += 1
-            for name, fn in (("S%d" % S, upd),) + ((("S2_two_source_kernel", upd2),) if S == 2 else ()):
+            for name, fn in (("S%d" % S, upd),) + ((("S2_two_source_entry", upd2),) if S == 2 else ()):
                 r = timed(fn, args.reps, inner=200)
                 nbytes = (3 * S + 1) * 4 * n
                 r.update(bytes_per_call=nbytes, implied_GBps=nbytes / (r["median_ms"] * 1e-3) / 1e9)
@@ -111,7 +111,7 @@ def main():
             t[0] += 1
             return out
         variants = {"side_streams": lambda: step_n(side), "sequential": lambda: step_n(None), "auto_streams": lambda: step_n("auto")}
-        if S == 2:   # the two-source path beside it: the same stream objects, none, and its own "auto" (two new streams per call)
+        if S == 2:   # the two-source signature beside it: the same stream objects, none, and "auto" (two new streams per call)
             variants.update({"two_source_path_side_streams": lambda: step_2(tuple(side)), "two_source_path_sequential": lambda: step_2(None),
                              "two_source_path_auto_streams": lambda: step_2("auto")})
         for fn in variants.values():

@@ -1,7 +1,8 @@
 """BASIS for any number of sources on the GPU: ``glowk_basis_update_n`` / ``glowk_basis_mix_n`` / ``glowk_random_source`` against
 the float64 formulas, their bitwise properties, the S-source loop against an fp64 oracle loop (tests/basis_sources_ref.py) and
-``audio.separate_sources`` end to end."""
+``audio.separate_sources`` end to end; the two-source entry points against the recorded results of the kernels they had."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -44,7 +45,8 @@ def draw(S, shape=SHAPE, seed=5):
 def test_update_kernel_against_the_formulas(S, process, unaligned):
     """glowk_basis_update_n == run_basis_sep.py:163-181 for S sources written out in float64, with injected noise: whole quads as
     16-byte accesses (1344 elements end inside the second workgroup), and element by element from buffers offset by one float
-    (test_partial_last_quad covers a last thread with fewer than four elements).  glowk_basis_mix_n against g alone; S = 2 against the two-source kernel."""
+    (test_partial_last_quad covers a last thread with fewer than four elements).  glowk_basis_mix_n against g alone; S = 2 bit for
+    bit against the two-source entry points."""
     put = offset_view if unaligned else dev
     mixed, xs, gs, eps = draw(S)
     want = ref.update(mixed, xs, gs, eps, ETA, LAM, process)
@@ -62,9 +64,8 @@ def test_update_kernel_against_the_formulas(S, process, unaligned):
     if S == 2 and process == "db":
         z1, z2 = dev(xs[0]), dev(xs[1])
         basis.langevin_update(dev(mixed), z1, z2, dev(gs[0]), dev(gs[1]), ETA, LAM, dev(eps[0]), dev(eps[1]))
-        np.testing.assert_allclose(ys[0].cpu().numpy(), z1.cpu().numpy(), rtol=1e-5, atol=1e-4)
-        np.testing.assert_allclose(ys[1].cpu().numpy(), z2.cpu().numpy(), rtol=1e-5, atol=1e-4)
-        np.testing.assert_allclose(mix.cpu().numpy(), basis.mixing_db(dev(xs[0]), dev(xs[1])).cpu().numpy(), rtol=2e-6, atol=2e-5)
+        assert torch.equal(ys[0], z1) and torch.equal(ys[1], z2)
+        assert torch.equal(mix, basis.mixing_db(dev(xs[0]), dev(xs[1])))
 
 
 def test_partial_last_quad():
@@ -78,6 +79,34 @@ def test_partial_last_quad():
     for f, x, w in zip(full, xs, want):
         np.testing.assert_allclose(f[:n].cpu().numpy(), w[:n], rtol=1e-5, atol=1e-4)
         assert float(f[n]) == np.float32(x[n])
+
+
+def test_two_sources_reproduce_the_recorded_two_source_kernels():
+    """tests/golden/basis_two_source.npz holds what k_basis_update / k_basis_mix, the two-source kernels that the S = 2 instance
+    replaced, returned on an MI355X at the last commit that had them (tests/golden/basis_two_source.md): n = 1343 elements (a
+    full workgroup, a second one, a last thread with three elements), states in [-100, 20] dB with equal pairs and pairs more
+    than 100 dB apart.  Both update entry points and both mixture entry points return those bits: with injected noise, with the
+    device RNG at a stream offset, and from buffers offset by one float, which go element by element."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "basis_two_source.npz"))
+    eta, lam = float(z["eta"]), float(z["lambda_recon"])
+    assert z["x1"].shape == (1343,) and int((z["x1"] == z["x2"]).sum()) >= 40 and int((np.abs(z["x1"] - z["x2"]) > 100.0).sum()) >= 60
+    for case, put, inject, kw in (("injected", dev, True, {}), ("device_rng", dev, False, dict(seed=99, step=5, offset=8)),
+                                  ("offset", offset_view, True, {})):
+        want = [dev(z[case + "_y1"]), dev(z[case + "_y2"])]
+        eps = [put(z["eps1"]), put(z["eps2"])] if inject else [None, None]
+        a, b = put(z["x1"]), put(z["x2"])
+        basis.langevin_update(put(z["mixed"]), a, b, put(z["g1"]), put(z["g2"]), eta, lam, eps[0], eps[1], **kw)
+        assert torch.equal(a, want[0]) and torch.equal(b, want[1]), case
+        ys = [put(z["x1"]), put(z["x2"])]
+        basis.langevin_update_n(put(z["mixed"]), ys, [put(z["g1"]), put(z["g2"])], eta, lam, eps if inject else None, **kw)
+        assert torch.equal(ys[0], want[0]) and torch.equal(ys[1], want[1]), case
+    a, b, mix = dev(z["x1"]), dev(z["x2"]), dev(z["mix"])
+    assert torch.equal(basis.mixing_db(a, b), mix) and torch.equal(basis.mixing([a, b]), mix)
+    out = torch.empty_like(a)                                  # (mixing_db goes through glowk_basis_mix_n: the C entry itself)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert _lib.load().glowk_basis_mix(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                       a.numel(), st) == _lib.OK
+    assert torch.equal(out, mix)
 
 
 def source_draw(k, shape, seed, step, offset=0):
@@ -210,6 +239,10 @@ def test_flag_and_argument_checks():
     with pytest.raises(_lib.GlowkError):
         basis.langevin_update_n(m, [x[0], x[0]], g[:2], ETA, LAM)
     with pytest.raises(_lib.GlowkError):
+        basis.langevin_update(m, x[0], x[0], g[0], g[1], ETA, LAM)                # the two-source entry makes the same checks
+    with pytest.raises(_lib.GlowkError):
+        basis.langevin_update(m, x[0], x[1], g[0], g[1], ETA, LAM, step=1 << 48)
+    with pytest.raises(_lib.GlowkError):
         basis.device_randn((8,), "cuda", seed=1, step=1 << 48, pair=1)
     with pytest.raises(ValueError):
         basis.langevin_update_n(m, x, g, ETA, LAM, mixing="power")
@@ -319,7 +352,7 @@ def test_separate_sources_end_to_end(audio_flows):
     assert torch.equal(ys, ys2) and torch.equal(xs, xs2)
     ys3, _, xs3 = audio.separate_sources(y, audio_flows, sig, T=2, delta=1e-4, seed=10)
     assert not torch.equal(xs, xs3) and not torch.equal(ys, ys3)
-    # two flows: the two-source path's tiles (same start states, same noise, its own kernel)
+    # two flows: the two-source signature's tiles (same start states, same noise, the same loop and kernel)
     y1, y2, m2, x1, x2 = audio.separate_audio(y, audio_flows[0], audio_flows[1], sig, **kw)
     yp, mp, xp = audio.separate_sources(y, audio_flows[:2], sig, **kw)
     assert torch.equal(mp, m2) and tuple(yp.shape) == (2, 2 * 32256)

@@ -15,7 +15,7 @@ from oracle import glowref as R
 pytestmark = pytest.mark.gpu
 PRIMARY_FAMILIES = ("f32", "h3_32x32x16", "h3s_16x16x32", "h3s_half", "fused")   # (co_resident / small_grid_q count subsets of these)
 FILES = sorted(f for f in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "*.npz"))
-               if not os.path.basename(f).startswith(("real_", "basis_real_")))   # (those two hold tiles, not oracle vectors)
+               if not os.path.basename(f).startswith(("real_", "basis_")))   # (those hold tiles and recorded kernel results, not oracle vectors)
 
 
 def dev(a):
