@@ -27,7 +27,7 @@ void launch_fail(const std::string& m) { fail(m); }
 static EnvSwitches read_env() {
   auto on = [](const char* n) { return getenv(n) != nullptr; };
   return EnvSwitches{on("GLOWK_BWD_LIGHT_4"), on("GLOWK_NO_FUSE"), on("GLOWK_WGRAD_PLAIN"), on("GLOWK_CO_OFF"), on("GLOWK_CO_RING3"), on("GLOWK_Q_OFF"), on("GLOWK_CO_TRAIN_OFF"),
-                     on("GLOWK_TRAIN_RECOMPUTE"), on("GLOWK_TRAIN_PERSTEP"), on("GLOWK_PG_JOIN")};
+                     on("GLOWK_TRAIN_RECOMPUTE"), on("GLOWK_TRAIN_PERSTEP"), on("GLOWK_NO_PRESUM"), on("GLOWK_PG_JOIN")};
 }
 static EnvSwitches g_env = read_env();
 const EnvSwitches& env() { return g_env; }
@@ -115,6 +115,14 @@ int launch_bwd_light(int c, const BwdArgs& a, int N, hipStream_t s) {
 // log-det slots of the flat-grid coupling kernel (k_couple_flat): slot[n * stride + base + workgroup within the sample]
 struct FlatLd { double* slot; int stride, base; };
 
+// (a.presum: the instances that read the pre-summed P, which only the 8- and 16-channel levels write)
+#define PDISPATCH(c, CALL)                                                                     \
+  switch (c) {                                                                                 \
+    case 8: { constexpr int CC = 8; CALL; } break;                                             \
+    case 16: { constexpr int CC = 16; CALL; } break;                                           \
+    default: return fail("pre-summed P at channel count " + std::to_string(c));                \
+  }
+
 int launch_couple(int c, const CoupleArgs& a, int N, hipStream_t s, const FlatLd* fl = nullptr, bool* flat_used = nullptr) {
   const int hw = a.h * a.w;
   if (N < 2 * num_cus() && hw % 64 == 0 && (!a.logdet || (fl && fl->slot))) {
@@ -124,17 +132,23 @@ int launch_couple(int c, const CoupleArgs& a, int N, hipStream_t s, const FlatLd
     b.logdet = nullptr;
     double* slots = a.logdet ? fl->slot : (double*)nullptr;
     const bool wide = c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus();
-    if (wide) { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
+    if (a.presum) {
+      if (wide) { PDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16, true>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
+      else { PDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 4, true>), dim3((a.Q + 63) / 64), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
+    }
+    else if (wide) { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
     else { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 4>), dim3((a.Q + 63) / 64), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
     LAUNCHCHK("k_couple_flat");
     if (flat_used && a.logdet) *flat_used = true;
     return 0;
   }
   if (N >= 2 * num_cus()) {   // enough per-sample workgroups to fill the chip: one lane per pixel
-    CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, false>), dim3(N), dim3(256), 0, s, a));
+    if (a.presum) { PDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, false, true>), dim3(N), dim3(256), 0, s, a)); }
+    else { CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, false>), dim3(N), dim3(256), 0, s, a)); }
   } else {                    // four lanes per pixel, up to 256 pixels in flight per sample
     const int threads = hw >= 256 ? 1024 : hw > 64 ? 512 : 256;
-    CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, true>), dim3(N), dim3(threads), 0, s, a));
+    if (a.presum) { PDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, true, true>), dim3(N), dim3(threads), 0, s, a)); }
+    else { CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, true>), dim3(N), dim3(threads), 0, s, a)); }
   }
   LAUNCHCHK("k_couple");
   return 0;
@@ -177,7 +191,7 @@ int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArg
   NetLaunch r;
   if (int rc = launch_net(h, lvl, c, F, na, s, call, &r)) return rc;
   if (!r.fused_px) {
-    ca.P = na.P; ca.np = r.np; ca.pstride = na.pstride;
+    ca.P = na.P; ca.np = r.np; ca.pstride = na.pstride; ca.presum = r.presum ? 1 : 0;
     return launch_couple(c, ca, N, s, fl, flat_used);
   }
   ++h->fused_steps;
@@ -332,7 +346,10 @@ NetArgs net_args(glowk_handle* h, const Level& lv, const StepDev& sd, const floa
   a.bnorm = 1.0f;
   a.fuse = 0; a.co = glowk_detail::env().co_off ? 0 : 1; a.fz_osave = nullptr; a.fz_b3 = nullptr; a.fz_A = nullptr; a.fz_b = nullptr; a.fz_out = nullptr; a.fz_out_stride = 0; a.fz_out_off = 0; a.fz_inverse = 0;
   a.fz_edge = nullptr; a.fz_ldpart = nullptr;
-  a.pad = nullptr;
+  // conv3's horizontal taps added in the forward 16x16x32 kernels (c3_presum_store): the level shape alone decides, so that every launch
+  // form of a shape -- whatever the batch size selects -- writes the same layout and adds in the same order
+  a.pw = (!glowk_detail::env().no_presum && (lv.c == 8 || lv.c == 16) && lv.w >= 4 && lv.w <= 16 && (lv.w & (lv.w - 1)) == 0) ? lv.w : 0;
+  a.pad = 0;
   a.xmax_out = h->d_probe ? h->d_probe + ((&lv - h->levels.data()) * h->cfg.K + (&sd - lv.dev.data())) : nullptr;
   return a;
 }
@@ -392,6 +409,7 @@ int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_
         na.st2 = na.st1 + (size_t)cfg.F * Q;
       }
       CoupleArgs ca;
+      ca.presum = 0;
       ca.vin = cur; ca.b3 = sd.b3; ca.logdet = h->bufLd; ca.log_s_out = nullptr; ca.t_out = nullptr;
       ca.o_save = save ? h->saveP + h->offP[sidx] : nullptr;
       ca.Q = (int)Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
@@ -572,7 +590,7 @@ int run_inverse(glowk_handle* h, const float* z, int N, float* x, hipStream_t s)
     for (int k = 0; k < K; ++k) {   // Chain.inverse: step 0 first
       const StepDev& sd = lv.dev[k];
       CoupleArgs ca;
-      ca.vin = cur; ca.P = h->bufP; ca.np = 1; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr; ca.o_save = nullptr;
+      ca.vin = cur; ca.P = h->bufP; ca.np = 1; ca.pstride = h->pstride; ca.presum = 0; ca.b3 = sd.b3; ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr; ca.o_save = nullptr;
       ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
       ca.A = sd.Ainv; ca.b = sd.binv; ca.out = oth; ca.out_stride = lv.c; ca.out_off = 0;
       if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, net_args(h, lv, sd, cur, lv.c, lv.c / 2, N), ca, N, s, net_call(h, NET_FWD))) return rc;
@@ -826,7 +844,7 @@ int run_step_inplace(glowk_handle* h, int lvl, int k, float* cur, float* tmp, in
   if (int rc = launch_net(h, lvl, lv.c, h->cfg.F, na, s, NetCall{NET_FWD, NET_EXACT})) return rc;
   CoupleArgs ca;
   ca.o_save = nullptr;
-  ca.vin = tmp; ca.P = h->bufP; ca.np = 1; ca.pstride = 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
+  ca.vin = tmp; ca.P = h->bufP; ca.np = 1; ca.pstride = 0; ca.presum = 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
   ca.out = cur; ca.out_stride = lv.c; ca.out_off = 0;
   ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
   ca.Q = Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = nullptr;
@@ -1242,7 +1260,7 @@ int glowk_step_forward(glowk_handle* h, int level, int step, const float* u_dev,
     }
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = h->bufA; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
+    ca.vin = h->bufA; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
     ca.out = y_dev; ca.out_stride = lv.c; ca.out_off = 0;
     ca.logdet = logdet_dev ? h->bufLd : nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
     ca.Q = Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
@@ -1270,7 +1288,7 @@ int glowk_step_inverse(glowk_handle* h, int level, int step, const float* y_dev,
     if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, y_dev, lv.c, lv.c / 2, N), s, net_call(h, NET_FWD), &r)) return rc;
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = y_dev; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = sd.Ainv; ca.b = sd.binv;
+    ca.vin = y_dev; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = sd.Ainv; ca.b = sd.binv;
     ca.out = u_dev; ca.out_stride = lv.c; ca.out_off = 0;
     ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
     ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
@@ -1292,7 +1310,7 @@ int glowk_coupling_net(glowk_handle* h, int level, int step, const float* xb_dev
     if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, xb_dev, lv.c / 2, 0, N), s, net_call(h, NET_FWD), &r)) return rc;
     CoupleArgs ca;
     ca.o_save = nullptr;
-    ca.vin = nullptr; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
+    ca.vin = nullptr; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
     ca.out = nullptr; ca.out_stride = 0; ca.out_off = 0;
     ca.logdet = nullptr; ca.log_s_out = log_s_dev; ca.t_out = t_dev;
     ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);

@@ -16,3 +16,35 @@
 constexpr int glowk_conv1_ks(int K1) { return (K1 + 1 + 31) / 32; }
 constexpr int glowk_conv1_ks_stacked(int K1) { return (3 * K1 + 2 + 31) / 32; }
 constexpr bool glowk_conv1_stacked(int K1) { return glowk_conv1_ks_stacked(K1) <= 2 * glowk_conv1_ks(K1); }
+
+// conv3 of the forward 16x16x32 kernels (RingS; M = 9 c output rows in 16-row tiles): row order of the A image at c = 8 and 16.
+// A lane of group kq = lane >> 4 holds, per 16-pixel half, register r of row tile mt = row 16 mt + 4 kq + r; the tiles of one
+// accumulator group (<= 6 tiles: mt = 6 gi + ml) are live together, s = 4 ml + r numbers the group's registers of a lane.  The
+// rows are ordered so that registers 3 u, 3 u + 1, 3 u + 2 of a lane group are the taps dx = -1, 0, +1 of ONE (dy, channel): the
+// kernels can then add the three horizontal taps in registers (two DPP row shifts: the neighbour pixels sit in the neighbour
+// lanes) and store P with 3 c rows instead of 9 c.  Triplet u of lane group kq in accumulator group gi is row
+//     T = 32 gi + 4 u + kq = (dy + 1) c + channel
+// of that pre-summed P (a full group of six tiles holds 4 x 8 triplets); c = 8: one group of five tiles, six triplets per lane
+// group and two spare registers (zero rows); c = 16: groups of six and three tiles, 8 + 4 triplets, no padding.  Every other c keeps
+// the natural order (row m = tap c + channel).  The packer writes the image, the kernels decode their store rows and the
+// per-row constants (which stay in natural order) by this one rule.
+constexpr bool glowk_conv3_permuted(int c) { return c == 8 || c == 16; }
+// row T of the pre-summed P that image row m belongs to, times 3, plus its tap dx + 1; -1: a padding row
+constexpr int glowk_conv3_triplet(int c, int m) {
+  const int nmt = (9 * c + 15) / 16;
+  const int mt = m / 16, kq = (m % 16) / 4, r = m % 4;
+  const int gi = mt / 6, ml = mt % 6;
+  const int gn = nmt - 6 * gi < 6 ? nmt - 6 * gi : 6;
+  const int s = 4 * ml + r, u = s / 3;
+  if (mt >= nmt || u >= 4 * gn / 3) return -1;
+  return 3 * (32 * gi + 4 * u + kq) + s % 3;
+}
+// natural row tap * c + channel (tap = 3 (dy + 1) + dx + 1) held by image row m; 9 c: a padding row.  Within a lane's register the
+// natural row of lane group kq is that of lane group 0 plus kq (4 u is a multiple of 4, c a multiple of 8).
+constexpr int glowk_conv3_row(int c, int m) {
+  if (!glowk_conv3_permuted(c)) return m < 9 * c ? m : 9 * c;
+  const int t = glowk_conv3_triplet(c, m);
+  if (t < 0) return 9 * c;
+  const int T = t / 3, dxi = t % 3;
+  return (3 * (T / c) + dxi) * c + T % c;
+}

@@ -253,11 +253,23 @@ __device__ __forceinline__ void co_Z(const NetArgs& a, const H3Ctx& hc, const Co
     acc3[ml][0] = mfma3s<MODE7 == NET_FWD2>(ah, al, bh[0], bl[0], acc3[ml][0]);
     acc3[ml][1] = mfma3s<MODE7 == NET_FWD2>(ah, al, bh[1], bl[1], acc3[ml][1]);
     if (fo == NFH - 1) {
+      if constexpr (G::S::C3P) {     // (the 8-channel level: one accumulator group of five tiles, two partial buffers)
+        static_assert(!G::MERGE && !G::FUSE && NMT == 5, "the pre-sum writes per-pass partials");
+        if (a.pw) {     // as h3s_Z: the sums stay in acc3, scaled; the last tile adds the horizontal taps and stores
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              acc3[ml][hf][r] = PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[c3_row<typename G::S>(ml, r, kq)]) : acc3[ml][hf][r] * a.sc3;
+          if (ml == NMT - 1) c3_presum_store<NMT, 2>(acc3, a.P + (size_t)PASS * a.pstride, a.Q, a.pw, 0, q, qok, lane, kq);
+          continue;
+        }
+      }
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int m = ml * 16 + 4 * kq + r;
+          const int m = c3_row<typename G::S>(ml, r, kq);
           const float part = G::BWD ? acc3[ml][hf][r] * (a.sc3 * hc.ub[hf]) : PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[m]) : acc3[ml][hf][r] * a.sc3;
           if constexpr (NEXT && G::MERGE) { keep[ml][hf][r] = part; continue; }
           const float val = (LAST && G::MERGE) ? part + keep[ml][hf][r] : part;

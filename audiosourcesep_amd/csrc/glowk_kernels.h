@@ -77,8 +77,12 @@ struct NetArgs {
   // (before BatchNorm); backward: st1 = mask2 * conv3^T(g_o) (gradient wrt relu2's output), st2 = mask1 * (K2 g_a2) (wrt relu1's)
   float* st1;
   float* st2;
-  void* pad;             // always null: keeps the kernel arguments at 264 bytes (256 moves the hidden arguments and changes the code)
+  int pw;                // the level's width w where the forward 16x16x32 kernels may add conv3's horizontal taps in registers (c = 8, 16;
+                         // w a power of two in [4, 16]: a 16-pixel half holds whole image rows) and write P as [3 c][Q], row (dy + 1) c + co
+                         // (c3_presum_store); 0: per-tap P [9 c][Q].  The level shape alone decides it, never the batch size
+  int pad;               // always 0: keeps the kernel arguments at 264 bytes (256 moves the hidden arguments and changes the code)
 };
+static_assert(sizeof(NetArgs) == 264, "kernel argument size");
 
 // cache modifier of the planar hidden stores: they are streamed (gigabytes per launch, read back by the weight-gradient GEMMs after the
 // level's sweep), so non-temporal -- measured -1.7 % on a 256-tile parameter-gradient sweep against "" on one box, neutral at 32 tiles
@@ -1129,6 +1133,8 @@ struct RingS {
   static constexpr bool STK = !BWD && glowk_conv1_stacked(K1);
   static constexpr int KSX = STK ? glowk_conv1_ks_stacked(K1) : KS;
   static constexpr int M3 = MOUT;
+  static constexpr bool C3P = !BWD && MOUT % 9 == 0 && glowk_conv3_permuted(MOUT / 9);   // forward image at c = 8, 16: conv3's rows in the
+                                                                  // triplet order of the pre-sum (glowk_act_scale.h: glowk_conv3_row; c3_presum_store)
   static constexpr int NMT = (M3 + 15) / 16;                      // 16-row blocks of P
   static constexpr int TPC = MAINP / 2;                           // conv3 tiles (16 rows x 32 k, hi + lo) per chunk
   static constexpr int NT = NFH * NMT;                            // conv3 tiles per pass
@@ -1179,6 +1185,53 @@ __device__ __forceinline__ f32x4 mfma3s(const h8& ahi, const h8& alo, const h8& 
   if (!TWO) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc, 0, 0, 0);
   return acc;
+}
+
+// ---- conv3's horizontal taps added in registers (c = 8, 16: RingS::C3P; row order of the image: glowk_act_scale.h) ----
+// natural row tap * c + channel of P -- the store row of the per-tap layout, the index of its per-row constant -- held in register
+// r of row tile mt by lane group kq (>= MOUT: a padding row, nothing is stored)
+template <class G>
+__device__ __forceinline__ int c3_row(int mt, int r, int kq) {
+  if constexpr (G::C3P) return glowk_conv3_row(G::M3 / 9, mt * 16 + r) + kq;
+  else return mt * 16 + 4 * kq + r;
+}
+// the value of the lane one pixel to the left / right within the DPP row of 16 lanes (= the 16-pixel half); 0 at the row's end
+__device__ __forceinline__ float dpp_row_shr1(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));     // row_shr:1 bound_ctrl:0
+}
+__device__ __forceinline__ float dpp_row_shl1(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xf, 0xf, true));     // row_shl:1 bound_ctrl:0
+}
+// The finished (scaled, bias included) sums of an accumulator group of GN row tiles: registers 3 u, 3 u + 1, 3 u + 2 of a lane are
+// the taps dx = -1, 0, +1 of row T = T0 + 4 u + kq of the pre-summed P.  Output pixel j takes tap dx from pixel j + dx:
+//     R = (shr1(P_-1) + P_0) + shl1(P_+1),
+// the shifts zero-filling at the ends of the 16-lane row, which is the convolution's zero padding when w = 16; w = 8, 4 (a half holds
+// 16 / w image rows): the shifted value is also dropped where the lane is the first / last pixel of its image row.  Two VALU
+// instructions per stored value; every lane takes part in the shifts, the pixel guard is on the store alone.
+template <int GN, int PXH, int NA>
+__device__ __forceinline__ void c3_presum_store(const f32x4 (&acc3)[NA][2], float* Pp, int Q, int pw, int T0, const int (&q)[2], const bool (&qok)[2],
+                                                int lane, int kq) {
+  static_assert(GN <= NA, "group");
+  const int jw = lane & (pw - 1);
+  const bool inner = pw < 16, zl = inner && jw == 0, zr = inner && jw == pw - 1;
+  float* row = Pp + (size_t)(T0 + kq) * Q;
+#pragma unroll
+  for (int hf = 0; hf < PXH; ++hf)
+#pragma unroll
+    for (int u = 0; u < 4 * GN / 3; ++u) {
+      const int s = 3 * u;
+      float l = dpp_row_shr1(acc3[s / 4][hf][s % 4]), rr = dpp_row_shl1(acc3[(s + 2) / 4][hf][(s + 2) % 4]);
+      if (inner) { l = zl ? 0.0f : l; rr = zr ? 0.0f : rr; }
+      const float R = (l + acc3[(s + 1) / 4][hf][(s + 1) % 4]) + rr;
+      if (qok[hf]) row[(size_t)(4 * u) * Q + q[hf]] = R;
+    }
+}
+template <int PXH, int NA>
+__device__ __forceinline__ void c3_presum_group(const f32x4 (&acc3)[NA][2], int gn, float* Pp, int Q, int pw, int T0, const int (&q)[2],
+                                                const bool (&qok)[2], int lane, int kq) {      // (gn: static at every call site)
+  if (gn == 6) { if constexpr (NA >= 6) c3_presum_store<6, PXH>(acc3, Pp, Q, pw, T0, q, qok, lane, kq); }
+  else if (gn == 5) { if constexpr (NA >= 5) c3_presum_store<5, PXH>(acc3, Pp, Q, pw, T0, q, qok, lane, kq); }
+  else c3_presum_store<3, PXH>(acc3, Pp, Q, pw, T0, q, qok, lane, kq);
 }
 
 // activation + split of one hidden block (two row blocks) of one pixel half -> the B fragment of the next contraction.
@@ -1459,11 +1512,23 @@ __device__ __forceinline__ void h3s_Z(const NetArgs& a, const H3Ctx& c, const fl
       acc3[ml][0] = mfma3s<net_dir<MODE> == NET_FWD2>(ah, al, bh[0], bl[0], acc3[ml][0]);
       if constexpr (G::PXH == 2) acc3[ml][1] = mfma3s<net_dir<MODE> == NET_FWD2>(ah, al, bh[1], bl[1], acc3[ml][1]);
       if (fo == NFH - 1) {
+        if constexpr (G::C3P) {
+          static_assert(!MERGE && !G::FUSE, "the pre-sum writes per-pass partials");
+          if (a.pw) {     // (wave-uniform) the tile's sums stay in acc3, scaled; the group's last tile adds the horizontal taps and stores
+#pragma unroll
+            for (int hf = 0; hf < G::PXH; ++hf)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                acc3[ml][hf][r] = PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[c3_row<G>(mt, r, kq)]) : acc3[ml][hf][r] * a.sc3;
+            if (ml == G::grp_n(mt / 6) - 1) c3_presum_group<G::PXH>(acc3, G::grp_n(mt / 6), Pp, a.Q, a.pw, 32 * (mt / 6), q, qok, lane, kq);
+            continue;
+          }
+        }
 #pragma unroll
         for (int hf = 0; hf < G::PXH; ++hf)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int m = mt * 16 + 4 * kq + r;
+            const int m = c3_row<G>(mt, r, kq);
             const float val = net_dir<MODE> == NET_BWD ? acc3[ml][hf][r] * (a.sc3 * c.ub[hf])
                               : PASS == 0 ? fmaf(acc3[ml][hf][r], a.sc3, pb[m]) : acc3[ml][hf][r] * a.sc3;
             if (MERGE && PASS == 0) { keep[ml][hf][r] = val; continue; }     // pass 1 adds it and stores once

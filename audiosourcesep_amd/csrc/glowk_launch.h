@@ -34,6 +34,8 @@ struct NetLaunch {
   int fused_px = 0;         // > 0: the coupling ran inside the kernel (fused_couple), in workgroups of this many pixels: no P was
                             // written, the step's output is in place but for the rows k_couple_edge finishes
   bool failed = false;      // launch_fail() has set glowk_last_error()
+  bool presum = false;      // P was written with conv3's horizontal taps already added: [3 c][Q] per partial (NetArgs::pw; the forward
+                            // launches of the 16x16x32 families at c = 8, 16) -- the coupling kernel is told (CoupleArgs::presum)
   explicit operator bool() const { return np > 0 || fused_px > 0; }   // a form was taken
 };
 
@@ -55,6 +57,7 @@ struct EnvSwitches {
   bool co_train_off;        // GLOWK_CO_TRAIN_OFF: the training sweep stays on the 32x32x16 family
   bool train_recompute;     // GLOWK_TRAIN_RECOMPUTE: the training sweep recomputes each step's forward pass instead of keeping it
   bool train_perstep;       // GLOWK_TRAIN_PERSTEP: one saving forward launch per step instead of the level's chain
+  bool no_presum;           // GLOWK_NO_PRESUM: the forward 16x16x32 kernels write per-tap P at the 8- and 16-channel levels too (NetArgs::pw = 0)
   bool pg_join;             // GLOWK_PG_JOIN: glowk_param_grad joins the caller's stream on the host first, as before the side stream
 };
 const EnvSwitches& env();
@@ -374,6 +377,8 @@ NetLaunch launch_net_t(const NetArgs& a, NetCall call, hipStream_t s, bool dry) 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return net_failed(std::string("k_net: ") + hipGetErrorString(e));
   }
+  // every forward form of the 16x16x32 families closes with the same conv3 ops (h3s_Z / co_Z), which pre-sum where the host set the width
+  r.presum = a.pw != 0 && call.dir != NET_BWD && (r.family == FAM_H3S || r.family == FAM_H3S_HALF) && RingS<CI, 18 * CI, NF, NET_FWD, 2>::C3P;
   return r;
 }
 

@@ -134,6 +134,8 @@ struct CoupleArgs {
   const float* P;       // [9C][Q] per-tap partial conv3 outputs of the network evaluated on vin[.., C/2:]
   int np;               // number of partial P buffers (f16x3 kernels: one per pass over the hidden width), >= 1
   size_t pstride;       // floats between them
+  int presum;           // 1: the network kernel has added conv3's horizontal taps (NetLaunch::presum): P is [3C][Q], row (dy + 1) C + co, and
+                        // output(q) = sum over dy with 0 <= i + dy < h, over the partials, of P[(dy + 1) C + co][q + dy w] (c = 8, 16 only)
   const float* b3;      // [C] conv3 bias
   const float* A;       // post affine [C][C] or null: forward = NEXT step's ActNorm+1x1, inverse = this step's inverse 1x1+ActNorm
   const float* b;       // [C]
@@ -164,14 +166,67 @@ __device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.0e3
 // following affine, store.  Returns the pixel's sum of log_s on the lane that finished it (lane 0 of a quad), 0 elsewhere.
 // LPP lanes per pixel: 1 (the same sums in the same order as 4, on one lane), 4 (lane r: taps r, r + 4, r + 8 of every partial) or 16 (the (tap, partial) pairs dealt round robin: the
 // deep levels at small batches, where 64 pixels x 16 channels x 4 partials are ~200 dependent loads per lane of a 4-lane kernel)
-template <int C, int LPP>
+// PRE: the pre-summed layout (CoupleArgs::presum): three row blocks dy = -1, 0, +1 instead of nine taps.  LPP = 4: lane r < 3 of the quad
+// takes dy = r - 1, lane 3 nothing, the quad's butterfly leaves (s0 + s1) + (s2 + 0); LPP = 1 adds in that order; LPP = 16 deals the
+// (dy, partial) pairs round robin.
+template <int C, int LPP, bool PRE = false>
 __device__ __forceinline__ float couple_pixel(const CoupleArgs& a, int q, int i, int j, bool live, int r4) {
   constexpr int CI = C / 2;
   constexpr bool QUAD = LPP == 4;
   float v[C], o[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) o[c] = 0.0f;
-  if constexpr (LPP == 16) {
+  if constexpr (PRE && LPP == 16) {
+    for (int idx = r4; idx < 3 * a.np; idx += 16) {
+      const int dyi = idx / a.np, part = idx % a.np;
+      const int dy = dyi - 1, ii = i + dy;
+      if (ii >= 0 && ii < a.h) {
+        const float* src = a.P + (size_t)part * a.pstride + (size_t)(dyi * C) * a.Q + (q + dy * a.w);
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c] += src[(size_t)c * a.Q];
+      }
+    }
+  } else if constexpr (PRE && LPP == 1) {
+    float s2[C];      // (the order of the four-lane form: (s0 + s1) + (s2 + 0), every s_r summed over the partials from zero)
+#pragma unroll
+    for (int c = 0; c < C; ++c) s2[c] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      float t[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) t[c] = 0.0f;
+      const int dy = r - 1, ii = i + dy;
+      if (ii >= 0 && ii < a.h) {
+        const size_t off = (size_t)(r * C) * a.Q + (q + dy * a.w);
+#pragma unroll
+        for (int part = 0; part < 4; ++part)
+          if (part < a.np) {
+            const float* src = a.P + (size_t)part * a.pstride + off;
+#pragma unroll
+            for (int c = 0; c < C; ++c) t[c] += src[(size_t)c * a.Q];
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        if (r < 2) o[c] += t[c];
+        else s2[c] += t[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] += s2[c] + 0.0f;
+  } else if constexpr (PRE) {
+    const int dy = r4 - 1, ii = i + dy;
+    if (r4 < 3 && ii >= 0 && ii < a.h) {
+      const size_t off = (size_t)(r4 * C) * a.Q + (q + dy * a.w);
+#pragma unroll
+      for (int part = 0; part < 4; ++part)      // all partials' loads in flight together
+        if (part < a.np) {
+          const float* src = a.P + (size_t)part * a.pstride + off;
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[c] += src[(size_t)c * a.Q];
+        }
+    }
+  } else if constexpr (LPP == 16) {
     for (int idx = r4; idx < 9 * a.np; idx += 16) {
       const int tap = idx / a.np, part = idx % a.np;
       const int dy = tap / 3 - 1, dx = tap % 3 - 1;
@@ -355,7 +410,7 @@ __device__ __forceinline__ float couple_pixel(const CoupleArgs& a, int q, int i,
   return lsum;
 }
 
-template <int C, bool QUAD>
+template <int C, bool QUAD, bool PRE = false>
 __global__ __launch_bounds__(QUAD ? 1024 : 256) void k_couple(CoupleArgs a) {   // QUAD: 256 .. 1024 threads; else 256
   __shared__ double red[16];
   const int n = blockIdx.x;
@@ -369,7 +424,7 @@ __global__ __launch_bounds__(QUAD ? 1024 : 256) void k_couple(CoupleArgs a) {   
   for (int pp0 = QUAD ? threadIdx.x >> 2 : threadIdx.x; pp0 < (hw + qpb - 1) / qpb * qpb; pp0 += qpb) {
     const bool live = pp0 < hw;
     const int pp = live ? pp0 : hw - 1;
-    lsum += couple_pixel<C, QUAD ? 4 : 1>(a, n * hw + pp, pp / a.w, pp % a.w, live, r4);
+    lsum += couple_pixel<C, QUAD ? 4 : 1, PRE>(a, n * hw + pp, pp / a.w, pp % a.w, live, r4);
   }
   if (a.logdet) {
     const double tot = block_sum_any((double)lsum, red);
@@ -382,7 +437,7 @@ __global__ __launch_bounds__(QUAD ? 1024 : 256) void k_couple(CoupleArgs a) {   
 // that they belong to one sample.  Its share of the sample's log-det goes to a slot of its own -- one slot per 16 pixels of a level:
 // slot[n * sample_stride + slot_base + first 16-pixel unit of the workgroup]; no two workgroups add to one address, the order of the
 // final sum (k_ld_fold) is fixed.
-template <int C, int LPP>
+template <int C, int LPP, bool PRE = false>
 __global__ __launch_bounds__(256) void k_couple_flat(CoupleArgs a, double* slot, int sample_stride, int slot_base) {
   __shared__ double red[4];
   constexpr int PPB = 256 / LPP;
@@ -391,7 +446,7 @@ __global__ __launch_bounds__(256) void k_couple_flat(CoupleArgs a, double* slot,
   const bool live = q0 < a.Q;
   const int q = live ? q0 : a.Q - 1;
   const int pp = q % hw;
-  const float lsum = couple_pixel<C, LPP>(a, q, pp / a.w, pp % a.w, live, threadIdx.x & (LPP - 1));
+  const float lsum = couple_pixel<C, LPP, PRE>(a, q, pp / a.w, pp % a.w, live, threadIdx.x & (LPP - 1));
   if (slot) {
     const double tot = block_sum_256((double)lsum, red);
     const int first = (int)blockIdx.x * PPB;

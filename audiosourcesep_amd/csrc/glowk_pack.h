@@ -557,7 +557,7 @@ bool pack_step(const glowk_config& cfg, const Level& lv, int k, float* dst, doub
                   if (t < NT) {
                     const int gi = t / (NFH * 6), gn = NMS - 6 * gi < 6 ? NMS - 6 * gi : 6, tl = t - gi * NFH * 6;   // RingS::tile_fo / tile_mt
                     const int fo = tl / gn, mt = 6 * gi + tl % gn;
-                    const int m = mt * 16 + i, f = (ps * NFH + fo) * 32 + kloc;
+                    const int m = glowk_conv3_row(CO, mt * 16 + i), f = (ps * NFH + fo) * 32 + kloc;   // (c = 8, 16: the triplet order of the pre-sum)
                     if (m < 9 * CO) { const int tap = m / CO, co = m % CO; w = K3f[((size_t)tap * F + f) * CO + co]; }
                   }
                 }
