@@ -8,11 +8,6 @@ thread_local std::string g_err;
 }
 using namespace glowk_eng;
 
-namespace glowk_eng {
-
-// ---- launch helpers (policy templates: glowk_launch.h) --------------------------------------------
-}  // namespace glowk_eng
-
 namespace glowk_detail {
 int num_cus() {
   static int n = 0;
@@ -96,18 +91,25 @@ int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipSt
   return r.failed ? 1 : 0;
 }
 
-
 // light backward kernel of one step: 16 lanes per pixel where the batch is small and the level deep (few pixels, many channels and
 // partial buffers: the gathers' dependent loads are what the launch waits for), one where the grid is large, else 4
-int launch_bwd_light(int c, const BwdArgs& a, int N, hipStream_t s) {
-  const bool wide = c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus() && !glowk_detail::env().bwd_light_4;
+int bwd_light_lanes(int c, const BwdArgs& a) {
+  if (glowk_detail::env().bwd_light_4) return 4;
   // large grids: one lane per pixel (the planar Pg gathers and the 16-byte rows of the [Q][C] arrays are then fully coalesced)
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool one = (a.Q + 255) / 256 >= 2 * num_cus() && al16(a.ghalf_in) && al16(a.v) && al16(a.osave) && al16(a.g_o) && al16(a.ghalf_out) &&
-                   al16(a.gu_out) && al16(a.gv_out) && !glowk_detail::env().bwd_light_4;
-  if (one) { CDISPATCH(c, hipLaunchKernelGGL((k_bwd_light<CC, 1>), dim3((a.Q + 255) / 256), dim3(256), 0, s, a)); }
-  else if (wide) { CDISPATCH(c, hipLaunchKernelGGL((k_bwd_light<CC, 16>), dim3((a.Q + 15) / 16), dim3(256), 0, s, a)); }
-  else { CDISPATCH(c, hipLaunchKernelGGL((k_bwd_light<CC, 4>), dim3((a.Q + 63) / 64), dim3(256), 0, s, a)); }
+  if ((a.Q + 255) / 256 >= 2 * num_cus() && al16(a.ghalf_in) && al16(a.v) && al16(a.osave) && al16(a.g_o) && al16(a.ghalf_out) &&
+      al16(a.gu_out) && al16(a.gv_out)) return 1;
+  return c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus() ? 16 : 4;
+}
+
+int launch_bwd_light(int c, const BwdArgs& a, hipStream_t s) {
+#define BWD_LIGHT(LPP_) CDISPATCH(c, hipLaunchKernelGGL((k_bwd_light<CC, LPP_>), dim3((a.Q + 256 / LPP_ - 1) / (256 / LPP_)), dim3(256), 0, s, a))
+  switch (bwd_light_lanes(c, a)) {
+    case 1: BWD_LIGHT(1); break;
+    case 16: BWD_LIGHT(16); break;
+    default: BWD_LIGHT(4);
+  }
+#undef BWD_LIGHT
   LAUNCHCHK("k_bwd_light");
   return 0;
 }
@@ -115,44 +117,47 @@ int launch_bwd_light(int c, const BwdArgs& a, int N, hipStream_t s) {
 // log-det slots of the flat-grid coupling kernel (k_couple_flat): slot[n * stride + base + workgroup within the sample]
 struct FlatLd { double* slot; int stride, base; };
 
-// (a.presum: the instances that read the pre-summed P, which only the 8- and 16-channel levels write)
+// Launch form of the coupling: a flat grid over the pixels (k_couple_flat: 4 or 16 lanes per pixel, 256 threads) or one workgroup of
+// `threads` per sample (k_couple: 1 or 4 lanes per pixel)
+struct CoupleForm { bool flat; int lanes, threads; };
+
+// slots: the caller has log-det slots for the flat grid (FlatLd), which a launch with a log-det needs there
+CoupleForm couple_form(int c, const CoupleArgs& a, int N, bool slots) {
+  const int hw = a.h * a.w;
+  // few samples: a flat grid over the pixels instead of one workgroup per sample (30 tiles: 30 workgroups on 256 CUs); sixteen
+  // lanes per pixel where the level is deep (c >= 8) and small
+  if (N < 2 * num_cus() && hw % 64 == 0 && (!a.logdet || slots)) return {true, c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus() ? 16 : 4, 256};
+  if (N >= 2 * num_cus()) return {false, 1, 256};   // enough per-sample workgroups to fill the chip: one lane per pixel
+  return {false, 4, hw >= 256 ? 1024 : hw > 64 ? 512 : 256};   // four lanes per pixel, up to 256 pixels in flight per sample
+}
+
+// (PDISPATCH: the instances that read the pre-summed P, which only the 8- and 16-channel levels write; the launches keep their order, and so the kernels their offsets)
 #define PDISPATCH(c, CALL)                                                                     \
   switch (c) {                                                                                 \
     case 8: { constexpr int CC = 8; CALL; } break;                                             \
     case 16: { constexpr int CC = 16; CALL; } break;                                           \
     default: return fail("pre-summed P at channel count " + std::to_string(c));                \
   }
+#define COUPLE_FLAT(DISPATCH, LPP_, PRE_) \
+  DISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, LPP_, PRE_>), dim3((a.Q + 256 / LPP_ - 1) / (256 / LPP_)), dim3(256), 0, s, a, slots, stride, base))
+#define COUPLE_TILE(DISPATCH, QUAD_, PRE_) DISPATCH(c, hipLaunchKernelGGL((k_couple<CC, QUAD_, PRE_>), dim3(N), dim3(f.threads), 0, s, a))
 
-int launch_couple(int c, const CoupleArgs& a, int N, hipStream_t s, const FlatLd* fl = nullptr, bool* flat_used = nullptr) {
-  const int hw = a.h * a.w;
-  if (N < 2 * num_cus() && hw % 64 == 0 && (!a.logdet || (fl && fl->slot))) {
-    // few samples: a flat grid over the pixels instead of one workgroup per sample (30 tiles: 30 workgroups on 256 CUs); sixteen
-    // lanes per pixel where the level is deep (c >= 8) and small
-    CoupleArgs b = a;
-    b.logdet = nullptr;
-    double* slots = a.logdet ? fl->slot : (double*)nullptr;
-    const bool wide = c >= 8 && (a.Q + 15) / 16 <= 8 * num_cus();
-    if (a.presum) {
-      if (wide) { PDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16, true>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
-      else { PDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 4, true>), dim3((a.Q + 63) / 64), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
-    }
-    else if (wide) { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 16>), dim3((a.Q + 15) / 16), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
-    else { CDISPATCH(c, hipLaunchKernelGGL((k_couple_flat<CC, 4>), dim3((a.Q + 63) / 64), dim3(256), 0, s, b, slots, fl ? fl->stride : 0, fl ? fl->base : 0)); }
-    LAUNCHCHK("k_couple_flat");
-    if (flat_used && a.logdet) *flat_used = true;
-    return 0;
-  }
-  if (N >= 2 * num_cus()) {   // enough per-sample workgroups to fill the chip: one lane per pixel
-    if (a.presum) { PDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, false, true>), dim3(N), dim3(256), 0, s, a)); }
-    else { CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, false>), dim3(N), dim3(256), 0, s, a)); }
-  } else {                    // four lanes per pixel, up to 256 pixels in flight per sample
-    const int threads = hw >= 256 ? 1024 : hw > 64 ? 512 : 256;
-    if (a.presum) { PDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, true, true>), dim3(N), dim3(threads), 0, s, a)); }
-    else { CDISPATCH(c, hipLaunchKernelGGL((k_couple<CC, true>), dim3(N), dim3(threads), 0, s, a)); }
-  }
-  LAUNCHCHK("k_couple");
+int launch_couple(int c, CoupleArgs a, int N, hipStream_t s, const FlatLd* fl = nullptr, bool* flat_used = nullptr) {
+  const CoupleForm f = couple_form(c, a, N, fl && fl->slot);
+  double* slots = f.flat && a.logdet ? fl->slot : nullptr;   // flat: the log-det goes to the slots (k_ld_fold adds them up)
+  if (slots && flat_used) *flat_used = true;
+  if (f.flat) a.logdet = nullptr;
+  const int stride = fl ? fl->stride : 0, base = fl ? fl->base : 0;
+  if (f.flat && a.presum) { if (f.lanes == 16) { COUPLE_FLAT(PDISPATCH, 16, true); } else { COUPLE_FLAT(PDISPATCH, 4, true); } }
+  else if (f.flat) { if (f.lanes == 16) { COUPLE_FLAT(CDISPATCH, 16, false); } else { COUPLE_FLAT(CDISPATCH, 4, false); } }
+  else if (f.lanes == 1) { if (a.presum) { COUPLE_TILE(PDISPATCH, false, true); } else { COUPLE_TILE(CDISPATCH, false, false); } }
+  else { if (a.presum) { COUPLE_TILE(PDISPATCH, true, true); } else { COUPLE_TILE(CDISPATCH, true, false); } }
+  LAUNCHCHK((f.flat ? "k_couple_flat" : "k_couple"));
   return 0;
 }
+#undef COUPLE_TILE
+#undef COUPLE_FLAT
+#undef PDISPATCH
 
 // One flow step's coupling network + coupling.  Plain forward direction of the split arithmetics at the 4-channel level with a grid
 // that fills the chip: ONE kernel (k_net_h3s<..., MODE | NET_FUSE>: the per-tap conv3 outputs never leave the workgroup) plus
@@ -164,6 +169,20 @@ bool fuse_geometry_ok(int h, int w, int pxw = 256) {     // pxw: pixels per work
   if (w < 4 || w > FUSE_EW || (w & (w - 1)) || pxw % w) return false;
   if (hw % pxw == 0) return true;
   return hw >= 32 && hw < pxw && (hw & (hw - 1)) == 0;
+}
+
+// k_couple_edge after the fused launch na of the coupling ca, in workgroups of pxw pixels
+EdgeArgs edge_args(const CoupleArgs& ca, const NetArgs& na, int pxw) {
+  EdgeArgs ea;
+  ea.vin = ca.vin; ea.edge = na.fz_edge; ea.ldpart = na.fz_ldpart; ea.A = ca.A; ea.b = ca.b;
+  ea.out = ca.out; ea.out_stride = ca.out_stride; ea.out_off = ca.out_off; ea.inverse = ca.inverse;
+  ea.logdet = ca.logdet; ea.osave = ca.o_save; ea.h = ca.h; ea.w = ca.w; ea.flag = ca.flag; ea.pxw = pxw;
+  return ea;
+}
+// the coupling a reading what the network launch r left in P
+CoupleArgs couple_reads(CoupleArgs a, const float* P, size_t pstride, const NetLaunch& r) {
+  a.P = P; a.np = r.np; a.pstride = pstride; a.presum = r.presum ? 1 : 0;
+  return a;
 }
 
 int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArgs ca, int N, hipStream_t s, NetCall call, const FlatLd* fl = nullptr,
@@ -190,27 +209,17 @@ int net_and_couple(glowk_handle* h, int lvl, int c, int F, NetArgs na, CoupleArg
   }
   NetLaunch r;
   if (int rc = launch_net(h, lvl, c, F, na, s, call, &r)) return rc;
-  if (!r.fused_px) {
-    ca.P = na.P; ca.np = r.np; ca.pstride = na.pstride; ca.presum = r.presum ? 1 : 0;
-    return launch_couple(c, ca, N, s, fl, flat_used);
-  }
+  if (!r.fused_px) return launch_couple(c, couple_reads(ca, na.P, na.pstride, r), N, s, fl, flat_used);
   ++h->fused_steps;
   const int pxw = r.fused_px;
   if (hw > pxw || ca.logdet) {
-    EdgeArgs ea;
-    ea.vin = ca.vin; ea.edge = na.fz_edge; ea.ldpart = na.fz_ldpart; ea.A = ca.A; ea.b = ca.b; ea.out = ca.out; ea.out_stride = ca.out_stride;
-    ea.out_off = ca.out_off; ea.inverse = ca.inverse; ea.logdet = ca.logdet; ea.osave = ca.o_save; ea.h = ca.h; ea.w = ca.w; ea.flag = ca.flag; ea.pxw = pxw;
-    hipLaunchKernelGGL(k_couple_edge, dim3(N), dim3(256), 0, s, ea);
+    hipLaunchKernelGGL(k_couple_edge, dim3(N), dim3(256), 0, s, edge_args(ca, na, pxw));
     LAUNCHCHK("k_couple_edge");
   }
   return 0;
 }
 
-PreArgs pre_args(const glowk_config& cfg) {
-  PreArgs p;
-  p.minval = cfg.minval; p.maxval = cfg.maxval; p.alpha = cfg.alpha; p.use_logit = cfg.use_logit;
-  return p;
-}
+PreArgs pre_args(const glowk_config& cfg) { return PreArgs{cfg.minval, cfg.maxval, cfg.alpha, cfg.use_logit}; }
 
 // ---- device memory of a handle: ONE description of every buffer, used by the allocators and by glowk_workspace_bytes ----
 struct WsSizes {      // forward / inverse workspace for N tiles (bytes)
@@ -319,7 +328,6 @@ int max_tiles(const glowk_handle* h) {
   return m < 1 ? 1 : (int)m;
 }
 
-
 int check_batch(const glowk_handle* h, int N) {
   if (N <= 0) return fail("batch size must be positive");
   if (N > max_tiles(h)) return fail("batch of " + std::to_string(N) + " tiles exceeds glowk_max_tiles() = " + std::to_string(max_tiles(h)) +
@@ -336,21 +344,39 @@ int check_ready(glowk_handle* h, int N) {
   return ensure_ws(h, N);
 }
 
+// The network launch of step sd of level lv on vin, as the plain forward network takes it (the gradient path's launches add their masks,
+// the backward network swaps in its own images, net_and_couple adds the coupling of a fused launch)
 NetArgs net_args(glowk_handle* h, const Level& lv, const StepDev& sd, const float* vin, int in_stride, int in_off, int N) {
   NetArgs a;
   a.vin = vin; a.in_stride = in_stride; a.in_off = in_off;
   a.Q = N * lv.h * lv.w; a.h = lv.h; a.w = lv.w;
-  a.K1p = sd.K1p; a.ep = sd.ep; a.R0p = sd.R0p; a.mask1 = nullptr; a.mask2 = nullptr; a.P = h->bufP;
-  a.RHp = sd.RHp; a.RSp = sd.RSp; a.fam16 = (sd.RSp && sd.RSBp) ? 1 : 0; a.eph = sd.epH; a.pstride = h->pstride; a.max_np = 4; a.sc1 = sd.sc1; a.sc2 = sd.sc2; a.sc3 = sd.sc3;
-  a.flag = flagp(h); a.xlim = sd.xlim_f; a.st1 = nullptr; a.st2 = nullptr;
-  a.bnorm = 1.0f;
-  a.fuse = 0; a.co = glowk_detail::env().co_off ? 0 : 1; a.fz_osave = nullptr; a.fz_b3 = nullptr; a.fz_A = nullptr; a.fz_b = nullptr; a.fz_out = nullptr; a.fz_out_stride = 0; a.fz_out_off = 0; a.fz_inverse = 0;
-  a.fz_edge = nullptr; a.fz_ldpart = nullptr;
+  a.K1p = sd.K1p; a.ep = sd.ep; a.R0p = sd.R0p; a.P = h->bufP; a.pstride = h->pstride;
+  a.RHp = sd.RHp; a.RSp = sd.RSp; a.fam16 = (sd.RSp && sd.RSBp) ? 1 : 0; a.eph = sd.epH; a.sc1 = sd.sc1; a.sc2 = sd.sc2; a.sc3 = sd.sc3;
+  a.flag = flagp(h); a.xlim = sd.xlim_f;
+  a.co = glowk_detail::env().co_off ? 0 : 1;
   // conv3's horizontal taps added in the forward 16x16x32 kernels (c3_presum_store): the level shape alone decides, so that every launch
   // form of a shape -- whatever the batch size selects -- writes the same layout and adds in the same order
   a.pw = (!glowk_detail::env().no_presum && (lv.c == 8 || lv.c == 16) && lv.w >= 4 && lv.w <= 16 && (lv.w & (lv.w - 1)) == 0) ? lv.w : 0;
-  a.pad = 0;
   a.xmax_out = h->d_probe ? h->d_probe + ((&lv - h->levels.data()) * h->cfg.K + (&sd - lv.dev.data())) : nullptr;
+  return a;
+}
+
+// The coupling of step sd of level lv on vin, result to out (element (q, co) at out[q * out_stride + out_off + co]; null: none).  The
+// caller adds what its call has beyond that (the following affine, log-det, saves, dumps); which P the kernel reads is the network
+// launch's answer (couple_reads).
+CoupleArgs couple_args(const glowk_handle* h, const Level& lv, const StepDev& sd, const float* vin, int N, int inverse, float* out,
+                       int out_stride, int out_off = 0) {
+  CoupleArgs a;
+  a.vin = vin; a.b3 = sd.b3; a.out = out; a.out_stride = out_stride; a.out_off = out_off;
+  a.Q = N * lv.h * lv.w; a.h = lv.h; a.w = lv.w; a.inverse = inverse; a.flag = flagp(h);
+  return a;
+}
+
+// The light backward launch of level lv: geometry, flag and the scale that undoes the sweep's power of two on the network gradients
+// (bfac: BwdArgs::go_scale of the level's launches that write g_o).  The caller adds the gradient's source, the affine and the coupling.
+BwdArgs bwd_args(const glowk_handle* h, const Level& lv, int N, float bfac) {
+  BwdArgs a;
+  a.Q = N * lv.h * lv.w; a.h = lv.h; a.w = lv.w; a.flag = flagp(h); a.pg_scale = 1.0f / bfac;
   return a;
 }
 
@@ -408,20 +434,12 @@ int run_forward(glowk_handle* h, const float* x, int N, float* z_dst, hipStream_
         na.st1 = h->trKeep + h->trKeepOff[sidx] * (size_t)N;
         na.st2 = na.st1 + (size_t)cfg.F * Q;
       }
-      CoupleArgs ca;
-      ca.presum = 0;
-      ca.vin = cur; ca.b3 = sd.b3; ca.logdet = h->bufLd; ca.log_s_out = nullptr; ca.t_out = nullptr;
-      ca.o_save = save ? h->saveP + h->offP[sidx] : nullptr;
-      ca.Q = (int)Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
       float* next = save && k > 0 ? h->saveV + h->offV[sidx + 1] : oth;
-      if (k > 0) {
-        ca.A = lv.dev[k - 1].Afwd; ca.b = lv.dev[k - 1].bfwd;
-        ca.out = next; ca.out_stride = lv.c; ca.out_off = 0;
-      } else if (lvl < L - 1) {
-        ca.A = nullptr; ca.b = nullptr; ca.out = oth; ca.out_stride = lv.c; ca.out_off = 0;
-      } else {
-        ca.A = nullptr; ca.b = nullptr; ca.out = z_dst; ca.out_stride = h->Cl; ca.out_off = lv.z_off;
-      }
+      const bool last = k == 0 && lvl == L - 1;    // the last step of all writes its slice of the latent
+      CoupleArgs ca = last ? couple_args(h, lv, sd, cur, N, 0, z_dst, h->Cl, lv.z_off) : couple_args(h, lv, sd, cur, N, 0, k > 0 ? next : oth, lv.c);
+      ca.logdet = h->bufLd;
+      if (save) ca.o_save = h->saveP + h->offP[sidx];
+      if (k > 0) { ca.A = lv.dev[k - 1].Afwd; ca.b = lv.dev[k - 1].bfwd; }    // the next step's ActNorm + 1x1
       const FlatLd fl{flat_ok ? h->bufLdSlot : nullptr, nslots, slot_base};
       slot_base += (lv.h * lv.w + 15) / 16;
       if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, na, ca, N, s, call, &fl, &flat_used)) return rc;
@@ -475,27 +493,27 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
     const bool level_batch = tc && h->trNB == K && K > 1;
     const size_t go_slot = level_batch ? (size_t)Q * lv.c : 0, m_slot = level_batch ? (size_t)cfg.F * Q : 0;
     const ptrdiff_t v_bs = K > 1 ? (ptrdiff_t)h->offV[(size_t)lvl * K] - (ptrdiff_t)h->offV[(size_t)lvl * K + 1] : 0;   // saved inputs: forward order
+    // (1) + (2) of BwdArgs for a launch that merges the network gradient the level's previous launch left in Pg, then goes through step
+    // ks's fused ActNorm + 1x1
+    auto merged = [&](int ks) {
+      BwdArgs ba = bwd_args(h, lv, N, bfac);
+      ba.ghalf_in = gh_a; ba.Pg = Pg; ba.npg = npg; ba.pgstride = h->pstride; ba.A = lv.dev[ks].Afwd;
+      return ba;
+    };
     for (int k = 0; k < K; ++k) {   // reverse of the forward order K-1 .. 0
       const StepDev& sd = lv.dev[k];
       const size_t sidx = (size_t)lvl * K + (K - 1 - k);
-      BwdArgs ba;
-      ba.Q = Q; ba.h = lv.h; ba.w = lv.w; ba.flag = flagp(h);
-      ba.go_scale = bfac; ba.pg_scale = 1.0f / bfac; ba.gmax = (tc && h->tr_gmax) ? h->tr_gmax + 16 * lvl : nullptr;
-      ba.v = h->saveV + h->offV[sidx]; ba.osave = h->saveP + h->offP[sidx];
       float* go_k = tc ? h->trGo + (size_t)k * go_slot : g_o;
-      ba.g_o = go_k; ba.ghalf_out = gh_b; ba.gu_out = nullptr;
-      if (k == 0) {
-        // gradient wrt the block output: the latent slice itself (last block) or what k_bwd_split assembled
-        ba.ghalf_in = nullptr; ba.Pg = nullptr; ba.npg = 1; ba.pgstride = 0; ba.A = nullptr;
-        if (lvl == L - 1) { ba.gv_direct = h->bufGz; ba.gvd_stride = h->Cl; ba.gvd_off = lv.z_off; }
-        else              { ba.gv_direct = gy_src;   ba.gvd_stride = lv.c;  ba.gvd_off = 0; }
-      } else {
-        // merge step k-1's network gradient, go through its fused ActNorm + 1x1, then this step's coupling
-        ba.ghalf_in = gh_a; ba.Pg = Pg; ba.npg = npg; ba.pgstride = h->pstride; ba.gv_direct = nullptr; ba.gvd_stride = 0; ba.gvd_off = 0;
-        ba.A = lv.dev[k - 1].Afwd;
-      }
-      ba.gv_out = (tc && k > 0) ? h->trGv + (size_t)(k - 1) * go_slot : nullptr;
-      if (int rc = launch_bwd_light(lv.c, ba, N, s)) return rc;
+      // gradient wrt the block output: the latent slice itself (last block) or what k_bwd_split assembled -- or merge step k-1's network
+      // gradient and go through its fused ActNorm + 1x1; then this step's coupling
+      BwdArgs ba = k > 0 ? merged(k - 1) : bwd_args(h, lv, N, bfac);
+      if (k == 0 && lvl == L - 1) { ba.gv_direct = h->bufGz; ba.gvd_stride = h->Cl; ba.gvd_off = lv.z_off; }
+      else if (k == 0)            { ba.gv_direct = gy_src;   ba.gvd_stride = lv.c; }
+      ba.go_scale = bfac; ba.gmax = (tc && h->tr_gmax) ? h->tr_gmax + 16 * lvl : nullptr;
+      ba.v = h->saveV + h->offV[sidx]; ba.osave = h->saveP + h->offP[sidx];
+      ba.g_o = go_k; ba.ghalf_out = gh_b;
+      if (tc && k > 0) ba.gv_out = h->trGv + (size_t)(k - 1) * go_slot;
+      if (int rc = launch_bwd_light(lv.c, ba, s)) return rc;
       if (tc && k > 0 && !level_batch)   // g_v of step k-1 is complete: its ActNorm + 1x1 gradient sums
         if (int rc = train_affine_sums(h, lvl, k - 1, 1, h->saveV + h->offV[sidx + 1], 0, h->trGv, 0, N, s)) return rc;
       std::swap(gh_a, gh_b);   // gh_a now holds this step's [g_va, g_yb]
@@ -536,14 +554,10 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
     }
     // first forward step of the block (k = K-1): merge, then through its ActNorm + 1x1 -> g_u of the squeezed block input
     {
-      BwdArgs ba;
-      ba.Q = Q; ba.h = lv.h; ba.w = lv.w; ba.flag = flagp(h);
-      ba.go_scale = 1.0f; ba.pg_scale = 1.0f / bfac; ba.gmax = nullptr;
-      ba.ghalf_in = gh_a; ba.Pg = Pg; ba.npg = npg; ba.pgstride = h->pstride; ba.gv_direct = nullptr; ba.gvd_stride = 0; ba.gvd_off = 0;
-      ba.A = lv.dev[K - 1].Afwd;
-      ba.v = nullptr; ba.osave = nullptr; ba.g_o = nullptr; ba.ghalf_out = nullptr; ba.gu_out = g_o;   // reuse g_o as g_u
-      ba.gv_out = tc ? h->trGv + (size_t)(K - 1) * go_slot : nullptr;
-      if (int rc = launch_bwd_light(lv.c, ba, N, s)) return rc;
+      BwdArgs ba = merged(K - 1);
+      ba.gu_out = g_o;   // reuse g_o as g_u
+      if (tc) ba.gv_out = h->trGv + (size_t)(K - 1) * go_slot;
+      if (int rc = launch_bwd_light(lv.c, ba, s)) return rc;
       if (tc && !level_batch)
         if (int rc = train_affine_sums(h, lvl, K - 1, 1, h->saveV + h->offV[(size_t)lvl * K], 0, h->trGv, 0, N, s)) return rc;
     }
@@ -589,10 +603,8 @@ int run_inverse(glowk_handle* h, const float* z, int N, float* x, hipStream_t s)
     std::swap(cur, oth);
     for (int k = 0; k < K; ++k) {   // Chain.inverse: step 0 first
       const StepDev& sd = lv.dev[k];
-      CoupleArgs ca;
-      ca.vin = cur; ca.P = h->bufP; ca.np = 1; ca.pstride = h->pstride; ca.presum = 0; ca.b3 = sd.b3; ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr; ca.o_save = nullptr;
-      ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
-      ca.A = sd.Ainv; ca.b = sd.binv; ca.out = oth; ca.out_stride = lv.c; ca.out_off = 0;
+      CoupleArgs ca = couple_args(h, lv, sd, cur, N, 1, oth, lv.c);
+      ca.A = sd.Ainv; ca.b = sd.binv;
       if (int rc = net_and_couple(h, lvl, lv.c, cfg.F, net_args(h, lv, sd, cur, lv.c, lv.c / 2, N), ca, N, s, net_call(h, NET_FWD))) return rc;
       std::swap(cur, oth);
     }
@@ -642,7 +654,6 @@ int guarded(glowk_handle* h, hipStream_t s, Run&& run) {
   h->precision = prec;
   return rc;
 }
-
 
 }  // namespace glowk_eng
 
@@ -842,12 +853,9 @@ int run_step_inplace(glowk_handle* h, int lvl, int k, float* cur, float* tmp, in
   LAUNCHCHK("k_affine");
   NetArgs na = net_args(h, lv, sd, tmp, lv.c, lv.c / 2, Nl);
   if (int rc = launch_net(h, lvl, lv.c, h->cfg.F, na, s, NetCall{NET_FWD, NET_EXACT})) return rc;
-  CoupleArgs ca;
-  ca.o_save = nullptr;
-  ca.vin = tmp; ca.P = h->bufP; ca.np = 1; ca.pstride = 0; ca.presum = 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
-  ca.out = cur; ca.out_stride = lv.c; ca.out_off = 0;
-  ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
-  ca.Q = Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = nullptr;
+  CoupleArgs ca = couple_args(h, lv, sd, tmp, Nl, 0, cur, lv.c);
+  ca.P = h->bufP;       // (the exact kernel: one partial)
+  ca.flag = nullptr;
   return launch_couple(lv.c, ca, Nl, s);
 }
 
@@ -1258,12 +1266,8 @@ int glowk_step_forward(glowk_handle* h, int level, int step, const float* u_dev,
       HIPCHK(hipMemcpyAsync(h->bufLd, init.data(), (size_t)N * 8, hipMemcpyHostToDevice, s));
       HIPCHK(hipStreamSynchronize(s));
     }
-    CoupleArgs ca;
-    ca.o_save = nullptr;
-    ca.vin = h->bufA; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
-    ca.out = y_dev; ca.out_stride = lv.c; ca.out_off = 0;
-    ca.logdet = logdet_dev ? h->bufLd : nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
-    ca.Q = Q; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
+    CoupleArgs ca = couple_reads(couple_args(h, lv, sd, h->bufA, N, 0, y_dev, lv.c), h->bufP, h->pstride, r);
+    if (logdet_dev) ca.logdet = h->bufLd;
     if (int rc = launch_couple(lv.c, ca, N, s)) return rc;
     if (logdet_dev) {
       hipLaunchKernelGGL(k_prior, dim3(N), dim3(256), 0, s, (const float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr,
@@ -1286,12 +1290,8 @@ int glowk_step_inverse(glowk_handle* h, int level, int step, const float* y_dev,
   return guarded(h, s, [&]() -> int {
     NetLaunch r;
     if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, y_dev, lv.c, lv.c / 2, N), s, net_call(h, NET_FWD), &r)) return rc;
-    CoupleArgs ca;
-    ca.o_save = nullptr;
-    ca.vin = y_dev; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = sd.Ainv; ca.b = sd.binv;
-    ca.out = u_dev; ca.out_stride = lv.c; ca.out_off = 0;
-    ca.logdet = nullptr; ca.log_s_out = nullptr; ca.t_out = nullptr;
-    ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 1; ca.flag = flagp(h);
+    CoupleArgs ca = couple_reads(couple_args(h, lv, sd, y_dev, N, 1, u_dev, lv.c), h->bufP, h->pstride, r);
+    ca.A = sd.Ainv; ca.b = sd.binv;
     return launch_couple(lv.c, ca, N, s);
   });
 }
@@ -1308,15 +1308,10 @@ int glowk_coupling_net(glowk_handle* h, int level, int step, const float* xb_dev
   return guarded(h, s, [&]() -> int {
     NetLaunch r;
     if (int rc = launch_net(h, level, lv.c, h->cfg.F, net_args(h, lv, sd, xb_dev, lv.c / 2, 0, N), s, net_call(h, NET_FWD), &r)) return rc;
-    CoupleArgs ca;
-    ca.o_save = nullptr;
-    ca.vin = nullptr; ca.P = h->bufP; ca.np = r.np; ca.pstride = h->pstride; ca.presum = r.presum ? 1 : 0; ca.b3 = sd.b3; ca.A = nullptr; ca.b = nullptr;
-    ca.out = nullptr; ca.out_stride = 0; ca.out_off = 0;
-    ca.logdet = nullptr; ca.log_s_out = log_s_dev; ca.t_out = t_dev;
-    ca.Q = N * lv.h * lv.w; ca.h = lv.h; ca.w = lv.w; ca.inverse = 0; ca.flag = flagp(h);
+    CoupleArgs ca = couple_reads(couple_args(h, lv, sd, nullptr, N, 0, nullptr, 0), h->bufP, h->pstride, r);   // the dumps alone
+    ca.log_s_out = log_s_dev; ca.t_out = t_dev;
     return launch_couple(lv.c, ca, N, s);
   });
 }
-
 
 }  // extern "C"

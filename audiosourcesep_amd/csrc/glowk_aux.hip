@@ -76,7 +76,7 @@ int glowk_basis_update_n(float* const* x, const float* const* g, const float* co
   }
   if (n == 0) return 0;
   DeviceGuard dg(ptr_device(x[0]));
-  BasisNArgs a = {};
+  BasisNArgs a;
   uintptr_t bits = (uintptr_t)mixed_dev;
   for (int k = 0; k < nsrc; ++k) {
     a.x[k] = x[k]; a.g[k] = g[k]; a.eps[k] = eps ? eps[k] : nullptr;
@@ -103,7 +103,7 @@ int glowk_basis_mix_n(const float* const* x, int nsrc, float* out_dev, size_t n,
     if (!x[k]) return fail("null tensor");
   if (n == 0) return 0;
   DeviceGuard dg(ptr_device(out_dev));
-  BasisMixNArgs a = {};
+  BasisMixNArgs a;
   for (int k = 0; k < nsrc; ++k) a.x[k] = x[k];
   a.out = out_dev; a.n = n; a.ln_s = (float)std::log((double)nsrc); a.inv_s = 1.0f / (float)nsrc; a.mixing = mixing;
   const dim3 grid((unsigned)((n + 255) / 256));

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> 4 x 32 random bits.  Stateless, so element e of
 // step t of stream w always gets the same draw whatever the grid: counter = (e / 4, t, w, 0), key = seed.
@@ -59,18 +60,19 @@ __device__ __forceinline__ bool basis_bad(float v) { return !(fabsf(v) <= 3.0e38
 #define GLOWK_BASIS_MAX_SOURCES 16
 
 struct BasisNArgs {
-  float* x[GLOWK_BASIS_MAX_SOURCES];           // [n] each, in place
-  const float* g[GLOWK_BASIS_MAX_SOURCES];     // [n] grad log p_k(x_k)
-  const float* eps[GLOWK_BASIS_MAX_SOURCES];   // optional [n] standard-normal draws of source k; null: device RNG (k & 1, pair k >> 1)
-  const float* mixed;   // [n]
-  size_t n;
-  float eta, lambda_recon, noise_scale;        // noise_scale = sqrt(2 eta)
-  float ln_s, inv_s;    // ln S, 1 / S
-  int mixing;           // enum glowk_mixing
-  int vec;              // every pointer is 16-byte aligned: whole quads move as float4
-  uint64_t seed, step, q0;
-  int* nonfinite;
+  float* x[GLOWK_BASIS_MAX_SOURCES] = {};           // [n] each, in place
+  const float* g[GLOWK_BASIS_MAX_SOURCES] = {};     // [n] grad log p_k(x_k)
+  const float* eps[GLOWK_BASIS_MAX_SOURCES] = {};   // optional [n] standard-normal draws of source k; null: device RNG (k & 1, pair k >> 1)
+  const float* mixed = nullptr;   // [n]
+  size_t n = 0;
+  float eta = 0.0f, lambda_recon = 0.0f, noise_scale = 0.0f;        // noise_scale = sqrt(2 eta)
+  float ln_s = 0.0f, inv_s = 1.0f;    // ln S, 1 / S
+  int mixing = 0;           // enum glowk_mixing
+  int vec = 0;              // every pointer is 16-byte aligned: whole quads move as float4
+  uint64_t seed = 0, step = 0, q0 = 0;
+  int* nonfinite = nullptr;
 };
+static_assert(sizeof(BasisNArgs) == 464 && std::is_trivially_copyable_v<BasisNArgs>, "kernel argument size");
 
 // The mixture and the weights m_k of one element from its S source values: v[k] holds x_k on entry and m_k on return, and
 // mix = scale * t with t returned.  Wherever a product meets a sum the rounding is written out (__fmul_rn / fmaf) instead of
@@ -180,12 +182,13 @@ __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
 }
 
 struct BasisMixNArgs {
-  const float* x[GLOWK_BASIS_MAX_SOURCES];
-  float* out;
-  size_t n;
-  float ln_s, inv_s;
-  int mixing;
+  const float* x[GLOWK_BASIS_MAX_SOURCES] = {};
+  float* out = nullptr;
+  size_t n = 0;
+  float ln_s = 0.0f, inv_s = 1.0f;
+  int mixing = 0;
 };
+static_assert(sizeof(BasisMixNArgs) == 160 && std::is_trivially_copyable_v<BasisMixNArgs>, "kernel argument size");
 
 // g(x_0 .. x_{S-1}) alone
 template <int S>

@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace glowk_bss {
 
@@ -30,15 +31,16 @@ constexpr int NENERGY = 8;
 
 // ---- correlations ---------------------------------------------------------------------------------------------------------------
 struct XcorrArgs {
-  const double* sig;
-  int nsig;
-  int64_t nsampl;
-  const int64_t* win;   // [nwin][2] start, stop
-  const int* pairs;     // [npairs][2] u, v
-  int npairs, L;
-  int per, nblk;        // chunks per workgroup, workgroups per (window, pair)
-  double* part;         // [nwin][npairs][nblk][L]
+  const double* sig = nullptr;
+  int nsig = 0;
+  int64_t nsampl = 0;
+  const int64_t* win = nullptr;   // [nwin][2] start, stop
+  const int* pairs = nullptr;     // [npairs][2] u, v
+  int npairs = 0, L = 0;
+  int per = 0, nblk = 0;        // chunks per workgroup, workgroups per (window, pair)
+  double* part = nullptr;         // [nwin][npairs][nblk][L]
 };
+static_assert(sizeof(XcorrArgs) == 64 && std::is_trivially_copyable_v<XcorrArgs>, "kernel argument size");
 
 __global__ __launch_bounds__(XC_THREADS) void k_bss_xcorr(XcorrArgs a) {
   __shared__ double su[XC_SUB];
@@ -84,14 +86,15 @@ __global__ __launch_bounds__(256) void k_bss_xcorr_sum(const double* __restrict_
 
 // ---- batched Cholesky solve -----------------------------------------------------------------------------------------------------
 struct CholArgs {
-  const double* corr;   // [nwin][npairs][L]
-  int nwin, npairs, P, L, np;   // system: np reference channels from p0, M = np * L; right-hand sides: the P estimate channels
-  const int* sys;       // [nsys][2] correlation window, p0
-  int sys0;             // first system of this launch (workspace slot = blockIdx.x)
-  double* A;            // [launch systems][M][M] workspace (lower triangle used)
-  double* X;            // [nsys][P][M] solutions
-  int* status;          // [nsys]
+  const double* corr = nullptr;   // [nwin][npairs][L]
+  int nwin = 0, npairs = 0, P = 0, L = 0, np = 0;   // system: np reference channels from p0, M = np * L; right-hand sides: the P estimate channels
+  const int* sys = nullptr;       // [nsys][2] correlation window, p0
+  int sys0 = 0;             // first system of this launch (workspace slot = blockIdx.x)
+  double* A = nullptr;            // [launch systems][M][M] workspace (lower triangle used)
+  double* X = nullptr;            // [nsys][P][M] solutions
+  int* status = nullptr;          // [nsys]
 };
+static_assert(sizeof(CholArgs) == 72 && std::is_trivially_copyable_v<CholArgs>, "kernel argument size");
 
 __global__ __launch_bounds__(CH_THREADS) void k_bss_chol(CholArgs a) {
   __shared__ double Ld[CH_NB][CH_NB + 1];
@@ -277,17 +280,18 @@ __global__ __launch_bounds__(CH_THREADS) void k_bss_chol(CholArgs a) {
 
 // ---- projections and energies ---------------------------------------------------------------------------------------------------
 struct ProjArgs {
-  const double* sig;    // [2P][nsampl]
-  int64_t nsampl;
-  int nsrc, nchan, L;
-  const int64_t* items; // [nitems][6] start, stop, jtrue, jest, C system, Cj system
-  int nitems, nchunk;
-  const double* coefC;  // [nsysC][P][P * L]
-  int nsysC;
-  const double* coefJ;  // [nsysJ][P][nchan * L]
-  int nsysJ;
-  double* part;         // [nitems][nchunk][NENERGY]
+  const double* sig = nullptr;    // [2P][nsampl]
+  int64_t nsampl = 0;
+  int nsrc = 0, nchan = 0, L = 0;
+  const int64_t* items = nullptr; // [nitems][6] start, stop, jtrue, jest, C system, Cj system
+  int nitems = 0, nchunk = 0;
+  const double* coefC = nullptr;  // [nsysC][P][P * L]
+  int nsysC = 0;
+  const double* coefJ = nullptr;  // [nsysJ][P][nchan * L]
+  int nsysJ = 0;
+  double* part = nullptr;         // [nitems][nchunk][NENERGY]
 };
+static_assert(sizeof(ProjArgs) == 88 && std::is_trivially_copyable_v<ProjArgs>, "kernel argument size");
 
 // energies: 0 |s_true|^2, 1 |est - s_true|^2, 2 |e_spat|^2 = |proj_j - s_true|^2, 3 |proj_j|^2, 4 |e_interf|^2 = |proj_all - proj_j|^2,
 // 5 |proj_all|^2, 6 |e_artif|^2 = |est - proj_all|^2, 7 |est - proj_j|^2, each over len + L - 1 samples and every channel

@@ -157,12 +157,7 @@ __device__ __forceinline__ void co_Y(const float4* slot, const h8 (&bh)[2], cons
   const char* ub = uniform_ptr(src);
   constexpr int NG = NFH / 2;
   h8 A[2][4];
-  auto load = [&](h8 (&d)[4], int gi) {
-    d[0] = buf[((2 * gi) * 2 + 0) * 64];            // row block 2gi hi, lo; row block 2gi+1 hi, lo
-    d[1] = buf[((2 * gi) * 2 + 1) * 64];
-    d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
-    d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
-  };
+  auto load = [&](h8 (&d)[4], int gi) { y_group_read(buf, gi, d); };
   load(A[0], 0);
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) {
@@ -177,20 +172,8 @@ __device__ __forceinline__ void co_Y(const float4* slot, const h8 (&bh)[2], cons
     }
     __builtin_amdgcn_sched_barrier(0);
     const h8 (&af)[4] = A[gi & 1];
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], acc2[o0][0], 0, 0, 0);
-    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
-    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
-    if (MODE7 != NET_FWD2) {
-      acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
-      acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
-      acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], acc2[o1][0], 0, 0, 0);
-      acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[1], acc2[o1][1], 0, 0, 0);
-    }
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[0], acc2[o0][0], 0, 0, 0);
-    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[0], acc2[o1][0], 0, 0, 0);
-    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
+    y_group_first<2>(af, bh, acc2[o0], acc2[o1]);
+    y_group_rest<2, MODE7 != NET_FWD2>(af, bh, bl, acc2[o0], acc2[o1]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -374,23 +357,13 @@ __device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const
   const char* uba = uniform_ptr(srca);
   const char* ubb = uniform_ptr(srcb);
   constexpr int NG = NFH / 2;
-  auto load = [&](h8 (&d)[4], int g) {
-    const h8* buf = g < NG ? bufa : bufb;
-    const int gi = g % NG;
-    d[0] = buf[((2 * gi) * 2 + 0) * 64];            // row block 2gi hi, lo; row block 2gi+1 hi, lo
-    d[1] = buf[((2 * gi) * 2 + 1) * 64];
-    d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
-    d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
-  };
+  auto load = [&](h8 (&d)[4], int g) { y_group_read(g < NG ? bufa : bufb, g % NG, d); };
 #pragma unroll
   for (int g = 0; g < 2 * NG; ++g) {
     const int gi = g % NG;
     const int o0 = (g / NG) * NFH + 2 * gi, o1 = o0 + 1;
     const h8 (&af)[4] = A[g & 1];
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], acc2[o0][0], 0, 0, 0);
-    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
-    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
+    y_group_first<2>(af, bh, acc2[o0], acc2[o1]);
     // the reads and DMA of this group go out BEHIND its first four MFMAs: the wait the compiler puts in front of a group's first MFMA is
     // always lgkmcnt(0) while a DMA is in flight, so reads issued in front of it would be waited for at once -- now it only finds reads
     // that have had the rest of the previous group to return
@@ -409,16 +382,7 @@ __device__ __forceinline__ void co_Ydb(const float4* sa, const float4* sb, const
     }
     if (g == 0) stage4<K1P, TAG * 16 + 15>(k1src, k1dst, w4, voff);
     __builtin_amdgcn_sched_barrier(0);
-    if (MODE7 != NET_FWD2) {
-      acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
-      acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
-      acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], acc2[o1][0], 0, 0, 0);
-      acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[1], acc2[o1][1], 0, 0, 0);
-    }
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[0], acc2[o0][0], 0, 0, 0);
-    acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[0], acc2[o1][0], 0, 0, 0);
-    acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
+    y_group_rest<2, MODE7 != NET_FWD2>(af, bh, bl, acc2[o0], acc2[o1]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }

@@ -25,6 +25,7 @@
 #include "glowk_act_scale.h"
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <utility>
 #include <stdint.h>
 
@@ -37,52 +38,52 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int mfma_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 struct NetArgs {
-  const float* vin;      // [Q][in_stride]; network input = channels [in_off, in_off + CI)
-  int in_stride, in_off;
-  int Q, h, w;
-  const float* K1p;      // [NF fi][KS1][64 lanes]
-  const float* ep;       // [6][F]: b1, g1, d1, b2, g2, d2   (BN folded: g = gamma/sqrt(var+eps), d = beta - mean*g)
-  const float4* R0p;     // ring image (Ring1): [NF + NMT] slots
-  unsigned short* mask1; // [blocks of 32 px][NF][64 lanes] ReLU mask bits of conv1 (NET_FWD_SAVE writes, NET_BWD reads)
-  unsigned short* mask2; // same for conv2
-  float* P;              // [9*CO][Q]
-  size_t pstride;        // f16x3: the pass-p partial sums of P go to P + p * pstride (the consumer adds the partials)
-  int max_np;            // host side: how many partial buffers P has room for (caps the number of passes)
-  const float4* RHp;     // f16x3 image (RingH) of the network this launch runs (forward or backward), or null
-  const float* eph;      // forward: [conv2 accumulator init (F) | per-row constants of P (32 NMT)], see pack_step
-  const float4* RSp;     // image for the 16x16x32 kernel (RingS; same constants and scales) of the network this launch runs, or null
-  int fam16;             // host side: this level's saving forward and backward launches both have a 16x16x32 image
-  float sc1, sc2, sc3;   // f16x3: 2^-S of the three layers' weight scales (sc3 also undoes the activation scale)
-  int* flag;             // sticky range flag of the handle, or null
-  float xlim;            // split kernels: raise the flag when a gathered input (times GLOWK_ACT_SCALE) exceeds this magnitude
-  float bnorm;           // split kernels, backward network (linear in its input): every pixel's gathered gradient vector is scaled by the
+  const float* vin = nullptr;      // [Q][in_stride]; network input = channels [in_off, in_off + CI)
+  int in_stride = 0, in_off = 0;
+  int Q = 0, h = 0, w = 0;
+  const float* K1p = nullptr;      // [NF fi][KS1][64 lanes]
+  const float* ep = nullptr;       // [6][F]: b1, g1, d1, b2, g2, d2   (BN folded: g = gamma/sqrt(var+eps), d = beta - mean*g)
+  const float4* R0p = nullptr;     // ring image (Ring1): [NF + NMT] slots
+  unsigned short* mask1 = nullptr; // [blocks of 32 px][NF][64 lanes] ReLU mask bits of conv1 (NET_FWD_SAVE writes, NET_BWD reads)
+  unsigned short* mask2 = nullptr; // same for conv2
+  float* P = nullptr;              // [9*CO][Q]
+  size_t pstride = 0;        // f16x3: the pass-p partial sums of P go to P + p * pstride (the consumer adds the partials)
+  int max_np = 4;            // host side: how many partial buffers P has room for (caps the number of passes)
+  const float4* RHp = nullptr;     // f16x3 image (RingH) of the network this launch runs (forward or backward), or null
+  const float* eph = nullptr;      // forward: [conv2 accumulator init (F) | per-row constants of P (32 NMT)], see pack_step
+  const float4* RSp = nullptr;     // image for the 16x16x32 kernel (RingS; same constants and scales) of the network this launch runs, or null
+  int fam16 = 0;             // host side: this level's saving forward and backward launches both have a 16x16x32 image
+  float sc1 = 0.0f, sc2 = 0.0f, sc3 = 0.0f;   // f16x3: 2^-S of the three layers' weight scales (sc3 also undoes the activation scale)
+  int* flag = nullptr;             // sticky range flag of the handle, or null
+  float xlim = 0.0f;            // split kernels: raise the flag when a gathered input (times GLOWK_ACT_SCALE) exceeds this magnitude
+  float bnorm = 1.0f;           // split kernels, backward network (linear in its input): every pixel's gathered gradient vector is scaled by the
                          // power of two that brings its largest magnitude into [bnorm, 2 bnorm) before the split, and the pixel's outputs
                          // are scaled back (exact): no gradient magnitude can leave the fp16 range, small pixels keep all their bits
   // ---- coupling fused into k_net_h3s<..., MODE | NET_FUSE> (fused_couple): what k_couple would have been given
-  int fuse;              // host side: ask the launch policy for the fused instance (its answer names the fused form and its pixels
+  int fuse = 0;              // host side: ask the launch policy for the fused instance (its answer names the fused form and its pixels
                          // per workgroup, NetLaunch::fused_px: 128 for the co-resident form -- k_couple_edge is told, EdgeArgs::pxw)
-  int co;                // host side: the co-resident form (glowk_co.h) may be taken where it has an instance
-  const float* fz_b3;    // [C] conv3 bias
-  const float* fz_A;     // post affine [C][C] or null (forward: the NEXT step's ActNorm + 1x1; inverse: this step's inverse 1x1 + ActNorm)
-  const float* fz_b;     // [C]
-  float* fz_out;         // element (q, co) at fz_out[q * fz_out_stride + fz_out_off + co] (stride and offset multiples of 4)
-  int fz_out_stride, fz_out_off, fz_inverse;
-  float* fz_osave;       // saving pass: [Q][2] the pre-tanh log_s inputs (CoupleArgs::o_save), or null
-  float* fz_edge;        // [workgroup][4][64][4]: partial sums of its first / last pixel row, contributions to the rows above / below
-  double* fz_ldpart;     // per workgroup (h w >= 256) or per sample: sum of log_s over the pixels completed in the kernel; or null
-  unsigned* xmax_out;    // diagnostic (glowk_range_probe_begin), normally null: the largest gathered |input| (times GLOWK_ACT_SCALE) of
+  int co = 0;                // host side: the co-resident form (glowk_co.h) may be taken where it has an instance
+  const float* fz_b3 = nullptr;    // [C] conv3 bias
+  const float* fz_A = nullptr;     // post affine [C][C] or null (forward: the NEXT step's ActNorm + 1x1; inverse: this step's inverse 1x1 + ActNorm)
+  const float* fz_b = nullptr;     // [C]
+  float* fz_out = nullptr;         // element (q, co) at fz_out[q * fz_out_stride + fz_out_off + co] (stride and offset multiples of 4)
+  int fz_out_stride = 0, fz_out_off = 0, fz_inverse = 0;
+  float* fz_osave = nullptr;       // saving pass: [Q][2] the pre-tanh log_s inputs (CoupleArgs::o_save), or null
+  float* fz_edge = nullptr;        // [workgroup][4][64][4]: partial sums of its first / last pixel row, contributions to the rows above / below
+  double* fz_ldpart = nullptr;     // per workgroup (h w >= 256) or per sample: sum of log_s over the pixels completed in the kernel; or null
+  unsigned* xmax_out = nullptr;    // diagnostic (glowk_range_probe_begin), normally null: the largest gathered |input| (times GLOWK_ACT_SCALE) of
                          // this launch, as float bits (non-negative floats order like unsigned ints), one atomic per wave
   // training (k_net_f32<..., STORE = true>): the two hidden tensors of this launch, PLANAR [F][Q] (the layout whose rows are the
   // K-contiguous operands of the weight-gradient GEMMs, glowk_train.h).  Forward: st1 = relu(conv1 + b1), st2 = relu(conv2 + b2)
   // (before BatchNorm); backward: st1 = mask2 * conv3^T(g_o) (gradient wrt relu2's output), st2 = mask1 * (K2 g_a2) (wrt relu1's)
-  float* st1;
-  float* st2;
-  int pw;                // the level's width w where the forward 16x16x32 kernels may add conv3's horizontal taps in registers (c = 8, 16;
+  float* st1 = nullptr;
+  float* st2 = nullptr;
+  int pw = 0;                // the level's width w where the forward 16x16x32 kernels may add conv3's horizontal taps in registers (c = 8, 16;
                          // w a power of two in [4, 16]: a 16-pixel half holds whole image rows) and write P as [3 c][Q], row (dy + 1) c + co
                          // (c3_presum_store); 0: per-tap P [9 c][Q].  The level shape alone decides it, never the batch size
-  int pad;               // always 0: keeps the kernel arguments at 264 bytes (256 moves the hidden arguments and changes the code)
+  int pad = 0;               // always 0: keeps the kernel arguments at 264 bytes (256 moves the hidden arguments and changes the code)
 };
-static_assert(sizeof(NetArgs) == 264, "kernel argument size");
+static_assert(sizeof(NetArgs) == 264 && std::is_trivially_copyable_v<NetArgs>, "kernel argument size");
 
 // cache modifier of the planar hidden stores: they are streamed (gigabytes per launch, read back by the weight-gradient GEMMs after the
 // level's sweep), so non-temporal -- measured -1.7 % on a 256-tile parameter-gradient sweep against "" on one box, neutral at 32 tiles
@@ -1409,6 +1410,39 @@ __device__ __forceinline__ void h3s_X_act(const f32x4 (&h1)[2][2], float sc1, h8
   for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false>(h1[0][hf], h1[1][hf], sc1, 0u, bh[hf], bl[hf]);
 }
 
+// the four A fragments of group gi of a conv2 chunk / unit (buf: this lane's column of its slot): row block 2 gi hi, lo; row block 2 gi + 1 hi, lo
+__device__ __forceinline__ void y_group_read(const h8* buf, int gi, h8 (&d)[4]) {
+  d[0] = buf[((2 * gi) * 2 + 0) * 64];
+  d[1] = buf[((2 * gi) * 2 + 1) * 64];
+  d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
+  d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
+}
+
+// The 12 MFMAs of a conv2 group -- row blocks o0, o1 (accumulators t0, t1) x PXH pixel halves x the three split terms lo x hi, hi x lo,
+// hi x hi (af: y_group_read's fragments; THREE = false, the two-term arithmetic, leaves hi x lo out) -- in the ORDER every form of the
+// 16x16x32 family adds them in: the forms agree bit for bit because of it.  In two parts, the first four apart, so that the double-buffered
+// co-resident form can issue its reads between them.
+template <int PXH>
+__device__ __forceinline__ void y_group_first(const h8 (&af)[4], const h8 (&bh)[2], f32x4 (&t0)[2], f32x4 (&t1)[2]) {
+  t0[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], t0[0], 0, 0, 0);
+  if constexpr (PXH == 2) t0[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], t0[1], 0, 0, 0);
+  t1[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], t1[0], 0, 0, 0);
+  if constexpr (PXH == 2) t1[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], t1[1], 0, 0, 0);
+}
+template <int PXH, bool THREE>
+__device__ __forceinline__ void y_group_rest(const h8 (&af)[4], const h8 (&bh)[2], const h8 (&bl)[2], f32x4 (&t0)[2], f32x4 (&t1)[2]) {
+  if (THREE) {
+    t0[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], t0[0], 0, 0, 0);
+    if constexpr (PXH == 2) t0[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], t0[1], 0, 0, 0);
+    t1[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], t1[0], 0, 0, 0);
+    if constexpr (PXH == 2) t1[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[1], t1[1], 0, 0, 0);
+  }
+  t0[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[0], t0[0], 0, 0, 0);
+  if constexpr (PXH == 2) t0[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[1], t0[1], 0, 0, 0);
+  t1[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[0], t1[0], 0, 0, 0);
+  if constexpr (PXH == 2) t1[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], t1[1], 0, 0, 0);
+}
+
 // Y: conv2 contribution of one hidden block (one k-step of 32) to the pass's NRB x 2 accumulator tiles; same pipelining and
 // DMA duties as h3_Y (groups of 12 MFMAs = two row blocks x two pixel halves x three split terms)
 template <int KIN, int MOUT, int NF, int MODE, int NP, int TAG>
@@ -1421,12 +1455,7 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
   constexpr int NG = G::NRB / 2;
   constexpr int PPG = G::MAINP / 4 / NG;            // DMA pieces per wave and group
   h8 A[2][4];
-  auto load = [&](h8 (&d)[4], int gi) {
-    d[0] = buf[((2 * gi) * 2 + 0) * 64];            // row block 2gi hi, lo; row block 2gi+1 hi, lo
-    d[1] = buf[((2 * gi) * 2 + 1) * 64];
-    d[2] = buf[((2 * gi + 1) * 2 + 0) * 64];
-    d[3] = buf[((2 * gi + 1) * 2 + 1) * 64];
-  };
+  auto load = [&](h8 (&d)[4], int gi) { y_group_read(buf, gi, d); };
   load(A[0], 0);
 #pragma unroll
   for (int gi = 0; gi < NG; ++gi) {
@@ -1446,20 +1475,8 @@ __device__ __forceinline__ void h3s_Y(const float4* slot, const h8 (&bh)[2], con
     }
     __builtin_amdgcn_sched_barrier(0);
     const h8 (&af)[4] = A[gi & 1];
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[0], acc2[o0][0], 0, 0, 0);
-    if constexpr (G::PXH == 2) acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[0], acc2[o1][0], 0, 0, 0);
-    if constexpr (G::PXH == 2) acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3], bh[1], acc2[o1][1], 0, 0, 0);
-    if (net_dir<MODE> != NET_FWD2) {
-      acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[0], acc2[o0][0], 0, 0, 0);
-      if constexpr (G::PXH == 2) acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bl[1], acc2[o0][1], 0, 0, 0);
-      acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[0], acc2[o1][0], 0, 0, 0);
-      if constexpr (G::PXH == 2) acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bl[1], acc2[o1][1], 0, 0, 0);
-    }
-    acc2[o0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[0], acc2[o0][0], 0, 0, 0);
-    if constexpr (G::PXH == 2) acc2[o0][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bh[1], acc2[o0][1], 0, 0, 0);
-    acc2[o1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[0], acc2[o1][0], 0, 0, 0);
-    if constexpr (G::PXH == 2) acc2[o1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2], bh[1], acc2[o1][1], 0, 0, 0);
+    y_group_first<G::PXH>(af, bh, acc2[o0], acc2[o1]);
+    y_group_rest<G::PXH, net_dir<MODE> != NET_FWD2>(af, bh, bl, acc2[o0], acc2[o1]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }

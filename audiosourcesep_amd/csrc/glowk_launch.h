@@ -78,29 +78,40 @@ NetLaunch launch_f32(const NetArgs& a, hipStream_t s, bool dry) {
   return {1, FAM_F32};
 }
 
-// k_net_h3 / k_net_h3s launch forms.  NP = passes over the hidden width (2, or 4 where the shape needs the registers);
-// when NP workgroups per 256 pixels still fit the CUs in one round the passes become workgroups of their own (SPLIT):
-// 1/NP of the latency per launch.  np = NP partial P buffers; not taken if no instance fits.
+// k_net_h3 / k_net_h3s launch forms.  NP = passes over the hidden width: 4 where that has an instance, the caller has room for four
+// partial P buffers (max_np) and the four passes fit the CUs as workgroups of their own or NP = 2 has no instance; else 2.  Where NP
+// workgroups per wgs still fit the CUs in one round the passes become workgroups of their own (split): 1/NP of the latency per launch.
+// np = NP partial P buffers; 0: no instance fits.
+struct Passes { int np; bool split; };
+inline Passes pick_passes(bool fits4, bool fits2, int wgs, int max_np) {
+  const int cus = num_cus();
+  if (fits4 && max_np >= 4 && (4 * wgs <= cus || !fits2)) return {4, 4 * wgs <= cus};
+  if (fits2) return {2, 2 * wgs <= cus};
+  return {0, false};
+}
+// the launch of KERNEL<..., MODE_, NP_, SPLIT> (eight-wave workgroups) for a run-time split
+#define GLOWK_LAUNCH_PASSES(KERNEL, MODE_, NP_, split_)                                                                  \
+  do {                                                                                                                 \
+    if (split_) hipLaunchKernelGGL((KERNEL<KIN, MOUT, NF, MODE_, NP_, true>), dim3(wgs, NP_), dim3(512), 0, s, a);      \
+    else hipLaunchKernelGGL((KERNEL<KIN, MOUT, NF, MODE_, NP_, false>), dim3(wgs), dim3(512), 0, s, a);                 \
+  } while (0)
+
 template <int KIN, int MOUT, int NF, int MODE>
 NetLaunch launch_h3(const NetArgs& a, hipStream_t s, bool dry) {
   constexpr bool F2 = RingH<KIN, MOUT, NF, MODE, 2>::FITS, F4 = RingH<KIN, MOUT, NF, MODE, 4>::FITS;
-  const int wgs = (a.Q + 255) / 256, cus = num_cus();
+  const int wgs = (a.Q + 255) / 256;
+  const Passes p = pick_passes(F4, F2, wgs, a.max_np);
   if constexpr (F4) {
-    if (a.max_np >= 4 && (4 * wgs <= cus || !F2)) {
-      const bool split = 4 * wgs <= cus;
-      if (!dry) {
-        if (split) hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-      }
+    if (p.np == 4) {
+      if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3, MODE, 4, p.split);
       return {4, FAM_H3};
     }
   }
   if constexpr (F2) {
-    if (!dry) {
-      if (2 * wgs <= cus) hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 2, true>), dim3(wgs, 2), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_net_h3<KIN, MOUT, NF, MODE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
+    if (p.np == 2) {
+      if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3, MODE, 2, p.split);
+      return {2, FAM_H3};
     }
-    return {2, FAM_H3};
   }
   return {};
 }
@@ -122,18 +133,14 @@ NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
   static_assert(!(MODE & NET_STORE), "no storing launches here: the co-resident branch does not check Q % 128 (launch_co_train does)");
   constexpr bool F2 = RingS<KIN, MOUT, NF, MODE, 2>::FITS, F4 = RingS<KIN, MOUT, NF, MODE, 4>::FITS;
   const int wgs = (a.Q + 255) / 256, cus = num_cus();
+  const Passes p = pick_passes(F4, F2, wgs, a.max_np);
   if constexpr (F4) {
-    if (a.max_np >= 4 && (4 * wgs <= cus || !F2)) {
-      const bool split = 4 * wgs <= cus;
-      if (!dry) {
-        if (split) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-      }
+    if (p.np == 4) {
+      if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE, 4, p.split);
       return {4, FAM_H3S};
     }
   }
   if constexpr (F2) {
-    const bool split = 2 * wgs <= cus;
     // the coupling fused into the kernel (glowk_kernels.h: fused_couple) where the caller asks for it (NetArgs::fuse: plain forward
     // direction, geometry checked by the host), the level has four channels and both passes run in one workgroup
     // the co-resident form (glowk_co.h: four-wave / 128-pixel workgroups, two to a CU), where the caller allows it (NetArgs::co) and it
@@ -166,24 +173,21 @@ NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
           return {RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2, FAM_H3S, true};
         }
       }
-      if (co_ok && split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
+      if (co_ok && p.split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
         if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
         return {2, FAM_H3S, true};
       }
     }
     if constexpr ((MODE == NET_FWD || MODE == NET_FWD2 || MODE == NET_FWD_SAVE) && MOUT == 36) {
       if constexpr (RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::FITS && RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::MERGE) {
-        if (a.fuse && !split) {
+        if (a.fuse && !p.split) {
           if (!dry) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_FUSE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
           return {0, FAM_FUSED, false, false, 256};
         }
       }
     }
-    if (!dry) {
-      if (split) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 2, true>), dim3(wgs, 2), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
-    }
-    return {(!split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2, FAM_H3S};   // (merged: the two passes' sums leave the kernel as one buffer)
+    if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE, 2, p.split);
+    return {(!p.split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2, FAM_H3S};   // (merged: the two passes' sums leave the kernel as one buffer)
   }
   return {};
 }
@@ -197,23 +201,22 @@ inline bool half_wave_grid(const NetArgs& a) { return 8 * ((a.Q + 255) / 256) <=
 template <int KIN, int MOUT, int NF, int MODE>
 NetLaunch launch_h3s_half(const NetArgs& a, hipStream_t s, bool dry) {
   if constexpr (RingS<KIN, MOUT, NF, MODE | NET_HALF, 4>::FITS) {
-    if (a.max_np < 4) return {};
     const int wgs = (a.Q + 127) / 128;
+    const Passes p = pick_passes(true, false, wgs, a.max_np);
+    if (p.np != 4) return {};
     // passes as workgroups of their own, each alone on its CU: the form with all conv1 blocks first (glowk_q.h), where it has an instance
     if constexpr (RingQ<KIN, MOUT, NF, MODE>::FITS) {
-      if (4 * wgs <= num_cus() && !env().q_off) {
+      if (p.split && !env().q_off) {
         if (!dry) hipLaunchKernelGGL((k_net_h3q<KIN, MOUT, NF, MODE>), dim3(wgs, 4), dim3(512), 0, s, a);
         return {4, FAM_H3S_HALF, false, true};
       }
     }
-    if (!dry) {
-      if (4 * wgs <= num_cus()) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_HALF, 4, true>), dim3(wgs, 4), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_HALF, 4, false>), dim3(wgs), dim3(512), 0, s, a);
-    }
+    if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE | NET_HALF, 4, p.split);
     return {4, FAM_H3S_HALF};
   }
   return {};
 }
+#undef GLOWK_LAUNCH_PASSES
 
 // the saving forward pass and the backward pass of a level must agree on the form (their ReLU-mask layouts differ: one entry per
 // pixel block of a wave): both have a half-wave instance (STORE: the training sweep's launches, which also store their hiddens)

@@ -33,9 +33,10 @@ __device__ __forceinline__ double block_sum_256(double v, double* red /* [4] in 
 // y[co] = b[co] + sum_ci x[ci] * A[ci][co]   (A row-major [C][C]; uniform addresses -> scalar loads)
 
 struct PreArgs {
-  float minval, maxval, alpha;
-  int use_logit;
+  float minval = 0.0f, maxval = 0.0f, alpha = 0.0f;
+  int use_logit = 0;
 };
+static_assert(sizeof(PreArgs) == 16 && std::is_trivially_copyable_v<PreArgs>, "kernel argument size");
 
 // SpecPreprocessing._forward on one element (flow_tfp_bijectors.py:372-379); ld accumulates the
 // data-dependent part of the logit log-det (-log p - log(1-p), :394)
@@ -130,26 +131,27 @@ __global__ __launch_bounds__(256) void k_pre_only(const float* __restrict__ x, i
 }
 
 struct CoupleArgs {
-  const float* vin;     // [Q][C]: forward: v = 1x1(actnorm(u)); inverse: y
-  const float* P;       // [9C][Q] per-tap partial conv3 outputs of the network evaluated on vin[.., C/2:]
-  int np;               // number of partial P buffers (f16x3 kernels: one per pass over the hidden width), >= 1
-  size_t pstride;       // floats between them
-  int presum;           // 1: the network kernel has added conv3's horizontal taps (NetLaunch::presum): P is [3C][Q], row (dy + 1) C + co, and
+  const float* vin = nullptr;     // [Q][C]: forward: v = 1x1(actnorm(u)); inverse: y
+  const float* P = nullptr;       // [9C][Q] per-tap partial conv3 outputs of the network evaluated on vin[.., C/2:]
+  int np = 1;               // number of partial P buffers (f16x3 kernels: one per pass over the hidden width), >= 1
+  size_t pstride = 0;       // floats between them
+  int presum = 0;           // 1: the network kernel has added conv3's horizontal taps (NetLaunch::presum): P is [3C][Q], row (dy + 1) C + co, and
                         // output(q) = sum over dy with 0 <= i + dy < h, over the partials, of P[(dy + 1) C + co][q + dy w] (c = 8, 16 only)
-  const float* b3;      // [C] conv3 bias
-  const float* A;       // post affine [C][C] or null: forward = NEXT step's ActNorm+1x1, inverse = this step's inverse 1x1+ActNorm
-  const float* b;       // [C]
-  float* out;           // element (q, co) at out[q*out_stride + out_off + co]
-  int out_stride, out_off;
-  double* logdet;       // [N] += sum log_s (forward only; may be null)
-  float* log_s_out;     // optional [Q][C/2] dumps of the network outputs (glowk_coupling_net)
-  float* t_out;
-  float* o_save;        // saving pass (input-gradient / training): [Q][C/2] the pre-tanh log_s inputs (bias included) -- all the backward
+  const float* b3 = nullptr;      // [C] conv3 bias
+  const float* A = nullptr;       // post affine [C][C] or null: forward = NEXT step's ActNorm+1x1, inverse = this step's inverse 1x1+ActNorm
+  const float* b = nullptr;       // [C]
+  float* out = nullptr;           // element (q, co) at out[q*out_stride + out_off + co]
+  int out_stride = 0, out_off = 0;
+  double* logdet = nullptr;       // [N] += sum log_s (forward only; may be null)
+  float* log_s_out = nullptr;     // optional [Q][C/2] dumps of the network outputs (glowk_coupling_net)
+  float* t_out = nullptr;
+  float* o_save = nullptr;        // saving pass (input-gradient / training): [Q][C/2] the pre-tanh log_s inputs (bias included) -- all the backward
                         // pass needs of the network's output; the per-tap outputs P themselves are scratch and are not kept
-  int Q, h, w;
-  int inverse;
-  int* flag;            // sticky range flag of the handle: set to 1 when a network output is not finite (may be null)
+  int Q = 0, h = 0, w = 0;
+  int inverse = 0;
+  int* flag = nullptr;            // sticky range flag of the handle: set to 1 when a network output is not finite (may be null)
 };
+static_assert(sizeof(CoupleArgs) == 136 && std::is_trivially_copyable_v<CoupleArgs>, "kernel argument size");
 
 // Second source of the range flag (the first is the split kernels' own range check, glowk_kernels.h: max3abs): a network
 // output or a coupling result that is not finite -- an overflow of the LAST hidden layer (no ReLU follows it to swallow the
@@ -467,18 +469,19 @@ __global__ __launch_bounds__(64) void k_ld_fold(double* __restrict__ logdet, con
 // the rows the fused kernel could not finish (see fused_couple): one workgroup per sample.  Also adds the sample's log-det:
 // the partial sums of the fused workgroups plus the edge pixels' own log_s.
 struct EdgeArgs {
-  const float* vin;      // [Q][4]
-  const float* edge;     // [workgroup][4][FUSE_EW][4]
-  const double* ldpart;
-  const float *A, *b;
-  float* out;
-  int out_stride, out_off, inverse;
-  double* logdet;        // [N] += (may be null)
-  float* osave;          // saving pass: [Q][2] pre-tanh log_s inputs of the edge pixels (complete sums), or null
-  int h, w;
-  int* flag;
-  int pxw;               // pixels per workgroup of the fused kernel that left `edge` / `ldpart`: 256 (k_net_h3s) or 128 (k_net_h3c)
+  const float* vin = nullptr;      // [Q][4]
+  const float* edge = nullptr;     // [workgroup][4][FUSE_EW][4]
+  const double* ldpart = nullptr;
+  const float *A = nullptr, *b = nullptr;
+  float* out = nullptr;
+  int out_stride = 0, out_off = 0, inverse = 0;
+  double* logdet = nullptr;        // [N] += (may be null)
+  float* osave = nullptr;          // saving pass: [Q][2] pre-tanh log_s inputs of the edge pixels (complete sums), or null
+  int h = 0, w = 0;
+  int* flag = nullptr;
+  int pxw = 256;               // pixels per workgroup of the fused kernel that left `edge` / `ldpart`: 256 (k_net_h3s) or 128 (k_net_h3c)
 };
+static_assert(sizeof(EdgeArgs) == 104 && std::is_trivially_copyable_v<EdgeArgs>, "kernel argument size");
 
 __global__ __launch_bounds__(256) void k_couple_edge(EdgeArgs a) {
   __shared__ double red[4];
@@ -726,31 +729,32 @@ struct BwdArgs {
   // (1) gradient wrt the tensor v_s entering step s's coupling:
   //     merge: g_v = [g_va, g_yb + sum_tap Pg[tap, cin][q - d(tap)]]   (ghalf_in, Pg of step s), or
   //     direct: g_v = gv_direct[q*gvd_stride + gvd_off + .]             (Pg == null)
-  const float* ghalf_in;
-  const float* Pg;
-  int npg;                 // number of partial Pg buffers (f16x3 backward kernel: one per pass), >= 1
-  size_t pgstride;
-  const float* gv_direct;
-  int gvd_stride, gvd_off;
+  const float* ghalf_in = nullptr;
+  const float* Pg = nullptr;
+  int npg = 1;                 // number of partial Pg buffers (f16x3 backward kernel: one per pass), >= 1
+  size_t pgstride = 0;
+  const float* gv_direct = nullptr;
+  int gvd_stride = 0, gvd_off = 0;
   // (2) through step s's fused ActNorm + 1x1: g_y = g_v . A^T (null: g_y = g_v)
-  const float* A;
+  const float* A = nullptr;
   // (3) coupling backward of the step that produced y (forward order: the step before s), or none (v == null)
-  const float* v;          // [Q][C] saved coupling input
-  const float* osave;      // [Q][C/2] saved pre-tanh log_s inputs of that coupling (CoupleArgs::o_save)
-  float* g_o;              // [Q][C] gradient wrt the network output o = [pre-tanh log_s, t]
-  float* ghalf_out;        // [Q][C] [g_va, g_yb]
-  float* gu_out;           // [Q][C] g_y itself when no coupling follows
-  int Q, h, w;
-  int* flag;               // sticky range flag (see CoupleArgs); may be null
-  float* gv_out;           // training: [Q][C] the merged g_v of (1) (the weight gradients of step s's ActNorm + 1x1 need it), or null
+  const float* v = nullptr;          // [Q][C] saved coupling input
+  const float* osave = nullptr;      // [Q][C/2] saved pre-tanh log_s inputs of that coupling (CoupleArgs::o_save)
+  float* g_o = nullptr;              // [Q][C] gradient wrt the network output o = [pre-tanh log_s, t]
+  float* ghalf_out = nullptr;        // [Q][C] [g_va, g_yb]
+  float* gu_out = nullptr;           // [Q][C] g_y itself when no coupling follows
+  int Q = 0, h = 0, w = 0;
+  int* flag = nullptr;               // sticky range flag (see CoupleArgs); may be null
+  float* gv_out = nullptr;           // training: [Q][C] the merged g_v of (1) (the weight gradients of step s's ActNorm + 1x1 need it), or null
   // training in the split arithmetic: the backward network and the weight-gradient GEMMs are linear in g_o, so g_o is written
   // times a power of two `go_scale` chosen by the host from the gradient magnitudes of the previous sweep (dynamic scaling: it
   // keeps every value the split kernels and GEMMs convert to fp16 inside the static range bound whatever the loss scale is),
   // the per-tap network gradients Pg that come back carry it and are multiplied by `pg_scale` = 1 / go_scale here, and the
   // assembly of the weight gradients divides by it.  gmax (optional): atomic maximum of |g_o| (unscaled, float bits) per launch.
-  float go_scale, pg_scale;
-  unsigned* gmax;          // [16] words per level (the workgroups spread their atomics over them)
+  float go_scale = 1.0f, pg_scale = 1.0f;
+  unsigned* gmax = nullptr;          // [16] words per level (the workgroups spread their atomics over them)
 };
+static_assert(sizeof(BwdArgs) == 144 && std::is_trivially_copyable_v<BwdArgs>, "kernel argument size");
 
 // LPP lanes per pixel: 1 (large grids: every load of the planar Pg arrays and every 16-byte row access is fully coalesced),
 // 4 (lane r gathers taps r, r + 4, r + 8 of every partial) or 16 -- the (tap, partial) pairs dealt round

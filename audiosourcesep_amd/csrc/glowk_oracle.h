@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "glowk_audio.h"
 
@@ -93,12 +94,13 @@ __device__ __forceinline__ double binary_mask(double ratio, double theta) {   //
 }
 
 struct MaskArgs {
-  float2* spec;
-  int64_t plane;                                     // 1025 T
-  int nsrc, nchan, irm;
-  double alpha, theta;
-  uint8_t* mask;                                     // nullable (IBM only)
+  float2* spec = nullptr;
+  int64_t plane = 0;                                     // 1025 T
+  int nsrc = 0, nchan = 0, irm = 0;
+  double alpha = 0.0, theta = 0.0;
+  uint8_t* mask = nullptr;                                     // nullable (IBM only)
 };
+static_assert(sizeof(MaskArgs) == 56 && std::is_trivially_copyable_v<MaskArgs>, "kernel argument size");
 
 __global__ __launch_bounds__(256) void k_oracle_mask(MaskArgs a) {
   const int64_t total = (int64_t)a.nchan * a.plane;  // one thread per (channel, bin, frame): every source of it

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace glowk_rs {
 
@@ -27,16 +28,17 @@ constexpr int RS_THREADS = 256;
 constexpr int RS_LDS_FLOATS = 15360;                          // 60 KB: the staged span of the widest supported ratio still holds 111 outputs
 
 struct ResampleArgs {
-  const float* x;        // [nsig][n_in]
-  float* y;              // [nsig][n_out]
-  const float2* tab;     // [Z P + 1] (T[k], T[k + 1] - T[k]); the last difference is 0
-  int64_t n_in, n_out, blocks_per_sig;
-  uint32_t a, b, d;      // reduced rates, d = max(a, b)
-  uint32_t stepk, stepr; // (b P) div d, (b P) mod d: the table advance of one tap
-  int H;                 // taps per side at most: floor(Z d / b) + 1
-  int tb;                // outputs per workgroup
-  float scale, inv_d;    // s = min(1, b / a); 1 / d
+  const float* x = nullptr;        // [nsig][n_in]
+  float* y = nullptr;              // [nsig][n_out]
+  const float2* tab = nullptr;     // [Z P + 1] (T[k], T[k + 1] - T[k]); the last difference is 0
+  int64_t n_in = 0, n_out = 0, blocks_per_sig = 0;
+  uint32_t a = 1, b = 1, d = 1;      // reduced rates, d = max(a, b)
+  uint32_t stepk = 0, stepr = 0; // (b P) div d, (b P) mod d: the table advance of one tap
+  int H = 0;                 // taps per side at most: floor(Z d / b) + 1
+  int tb = 0;                // outputs per workgroup
+  float scale = 1.0f, inv_d = 1.0f;    // s = min(1, b / a); 1 / d
 };
+static_assert(sizeof(ResampleArgs) == 88 && std::is_trivially_copyable_v<ResampleArgs>, "kernel argument size");
 
 __global__ __launch_bounds__(RS_THREADS) void k_resample(ResampleArgs g) {
   extern __shared__ float xs[];                        // x[m0 .. m0 + span)

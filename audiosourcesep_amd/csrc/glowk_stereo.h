@@ -21,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace glowk_stereo {
 
@@ -35,12 +36,13 @@ __host__ __device__ inline size_t em_state_bytes(int nt) { return (size_t)(MAX_S
 __host__ __device__ inline size_t em_stage_bytes(int S, int T) { return (size_t)T * ((size_t)S * sizeof(float) + 2 * sizeof(float2)); }
 
 struct EmArgs {
-  const float2* x;    // [P][2][1025][T]
-  float* v;           // [S][P][1025][T]
-  float2* y;          // [S][P][2][1025][T]
-  double* r;          // nullable [S][P][1025][4]
-  int S, P, T, n_iter;
+  const float2* x = nullptr;    // [P][2][1025][T]
+  float* v = nullptr;           // [S][P][1025][T]
+  float2* y = nullptr;          // [S][P][2][1025][T]
+  double* r = nullptr;          // nullable [S][P][1025][4]
+  int S = 0, P = 0, T = 0, n_iter = 0;
 };
+static_assert(sizeof(EmArgs) == 48 && std::is_trivially_copyable_v<EmArgs>, "kernel argument size");
 
 // The four time sums of one source over the wave's 64 lanes in 7 exchanges instead of 24: lanes 32 apart split the four values
 // between them (the lower half keeps s0, s1), lanes 16 apart split the two, then a butterfly over each 16-lane group.  Every lane

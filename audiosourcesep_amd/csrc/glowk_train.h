@@ -56,18 +56,19 @@ __device__ __forceinline__ void gemm_barrier() {
 // an MFMA operand is one conflict-free ds_read_b32 per lane; the next tile's global loads are issued before the MFMAs of
 // the current one.  Split-K partials are written, not atomically added: the reduction order is fixed (bitwise repeatable).
 struct WgradArgs {
-  const float* A;
-  const float* B;
-  int M, N;          // rows of A / B actually stored
-  int a_ones;        // 1: an extra row M of ones
-  int K;             // pixels
-  int kslice;        // pixels per split (multiple of 32)
-  float* Cpart;      // [batch][S][Mp][Np], Mp = M + a_ones, Np = N; output z = b * S + s starts at Cpart + z * csz
-  int S;             // slices per batch entry
-  int tm, tn;        // tiles in each direction (1-D grid of tm * tn * batch * S workgroups, XCD-aware order: see k_wgrad_h3)
-  ptrdiff_t bsA, bsB;   // floats between the batch entries of A / B (may be negative)
-  size_t csz;        // floats between consecutive outputs (>= Mp * Np)
+  const float* A = nullptr;
+  const float* B = nullptr;
+  int M = 0, N = 0;          // rows of A / B actually stored
+  int a_ones = 0;        // 1: an extra row M of ones
+  int K = 0;             // pixels
+  int kslice = 0;        // pixels per split (multiple of 32)
+  float* Cpart = nullptr;      // [batch][S][Mp][Np], Mp = M + a_ones, Np = N; output z = b * S + s starts at Cpart + z * csz
+  int S = 1;             // slices per batch entry
+  int tm = 0, tn = 0;        // tiles in each direction (1-D grid of tm * tn * batch * S workgroups, XCD-aware order: see k_wgrad_h3)
+  ptrdiff_t bsA = 0, bsB = 0;   // floats between the batch entries of A / B (may be negative)
+  size_t csz = 0;        // floats between consecutive outputs (>= Mp * Np)
 };
+static_assert(sizeof(WgradArgs) == 88 && std::is_trivially_copyable_v<WgradArgs>, "kernel argument size");
 
 // logical workgroup id of a 1-D grid such that each of the 8 XCDs (hardware deals consecutive ids round-robin to them) owns a contiguous
 // run of logical ids: tiles that share operand panels then share an L2.  Bijective for any grid size.
@@ -197,20 +198,21 @@ __global__ __launch_bounds__(256) void k_wgrad_nt(WgradArgs a) {
 // conv2 gradient, 128 x 64 (4 x 1 waves of 32 x 64) for the skinny conv1 / conv3 ones, which are bound by streaming (and converting) A.
 // A launch covers `batch` independent GEMMs (the steps of a level) of S slices each.
 struct WgradSplitArgs {
-  const float* A;
-  const float* B;
-  int M, N, K;
-  int kslice;        // pixels per slice (multiple of 32)
-  int S;             // slices per batch entry
-  int tm, tn;        // tiles in each direction
-  ptrdiff_t bsA, bsB;   // floats between the batch entries of A / B (may be negative)
-  float sa, sb;      // powers of two; sa must be 1
-  float* Cpart;      // output z = b * S + s starts at Cpart + z * csz
-  size_t csz;        // floats between consecutive outputs (>= M * N, or (M + 1) * N with b_sums)
-  int plain;         // 1: the plain round order for every shape (A/B timing: GLOWK_WGRAD_PLAIN)
-  int b_sums;        // 1: row M of every output = the row sums of B over the slice (what a row of ones appended to A would give; fp64
+  const float* A = nullptr;
+  const float* B = nullptr;
+  int M = 0, N = 0, K = 0;
+  int kslice = 0;        // pixels per slice (multiple of 32)
+  int S = 1;             // slices per batch entry
+  int tm = 0, tn = 0;        // tiles in each direction
+  ptrdiff_t bsA = 0, bsB = 0;   // floats between the batch entries of A / B (may be negative)
+  float sa = 1.0f, sb = 1.0f;      // powers of two; sa must be 1
+  float* Cpart = nullptr;      // output z = b * S + s starts at Cpart + z * csz
+  size_t csz = 0;        // floats between consecutive outputs (>= M * N, or (M + 1) * N with b_sums)
+  int plain = 0;         // 1: the plain round order for every shape (A/B timing: GLOWK_WGRAD_PLAIN)
+  int b_sums = 0;        // 1: row M of every output = the row sums of B over the slice (what a row of ones appended to A would give; fp64
                      // accumulation in the workgroups of the first row tile, which stage those rows anyway)
 };
+static_assert(sizeof(WgradSplitArgs) == 96 && std::is_trivially_copyable_v<WgradSplitArgs>, "kernel argument size");
 
 // VEC: K is a multiple of 4 (float4 loads; a template parameter because a run-time branch around every load makes hipcc wait for
 // each load in turn)
@@ -496,24 +498,26 @@ __global__ __launch_bounds__(256) void k_sum_parts_f64(const double* __restrict_
 //   dK1[tap][ci][f] = g1[f] C1[f][tap ci_n + ci]                             db1[f] = g1[f] SM1[f]
 // Every gradient is multiplied by `scale` (= -1 / global batch: the loss is the mean negative log-likelihood).
 struct StepGradArgs {
-  int F, c;
-  const float* K2;      // [F][F] parameters (reference layout)
-  const float* K3;      // [9][F][c]
-  const float* bn;      // [8][F]: gamma1, beta1, mean1, var1, gamma2, beta2, mean2, var2
-  const float* ep;      // [6][F]: b1, g1, d1, b2, g2, d2 -- the step's folded BatchNorm block as the kernels read it (k_fold_bn / pack_step)
-  float eps;
+  int F = 0, c = 0;
+  const float* K2 = nullptr;      // [F][F] parameters (reference layout)
+  const float* K3 = nullptr;      // [9][F][c]
+  const float* bn = nullptr;      // [8][F]: gamma1, beta1, mean1, var1, gamma2, beta2, mean2, var2
+  const float* ep = nullptr;      // [6][F]: b1, g1, d1, b2, g2, d2 -- the step's folded BatchNorm block as the kernels read it (k_fold_bn / pack_step)
+  float eps = 0.0f;
   // scaled = 1: the planar arrays came from the split kernels (k_net_h3, MODE | NET_STORE) in the units those kernels split in:
   //   A1 = ACT 2^e1[f] R1,  A2 = ACT 2^e2[f] R2  (g = m 2^e: the power of two of the BatchNorm gain is folded into the producer),
   //   G2 = ACT g2[f] M2 = ACT g_a2,  G1 = ACT g1[f] M1 = ACT g_a1  (the backward images carry the gains),  ACT = GLOWK_ACT_SCALE.
   // The GEMMs ran on those; the per-row factors are undone here (powers of two and the gains themselves; a gain of exactly zero
   // -- a dead channel -- gets a zero gamma gradient).
-  int scaled;
-  const float *C1, *C2, *C3;
-  float scale;
-  float *dK1, *db1, *dgamma1, *dbeta1, *dK2, *db2, *dgamma2, *dbeta2, *dK3, *db3;
+  int scaled = 0;
+  const float *C1 = nullptr, *C2 = nullptr, *C3 = nullptr;
+  float scale = 1.0f;
+  float *dK1 = nullptr, *db1 = nullptr, *dgamma1 = nullptr, *dbeta1 = nullptr, *dK2 = nullptr, *db2 = nullptr, *dgamma2 = nullptr, *dbeta2 = nullptr,
+        *dK3 = nullptr, *db3 = nullptr;
   // batch entry b (blockIdx.y: a step of the level): parameters and gradients advance by ps floats, ep by es, C1 / C2 / C3 by their strides
-  size_t ps, es, c1s, c2s, c3s;
+  size_t ps = 0, es = 0, c1s = 0, c2s = 0, c3s = 0;
 };
+static_assert(sizeof(StepGradArgs) == 200 && std::is_trivially_copyable_v<StepGradArgs>, "kernel argument size");
 __device__ __forceinline__ void step_grad_batch(StepGradArgs& a, size_t b) {
   a.K2 += b * a.ps; a.K3 += b * a.ps; a.bn += b * a.ps; a.ep += b * a.es;
   a.C1 += b * a.c1s; a.C2 += b * a.c2s; a.C3 += b * a.c3s;

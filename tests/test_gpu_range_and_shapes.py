@@ -439,3 +439,58 @@ def test_training_sweep_recalibrates_its_gradient_scale():
     _, gy = eng.param_grad(x, -1.0 / 24)
     for g in (g3, g4):
         assert float((g - gy).abs().max()) <= 5e-6 * float(gy.abs().max())
+
+
+# ---- the launch forms the host chooses between, each against the fp64 oracle ----------------------------------------------------------
+# launch_couple: a flat pixel grid (4 or 16 lanes per pixel) below 2 x CUs tiles where a level has a multiple of 64 pixels, else one
+# workgroup per tile (one lane per pixel from 2 x CUs tiles, four below, in 256 / 512 / 1024 threads); each reading per-tap or pre-summed P
+# (the split arithmetic at an 8-channel level whose width is a power of two in [4, 16]; the exact kernels always write per-tap P, so every
+# case runs in both).  launch_bwd_light: one lane per pixel from 2 x CUs x 256 pixels, 16 at an 8-channel level of at most 8 x CUs x 16
+# pixels, else 4.  The network launches of these grids take their passes as workgroups of their own (small grids) or not.
+# name: (H, W, K, tiles for a device of `cus` compute units[, L, n_filters]); C = 1, L = 2, n_filters = 128 unless given: level 0 is
+# (H/2, W/2, 4), level 1 (H/4, W/4, 8)
+LAUNCH_FORM_CASES = {
+    "one_lane_per_tap": (8, 8, 1, lambda cus: 2 * cus + 1),             # per tile, one lane; level 1 is 2 x 2: per-tap P
+    "one_lane_presum": (16, 16, 2, lambda cus: 2 * cus + 1),            # ... level 1 is 4 x 4: pre-summed P
+    "flat_4_and_16_presum": (32, 32, 2, lambda cus: 3),                 # flat: level 0 (16 x 16 x 4) 4 lanes, level 1 (8 x 8 x 8) 16 lanes
+    "flat_16_per_tap": (8, 128, 1, lambda cus: 3),                      # level 1 is 2 x 32: 64 pixels, too wide to pre-sum
+    "flat_4_presum_bwd_one_lane": (64, 64, 1, lambda cus: cus // 2 + 1),   # level 1: more than 8 x CUs x 16 pixels; level 0: 2 x CUs x 256
+    "four_lanes_512_256_per_tap": (24, 24, 2, lambda cus: 3),           # 12 x 12 and 6 x 6 pixels: no multiple of 64
+    "four_lanes_1024_512_per_tap": (36, 36, 1, lambda cus: 2),          # 18 x 18 and 9 x 9
+    "four_lanes_256_presum": (24, 32, 1, lambda cus: 3),                # level 1 is 6 x 8
+    "four_lanes_1024_presum": (72, 64, 1, lambda cus: 2),               # level 1 is 18 x 16
+    # grids too large for the passes to be workgroups of their own (more than CUs / NP workgroups), at n_filters = 256, where the 16-channel
+    # level's backward network and the 32-channel level's forward network have no two-pass instance and the 32-channel level's gradient
+    # path only the half-wave form: level 2 (4 x 4 x 16, 256 x CUs + 16 pixels) runs k_net_h3s NP = 2 forward and saving, NP = 4 backward,
+    # level 3 (2 x 2 x 32, 64 x CUs + 4 pixels) NP = 4 forward and the half-wave form saving and backward, each in one workgroup
+    "passes_in_one_workgroup": (32, 32, 1, lambda cus: 16 * cus + 1, 4, 256),
+}
+
+
+@pytest.mark.parametrize("name", list(LAUNCH_FORM_CASES))
+def test_launch_forms_against_the_fp64_oracle(name):
+    """log_prob within 1e-4 relative of the fp64 oracle, the input gradient within 2e-4 of its largest entry, in the exact and the
+    three-term split arithmetic; the oracle sees the first two and the last tile (tiles are independent), and its fp32 run has to
+    agree with its fp64 run inside the same bars first."""
+    H, W, K, tiles, L, F = (LAUNCH_FORM_CASES[name] + (2, 128))[:6]
+    n = tiles(torch.cuda.get_device_properties(0).multi_processor_count)
+    cfg = GlowConfig(H=H, W=W, C=1, L=L, K=K, F=F)
+    eng, params = calibrated_engine(cfg, device=0, init_tiles=8)
+    eng.set_range_policy("error")
+    x = synthetic_mel_tiles(n, cfg, seed=21)
+    idx = sorted({0, 1, n - 1})
+    lp_ref, g_ref = RT.log_prob_and_grad(x[idx].astype(np.float64), params, cfg.as_dict())
+    lp_32, g_32 = RT.log_prob_and_grad(x[idx], params, cfg.as_dict(), dtype=torch.float32)
+    gmax = np.abs(g_ref).max()
+    assert np.max(np.abs(lp_32 - lp_ref) / np.abs(lp_ref)) <= 1e-4 and np.abs(g_32 - g_ref).max() <= 2e-4 * gmax
+    for prec in (_lib.PREC_F32, _lib.PREC_F16X3):
+        eng.set_precision(prec)
+        lp = eng.log_prob(dev(x)).cpu().numpy()[idx]
+        lpg, g = eng.log_prob_grad(dev(x))
+        lpg, g = lpg.cpu().numpy()[idx], g.cpu().numpy()[idx]
+        e_lp = max(np.max(np.abs(lp - lp_ref) / np.abs(lp_ref)), np.max(np.abs(lpg - lp_ref) / np.abs(lp_ref)))
+        e_g = np.abs(g - g_ref).max() / gmax
+        print("%s prec %d: %d tiles, log_prob rel err %.2e, gradient err / max %.2e" % (name, prec, n, e_lp, e_g))
+        assert e_lp <= 1e-4 and e_g <= 2e-4, (name, prec, e_lp, e_g)
+    assert eng.range_status() == (False, 0)
+    eng.close()
