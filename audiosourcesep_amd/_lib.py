@@ -132,6 +132,9 @@ SYMBOLS = {
     "glowk_mel_frames": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, _vp]),
     "glowk_tile_cut": (_i, [_vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
     "glowk_tile_stitch": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_frames_to_tiles": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
+    "glowk_basis_update_frames": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp]),
 }
 
 _lib = None

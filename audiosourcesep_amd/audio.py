@@ -628,10 +628,15 @@ def _check_long_frames(f, what):
         raise ValueError("%s: expected [C, 96, F] dB frames with 1 <= F <= %d, got %s" % (what, GRIFFINLIM_MAX_FRAMES, tuple(f.shape)))
 
 
+def _check_top_db(top_db):
+    if not (top_db is None or (isinstance(top_db, (int, float, np.integer, np.floating)) and math.isfinite(top_db))):
+        raise ValueError("top_db: expected None or a finite number, got %r" % (top_db,))
+
+
 def tile_count(n_frames, width=64, tile_hop=32):
     """Tiles of ``width`` frames every ``tile_hop`` frames that cover ``n_frames``: 1 if they fit one tile, else
     1 + ceil((n_frames - width) / tile_hop)."""
-    return 1 if n_frames <= width else 1 + -(-(n_frames - width) // tile_hop)
+    return basis.tile_count(n_frames, width, tile_hop)
 
 
 def mel_frames(y, return_stft=False):
@@ -659,8 +664,7 @@ def frame_tiles(frames, width=64, tile_hop=32, top_db=80.0):
         f = f[None]
     _check_long_frames(f, "frames")
     _check_tiling(width, tile_hop)
-    if not (top_db is None or (isinstance(top_db, (int, float, np.integer, np.floating)) and math.isfinite(top_db))):
-        raise ValueError("top_db: expected None or a finite number, got %r" % (top_db,))
+    _check_top_db(top_db)
     f = f.to(device=_device(f), dtype=torch.float32).contiguous()
     C, _, F = f.shape
     out = torch.empty((C, tile_count(F, width, tile_hop), NMEL, width, 1), device=f.device, dtype=torch.float32)
@@ -750,21 +754,29 @@ def _tile_width(flows):
 
 
 def separate_long(mix, flows, sigmas, restores=None, tile_hop=32, T=100, delta=2e-5, seed=0, top_db=80.0, iters=200, wiener=True,
-                  em_iter=2, mixing="db"):
+                  em_iter=2, mixing="db", coupled=False):
     """A whole mixture (wav path, [n] mono or [2, n] stereo 16 kHz samples, n > 1024) -> S = len(flows) stems exactly as long as
     it and aligned with it, S in [2, 16].  One STFT of the signal (``mel_frames``; stereo: of both channels and of the downmix
     (L + R) / 2, which is what the priors see); tiles of the priors' width W every ``tile_hop`` frames with the per-tile ``top_db``
     floor (``frame_tiles``); ``basis.basis_outer_loop_n`` on them from ``separate_sources``' start states and RNG streams;
     the separated tiles cross-faded into frames (``stitch_tiles``); ``invert_frames`` (``wiener``, ``iters``; stereo: ``em_iter``
     EM iterations of the multichannel Wiener filter, one model for the signal).  The priors see independent tiles: only their
-    estimates are cross-faded.  Returns ``(ys, mixed_frames, source_frames)``: [S, n] (stereo [S, 2, n]), the mixture's (downmix's)
-    unfloored frames [96, F] and the separated frames [S, 96, F], F = 1 + ceil(n / 512)."""
+    estimates are cross-faded.
+    ``coupled=True`` runs ONE chain over the whole signal instead (``basis.basis_outer_loop_frames``): the state is the signal's
+    frames, the priors see its overlapping tiles, and a frame's prior score is the cross-fade of the scores of the tiles that
+    cover it, so the tiles are coupled inside the Langevin loop and nothing is stitched afterwards.  The mixture's frames are
+    floored once over the whole signal (max - ``top_db``, clipped to [-100, 20]; None or 0: no floor), the start states are
+    -100 + 120 U in the frame layout from the streams of ``separate_sources``, and ``source_frames`` is the chain's result.
+    Returns ``(ys, mixed_frames, source_frames)``: [S, n] (stereo [S, 2, n]), the mixture's (downmix's) unfloored frames [96, F]
+    and the separated frames [S, 96, F], F = 1 + ceil(n / 512)."""
     flows = list(flows)
     if not 2 <= len(flows) <= basis.MAX_SOURCES:
         raise ValueError("flows: expected 2..%d priors, got %d" % (basis.MAX_SOURCES, len(flows)))
     W = _tile_width(flows)
     _check_tiling(W, tile_hop)
     _check_em_iter(em_iter, "em_iter")
+    if not isinstance(coupled, bool):
+        raise ValueError("coupled: expected True or False, got %r" % (coupled,))
     if isinstance(mix, (str, bytes)) or hasattr(mix, "__fspath__"):
         y = load_audio(mix, sr=SR, mono=False)[0]
         y = y[0] if y.shape[0] == 1 else y
@@ -776,6 +788,15 @@ def separate_long(mix, flows, sigmas, restores=None, tile_hop=32, T=100, delta=2
     y = y.to(device=_device(y), dtype=torch.float32)
     mel, X = mel_frames(torch.stack([y[0], y[1], (y[0] + y[1]) / 2]) if stereo else y, return_stft=True)
     mixed_frames = mel[-1]
+    if coupled:
+        _check_top_db(top_db)
+        floored = torch.maximum(mixed_frames, mixed_frames.max() - float(top_db)) if top_db else mixed_frames
+        xs = torch.stack([-100.0 + 120.0 * basis.device_randn(tuple(mixed_frames.shape), mixed_frames.device, seed=seed, which=14 + (k & 1),
+                                                              uniform=True, pair=k >> 1) for k in range(len(flows))])
+        source_frames, _ = basis.basis_outer_loop_frames(floored.clamp(-100.0, 20.0), xs, flows, sigmas, W, tile_hop, restores=restores,
+                                                         T=T, delta=delta, seed=seed, mixing=mixing)
+        ys = invert_frames(source_frames, X[:2] if stereo else X[0], n, wiener=wiener, iters=iters, em_iter=em_iter)
+        return ys, mixed_frames, source_frames
     mixed = frame_tiles(mixed_frames, W, tile_hop, top_db)[0]                             # [N, 96, W, 1]
     xs = [-100.0 + 120.0 * basis.device_randn(tuple(mixed.shape), mixed.device, seed=seed, which=14 + (k & 1), uniform=True, pair=k >> 1)
           for k in range(len(flows))]

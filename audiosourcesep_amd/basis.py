@@ -25,6 +25,13 @@ stream ``k & 1`` of source pair ``k >> 1``, so sources 0 and 1 see the two-sourc
 The S gradient evaluations go to at most four side streams, round-robin.  The two-source functions (``mixing_db``,
 ``langevin_update``, ``basis_inner_loop``, ``basis_outer_loop``, ``prior_parallel_layout`` / ``make_pair_group`` /
 ``exchange_prior_gradients``) are these at S = 2 under their first signatures: the same kernel, the same loops.
+
+One chain over a whole signal: the ``*_frames`` functions (``cut_frames``, ``langevin_update_frames``,
+``basis_inner_loop_frames``, ``basis_outer_loop_frames``) keep the Langevin state as the signal's frames [S, rows, F].  The priors
+see its overlapping tiles, and a frame's prior score is the cross-fade of the scores of the tiles that cover it, with weights that
+sum to one, so overlapping tiles are coupled inside the loop (not in the reference, which cuts disjoint
+extracts).  The update, the stitch in front of it and the next step's tiles are one kernel (``glowk_basis_update_frames``,
+csrc/glowk_frames.h), which shares the update's device code with ``glowk_basis_update_n``.
 """
 import ctypes
 import math
@@ -329,6 +336,24 @@ def _grad_n(xs, models, streams):
     return out
 
 
+def _side_streams(streams, models, device):
+    """``streams`` of the loops: "auto" becomes one side stream per distinct engine on the GPU, at most four (None for one engine
+    or CPU tensors); anything else is passed through."""
+    if not (isinstance(streams, str) and streams == "auto"):
+        return streams
+    distinct = len({id(getattr(m, "engine", m)) for m in models})
+    if device.type == "cuda" and distinct > 1:
+        return [torch.cuda.Stream(device=device) for _ in range(min(distinct, MAX_SIDE_STREAMS))]
+    return None
+
+
+def _step_sizes(sigma_idx, sigmas, delta):
+    """-> (eta, lambda_recon) of noise level ``sigma_idx`` (run_basis_sep.py:157-161)."""
+    sigma = float(sigmas[sigma_idx])
+    sigma_l = float(sigmas[-1])
+    return float(np.float32(delta * (sigma / sigma_l) ** 2)), 1.0 / (sigma ** 2)
+
+
 def basis_inner_loop_n(mixed, xs, models, sigma_idx, sigmas, delta=2e-5, T=100, noise_fn=None, debug=False, streams="auto", seed=0,
                        step0=0, offset=0, prior_group=None, prior_index=None, mixing="db"):
     """run_basis_sep.py:152-214 (model_type == 'glow') for S = len(xs) sources -> list of S tensors.  ``noise_fn(t, k, shape) ->
@@ -352,17 +377,8 @@ def basis_inner_loop_n(mixed, xs, models, sigma_idx, sigmas, delta=2e-5, T=100, 
     if pp and (not isinstance(prior_index, int) or not 0 <= prior_index < S):
         raise ValueError("prior_index must be 0..%d in prior-parallel mode" % (S - 1))
     on_gpu = xs[0].device.type == "cuda"
-    if pp:
-        streams = None
-    if isinstance(streams, str) and streams == "auto":
-        streams = None
-        distinct = len({id(getattr(m, "engine", m)) for m in models})
-        if on_gpu and distinct > 1:
-            streams = [torch.cuda.Stream(device=xs[0].device) for _ in range(min(distinct, MAX_SIDE_STREAMS))]
-    sigma = float(sigmas[sigma_idx])
-    sigma_l = float(sigmas[-1])
-    eta = float(np.float32(delta * (sigma / sigma_l) ** 2))
-    lambda_recon = 1.0 / (sigma ** 2)
+    streams = None if pp else _side_streams(streams, models, xs[0].device)
+    eta, lambda_recon = _step_sizes(sigma_idx, sigmas, delta)
 
     def grads(cur):
         if not pp:
@@ -379,7 +395,7 @@ def basis_inner_loop_n(mixed, xs, models, sigma_idx, sigmas, delta=2e-5, T=100, 
         eps = [noise_fn(t, k, xs[k].shape) for k in range(S)] if noise_fn is not None else None
         langevin_update_n(mixed, xs, gs, eta, lambda_recon, eps, seed=seed, step=step0 + t, nonfinite=flag, offset=offset, mixing=mixing)
         if debug:
-            assert int(flag.item()) == 0, (sigma, t)   # run_basis_sep.py:183-191
+            assert int(flag.item()) == 0, (float(sigmas[sigma_idx]), t)   # run_basis_sep.py:183-191
     return xs
 
 
@@ -388,14 +404,31 @@ def _inner_loop_host_n(mixed, xs, grads, eta, lambda_recon, T, noise_fn, debug, 
     if noise_fn is None:
         noise_fn = lambda t, k, shape: torch.randn(shape, dtype=torch.float32)  # noqa: E731
     for t in range(T):
-        eps = [math.sqrt(2.0 * eta) * noise_fn(t, k, x.shape) for k, x in enumerate(xs)]
-        gs = grads(xs)
-        mix = mixing(xs, process)
-        ms = grad_mixing(xs, process)
-        xs = [x + eta * (g + lambda_recon * m * (mixed - mix)) + e for x, g, m, e in zip(xs, gs, ms, eps)]
+        z = [noise_fn(t, k, x.shape) for k, x in enumerate(xs)]
+        xs = _update_host_n(mixed, xs, grads(xs), z, eta, lambda_recon, process)
         if debug:
             assert all(torch.isfinite(x).all() for x in xs), t
     return xs
+
+
+def _models_at_level(models, restores, sigma, prior_group=None, prior_index=None):
+    """The S priors with their weights for noise level ``sigma`` (``restores`` as in ``basis_outer_loop_n``); None for a prior that
+    another rank of ``prior_group`` owns."""
+    current = []
+    for k, (model, restore) in enumerate(zip(models, restores)):
+        if prior_group is not None and k != prior_index:
+            current.append(None)          # another rank of the group owns this prior
+            continue
+        if restore is not None:
+            state = restore[float(sigma)] if float(sigma) in restore else restore[sigma]
+            if hasattr(state, "log_prob"):      # a resident flow for this noise level: no weight swap at all
+                model = state
+            elif isinstance(state, str):
+                model.restore(state)            # ~0.4 s for config B (host re-pack on 16 threads + 0.5 GB upload)
+            else:
+                model.load_state_dict(state)
+        current.append(model)
+    return current
 
 
 def basis_outer_loop_n(mixed, xs, models, sigmas, restores=None, T=100, delta=2e-5, noise_fn=None, debug=False, seed=0, tile_offset=0,
@@ -418,20 +451,7 @@ def basis_outer_loop_n(mixed, xs, models, sigmas, restores=None, T=100, delta=2e
     elems_per_tile = int(np.prod(mixed.shape[1:]))
     x_arr = {"x%d" % (k + 1): [x.cpu().numpy()] for k, x in enumerate(xs)}
     for sigma_idx, sigma in enumerate(sigmas):
-        current = []
-        for k, (model, restore) in enumerate(zip(models, restores)):
-            if prior_group is not None and k != prior_index:
-                current.append(None)          # another rank of the group owns this prior
-                continue
-            if restore is not None:
-                state = restore[float(sigma)] if float(sigma) in restore else restore[sigma]
-                if hasattr(state, "log_prob"):      # a resident flow for this noise level: no weight swap at all
-                    model = state
-                elif isinstance(state, str):
-                    model.restore(state)            # ~0.4 s for config B (host re-pack on 16 threads + 0.5 GB upload)
-                else:
-                    model.load_state_dict(state)
-            current.append(model)
+        current = _models_at_level(models, restores, sigma, prior_group, prior_index)
         nf = None if noise_fn is None else (lambda t, k, shape, _s=sigma_idx: noise_fn(_s, t, k, shape))
         xs = basis_inner_loop_n(mixed, xs, current, sigma_idx, sigmas, delta=delta, T=T, noise_fn=nf, debug=debug, seed=seed,
                                 step0=sigma_idx * T, offset=int(tile_offset) * elems_per_tile, prior_group=prior_group,
@@ -439,3 +459,209 @@ def basis_outer_loop_n(mixed, xs, models, sigmas, restores=None, T=100, delta=2e
         for k, x in enumerate(xs):
             x_arr["x%d" % (k + 1)].append(x.cpu().numpy())
     return xs, x_arr
+
+
+# ---- one chain over a whole signal: the state is the signal's frames, the priors see its overlapping tiles -------------------------
+MAX_TILE_WIDTH = 128
+MAX_FRAMES = 1 << 20
+MAX_ROWS = 1 << 16
+
+
+def tile_count(n_frames, width, hop):
+    """Tiles of ``width`` frames every ``hop`` frames that cover ``n_frames``: 1 if they fit one tile, else
+    1 + ceil((n_frames - width) / hop)."""
+    return 1 if n_frames <= width else 1 + -(-(n_frames - width) // hop)
+
+
+def _check_frame_tiling(width, hop):
+    for name, v in (("width", width), ("hop", hop)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: expected an integer, got %r" % (name, v))
+    if not 2 <= width <= MAX_TILE_WIDTH:
+        raise ValueError("width: expected a tile width in [2, %d], got %d" % (MAX_TILE_WIDTH, width))
+    if not 1 <= hop <= width:
+        raise ValueError("hop: expected an integer in [1, width = %d], got %d" % (width, hop))
+
+
+def stitch_window(width, dtype=torch.float32):
+    """w[j] = sin^2(pi (j + 1/2) / width), built in float64 and rounded once: the cross-fade weights of ``glowk_tile_stitch``."""
+    return (torch.sin(math.pi * (torch.arange(width, dtype=torch.float64) + 0.5) / width) ** 2).to(dtype)
+
+
+def cut_frames(x, width, hop, pad=-100.0):
+    """Frames [rows, F] or [nsig, rows, F] -> tiles [N, rows, width] ([nsig, N, rows, width]), N = ``tile_count(F, width, hop)``:
+    tile t holds frames [t hop, t hop + width) and ``pad`` at and beyond F.  A raw gather (``glowk_frames_to_tiles``): no floor and
+    no clip, unlike ``audio.frame_tiles`` -- BASIS states leave [-100, 20].  CPU tensors take the torch formula."""
+    _check_frame_tiling(width, hop)
+    if x.dim() not in (2, 3) or not 1 <= x.shape[-1] <= MAX_FRAMES or not 1 <= x.shape[-2] <= MAX_ROWS:
+        raise ValueError("cut_frames: expected [rows, F] or [nsig, rows, F] frames with rows <= %d and 1 <= F <= %d, got %s"
+                         % (MAX_ROWS, MAX_FRAMES, tuple(x.shape)))
+    rows, F = x.shape[-2:]
+    N = tile_count(F, width, hop)
+    if not x.is_cuda:
+        padded = torch.nn.functional.pad(x, (0, (N - 1) * hop + width - F), value=float(pad))
+        return torch.stack([padded[..., t * hop:t * hop + width] for t in range(N)], dim=-3)
+    x = x.to(torch.float32).contiguous()
+    nsig = x.shape[0] if x.dim() == 3 else 1
+    out = torch.empty(tuple(x.shape[:-2]) + (N, rows, width), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().glowk_frames_to_tiles(_p(x), nsig, rows, F, int(width), int(hop), float(pad), _p(out), _s(x)))
+    return out
+
+
+def stitch_scores(g_tiles, n_frames, hop):
+    """Gradient tiles [N, rows, width] -> the prior score of every frame [rows, n_frames]: the mean of the scores the covering tiles
+    give it, weighted by ``stitch_window`` at the frame's place in each; gradients with respect to pad cells are dropped.  Torch
+    formula in the tiles' dtype (the CPU loop; on the GPU ``glowk_basis_update_frames`` does this in front of its update)."""
+    N, rows, width = g_tiles.shape
+    w = stitch_window(width, g_tiles.dtype)
+    span = (N - 1) * hop + width
+    num, den = g_tiles.new_zeros((rows, span)), g_tiles.new_zeros(span)
+    for t in range(N):
+        num[:, t * hop:t * hop + width] += w * g_tiles[t]
+        den[t * hop:t * hop + width] += w
+    out = (num / den)[:, :n_frames]
+    for f in range(n_frames):                           # a frame under exactly one tile takes that tile's gradient as it is
+        t_hi, t_lo = min(N - 1, f // hop), 0 if f < width else (f - width) // hop + 1
+        if t_lo == t_hi:
+            out[:, f] = g_tiles[t_lo][:, f - t_lo * hop]
+    return out
+
+
+def _as_tiles(g, N, rows, width, what):
+    if g.dim() == 4 and g.shape[3] == 1:
+        g = g[..., 0]
+    if tuple(g.shape) != (N, rows, width):
+        raise ValueError("%s: expected [%d, %d, %d] or [%d, %d, %d, 1] tiles, got %s" % (what, N, rows, width, N, rows, width, tuple(g.shape)))
+    return g
+
+
+def langevin_update_frames(mixed, x, g_tiles, width, hop, eta, lambda_recon, eps=None, seed=0, step=0, nonfinite=None, mixing="db",
+                           tiles_out=None, pad=-100.0):
+    """run_basis_sep.py:163-181 on the frames of a whole signal, IN PLACE on ``x`` [S, rows, F] (contiguous float32), for S
+    sources in one kernel (``glowk_basis_update_frames``).  ``g_tiles``: S gradient tensors [N, rows, width(, 1)], source k's the
+    gradient of prior k at ``cut_frames(x[k], width, hop)``; frame f takes their cross-fade (``stitch_scores``) as its
+    ``grad_logprob``.  ``mixed`` [rows, F].  ``eps``: None, or S entries, each None or [rows, F] standard-normal draws; a source
+    without draws takes the device RNG's, stream ``k & 1`` of pair ``k >> 1`` at (seed, step), element b F + f at offset 0.
+    ``tiles_out`` (optional, [S, N, rows, width] contiguous float32): receives ``cut_frames`` of the updated ``x``, pad cells
+    included -- the tiles of the next step's gradient calls.  CPU tensors take the torch formulas."""
+    mid = _mixing_id(mixing)
+    _check_frame_tiling(width, hop)
+    if x.dim() != 3:
+        raise ValueError("langevin_update_frames: expected states [S, rows, F], got %s" % (tuple(x.shape),))
+    S, rows, F = x.shape
+    N = tile_count(F, width, hop)
+    if len(g_tiles) != S or (eps is not None and len(eps) != S):
+        raise ValueError("langevin_update_frames: %d states need %d gradients (and noise entries)" % (S, S))
+    if tuple(mixed.shape) != (rows, F) or any(e is not None and tuple(e.shape) != (rows, F) for e in (eps or [])):
+        raise ValueError("langevin_update_frames: the mixture and the noise must be [rows, F] = [%d, %d]" % (rows, F))
+    gs = [_as_tiles(g, N, rows, width, "g_tiles[%d]" % k) for k, g in enumerate(g_tiles)]
+    if tiles_out is not None and tuple(tiles_out.shape) != (S, N, rows, width):
+        raise ValueError("tiles_out: expected [%d, %d, %d, %d], got %s" % (S, N, rows, width, tuple(tiles_out.shape)))
+    if not x.is_cuda:
+        xs = list(x)
+        z = [e if e is not None else torch.randn((rows, F), dtype=x.dtype) for e in (eps or [None] * S)]
+        new = _update_host_n(mixed, xs, [stitch_scores(g, F, hop) for g in gs], z, eta, lambda_recon, mixing)
+        x.copy_(torch.stack(new))
+        if tiles_out is not None:
+            tiles_out.copy_(cut_frames(x, width, hop, pad))
+        return
+    for t, name in ((x, "x"), (tiles_out, "tiles_out")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("langevin_update_frames: %s is written in place and must be a contiguous float32 CUDA tensor" % name)
+    mixed_c = mixed.to(torch.float32).contiguous()
+    gs_c = [g.to(torch.float32).contiguous() for g in gs]
+    eps_c = None if eps is None else [e.to(torch.float32).contiguous() if e is not None else None for e in eps]
+    _lib.check(_lib.load().glowk_basis_update_frames(_p(x), _ptrs(gs_c), _ptrs(eps_c) if eps_c is not None else None, S, _p(mixed_c),
+                                                     rows, F, int(width), int(hop), mid, float(eta), float(lambda_recon), int(seed),
+                                                     int(step), float(pad), _p(tiles_out), _p(nonfinite), _s(x)))
+
+
+def _update_host_n(mixed, xs, gs, z, eta, lambda_recon, process):
+    """One step on torch formulas: ``z[k]`` are standard-normal draws."""
+    mix = mixing(xs, process)
+    ms = grad_mixing(xs, process)
+    return [x + eta * (g + lambda_recon * m * (mixed - mix)) + math.sqrt(2.0 * eta) * e for x, g, m, e in zip(xs, gs, ms, z)]
+
+
+def _check_frames_problem(mixed, x, models, width, tile_hop):
+    """The states as one [S, rows, F] tensor, checked against the mixture, the priors and the tiling."""
+    x = torch.stack(list(x)) if isinstance(x, (list, tuple)) else x
+    if x.dim() != 3:
+        raise ValueError("BASIS on frames: expected states [S, rows, F], got %s" % (tuple(x.shape),))
+    S, rows, F = x.shape
+    if S < 2 or S > MAX_SOURCES:
+        raise ValueError("BASIS: the number of sources must be 2..%d, got %d" % (MAX_SOURCES, S))
+    if len(models) != S:
+        raise ValueError("BASIS: %d states need %d priors, got %d" % (S, S, len(models)))
+    _check_frame_tiling(width, tile_hop)
+    if not 1 <= F <= MAX_FRAMES or not 1 <= rows <= MAX_ROWS:
+        raise ValueError("BASIS on frames: expected rows <= %d and 1 <= F <= %d, got %s" % (MAX_ROWS, MAX_FRAMES, tuple(x.shape)))
+    if tuple(mixed.shape) != (rows, F):
+        raise ValueError("BASIS on frames: the mixture must be [rows, F] = [%d, %d], got %s" % (rows, F, tuple(mixed.shape)))
+    for k, m in enumerate(models):
+        shape = getattr(m, "event_shape", None)
+        if shape is not None and tuple(int(d) for d in shape) != (rows, width, 1):
+            raise ValueError("BASIS on frames: prior %d takes tiles %s, not [rows, width, 1] = [%d, %d, 1]"
+                             % (k, tuple(int(d) for d in shape), rows, width))
+    return x
+
+
+def basis_inner_loop_frames(mixed, x, models, sigma_idx, sigmas, width, tile_hop, delta=2e-5, T=100, noise_fn=None, debug=False,
+                            streams="auto", seed=0, step0=0, mixing="db"):
+    """``basis_inner_loop_n`` as ONE chain over a whole signal -> x [S, rows, F].  The state is the signal's frames ``x`` [S, rows,
+    F] (``mixed`` [rows, F]); prior k sees the N = ``tile_count(F, width, tile_hop)`` overlapping tiles of x[k] (``cut_frames``), and
+    the score of a frame is the mean of the scores the tiles that cover it give it, weighted by w[j] = sin^2(pi (j + 1/2) / width)
+    at the frame's place in each and divided by the weights' sum.  The weights of a frame thus sum to one: the prior pulls on a
+    frame as hard as in a per-tile chain, two tiles never hold different values for one frame, and at tile_hop = width this is
+    ``basis_inner_loop_n`` on the disjoint tiles.  A step on the GPU is the S gradient evaluations (``_grad_n``: ``streams`` and the
+    range-guard handling as in ``basis_inner_loop_n``) and one launch of ``glowk_basis_update_frames``, which also writes the next
+    step's tiles.  ``noise_fn(t, k, shape)`` gets the frame shape [rows, F]; without it the kernel draws at (seed, step0 + t).
+    There is no prior-parallel mode."""
+    _mixing_id(mixing)
+    models = list(models)
+    x = _check_frames_problem(mixed, x, models, width, tile_hop)
+    S, rows, F = x.shape
+    streams = _side_streams(streams, models, x.device)
+    eta, lambda_recon = _step_sizes(sigma_idx, sigmas, delta)
+
+    def tile_grads(tiles):
+        return _grad_n([tiles[k].unsqueeze(-1) for k in range(S)], models, streams)
+
+    if not x.is_cuda:
+        def grads(xs):
+            return [stitch_scores(g[..., 0], F, tile_hop) for g in tile_grads(cut_frames(torch.stack(xs), width, tile_hop))]
+        return torch.stack(_inner_loop_host_n(mixed, list(x), grads, eta, lambda_recon, T, noise_fn, debug, mixing))
+    mixed = mixed.to(torch.float32).contiguous()
+    x = x.to(torch.float32).clone().contiguous()                  # (the update is in place)
+    tiles = cut_frames(x, width, tile_hop)                        # [S, N, rows, width]: rewritten by every update
+    flag = torch.zeros(1, dtype=torch.int32, device=x.device) if debug else None
+    for t in range(T):
+        gs = tile_grads(tiles)
+        eps = [noise_fn(t, k, (rows, F)) for k in range(S)] if noise_fn is not None else None
+        langevin_update_frames(mixed, x, gs, width, tile_hop, eta, lambda_recon, eps, seed=seed, step=step0 + t, nonfinite=flag,
+                               mixing=mixing, tiles_out=tiles)
+        if debug:
+            assert int(flag.item()) == 0, (float(sigmas[sigma_idx]), t)   # run_basis_sep.py:183-191
+    return x
+
+
+def basis_outer_loop_frames(mixed, x, models, sigmas, width, tile_hop, restores=None, T=100, delta=2e-5, noise_fn=None, debug=False,
+                            seed=0, mixing="db"):
+    """``basis_outer_loop_n`` over ``basis_inner_loop_frames``: the annealing over ``sigmas`` with the per-level ``restores`` of
+    ``basis_outer_loop_n``.  ``noise_fn(sigma_idx, t, k, shape)`` with the frame shape.  Returns ``(x [S, rows, F], x_arr)``, the
+    trajectory ``{"x1": [...], .., "xS": [...]}`` of frame arrays (start state and one entry per level)."""
+    models = list(models)
+    x = _check_frames_problem(mixed, x, models, width, tile_hop)
+    S = x.shape[0]
+    if restores is not None and len(restores) != S:
+        raise ValueError("BASIS: %d states need %d priors (and restore maps)" % (S, S))
+    restores = [None] * S if restores is None else list(restores)
+    x_arr = {"x%d" % (k + 1): [x[k].cpu().numpy()] for k in range(S)}
+    for sigma_idx, sigma in enumerate(sigmas):
+        current = _models_at_level(models, restores, sigma)
+        nf = None if noise_fn is None else (lambda t, k, shape, _s=sigma_idx: noise_fn(_s, t, k, shape))
+        x = basis_inner_loop_frames(mixed, x, current, sigma_idx, sigmas, width, tile_hop, delta=delta, T=T, noise_fn=nf, debug=debug,
+                                    seed=seed, step0=sigma_idx * T, mixing=mixing)
+        for k in range(S):
+            x_arr["x%d" % (k + 1)].append(x[k].cpu().numpy())
+    return x, x_arr

@@ -1,7 +1,7 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
 // systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h),
-// whole-signal mel frames and overlapping tiles (glowk_longform.h)
+// whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -10,6 +10,7 @@
 #include "glowk_resample.h"
 #include "glowk_stereo.h"
 #include "glowk_longform.h"
+#include "glowk_frames.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -825,6 +826,22 @@ int tile_geometry(const char* who, int nsig, int width, int hop) {
   if (hop < 1 || hop > width) return fail(std::string(who) + ": hop must be in [1, width]");
   return 0;
 }
+
+// sin^2(pi (j + 1/2) / width) in fp64, rounded once; zero past the width (never read)
+glowk_long::StitchWindow stitch_window(int width) {
+  glowk_long::StitchWindow win;
+  for (int j = 0; j < glowk_long::MAX_WIDTH; ++j) {
+    const double sn = std::sin(3.14159265358979323846 * (j + 0.5) / width);
+    win.w[j] = j < width ? (float)(sn * sn) : 0.0f;
+  }
+  return win;
+}
+
+// [a, a + na) and [b, b + nb) floats share an element
+bool floats_overlap(const float* a, size_t na, const float* b, size_t nb) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p < q + nb * sizeof(float) && q < p + na * sizeof(float);
+}
 }  // namespace
 
 int glowk_mel_frames(const float* audio_dev, int nsig, int64_t n_samples, float* mel_db_dev, float* stft_dev, void* stream) {
@@ -883,14 +900,88 @@ int glowk_tile_stitch(const float* tiles_dev, int nsig, int N, int width, int ho
   int dev;
   if (int rc = audio_device({tiles_dev, frames_dev}, &dev, "tile_stitch")) return rc;
   DeviceGuard dg(dev);
-  StitchWindow win;                            // sin^2(pi (j + 1/2) / width) in fp64, rounded once; zero past the width (never read)
-  for (int j = 0; j < MAX_WIDTH; ++j) {
-    const double sn = std::sin(3.14159265358979323846 * (j + 0.5) / width);
-    win.w[j] = j < width ? (float)(sn * sn) : 0.0f;
-  }
+  const StitchWindow win = stitch_window(width);
   hipLaunchKernelGGL(k_tile_stitch, dim3((unsigned)(nsig * fblocks), glowk_audio::NMEL), dim3(256), 0, (hipStream_t)stream, tiles_dev, N, width,
                      hop, frames, fblocks, win, frames_dev);
   LAUNCHCHK("k_tile_stitch");
+  return 0;
+}
+
+// ---- BASIS as one chain over a whole signal: the state is its frames, the priors see its overlapping tiles (glowk_frames.h) --------
+int glowk_frames_to_tiles(const float* x_dev, int nsig, int rows, int frames, int width, int hop, float pad, float* tiles_dev,
+                          void* stream) {
+  using namespace glowk_long;
+  if (int rc = tile_geometry("frames_to_tiles", nsig, width, hop)) return rc;
+  if (rows < 1 || rows > MAX_ROWS) return fail("frames_to_tiles: rows must be in [1, 65536]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail("frames_to_tiles: frames must be in [1, 2^20]");
+  if (!(std::fabs(pad) < 1e30f)) return fail("frames_to_tiles: pad must be finite");
+  const int N = frames <= width ? 1 : 1 + (frames - width + hop - 1) / hop;
+  if ((double)nsig * N * rows * width > 1e12) return fail("frames_to_tiles: too many tile cells for one launch");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!x_dev || !tiles_dev) return fail("null tensor");
+  const size_t cells = (size_t)nsig * N * rows * width;
+  if (floats_overlap(x_dev, (size_t)nsig * rows * frames, tiles_dev, cells)) return fail("frames_to_tiles: the tiles alias the frames");
+  int dev;
+  if (int rc = audio_device({x_dev, tiles_dev}, &dev, "frames_to_tiles")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_frames_to_tiles, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, rows, frames, N,
+                     width, hop, pad, cells, tiles_dev);
+  LAUNCHCHK("k_frames_to_tiles");
+  return 0;
+}
+
+int glowk_basis_update_frames(float* x_dev, const float* const* g, const float* const* eps, int nsrc, const float* mixed_dev, int rows,
+                              int frames, int width, int hop, int mixing, float eta, float lambda_recon, uint64_t seed, uint64_t step,
+                              float pad, float* tiles_out_dev, int* nonfinite_dev, void* stream) {
+  using namespace glowk_long;
+  if (nsrc < 2 || nsrc > GLOWK_BASIS_MAX_SOURCES) return fail("basis_update_frames: the number of sources must be 2..16");
+  if (mixing != GLOWK_MIX_DB && mixing != GLOWK_MIX_MEAN) return fail("basis_update_frames: unknown mixing process");
+  if (int rc = tile_geometry("basis_update_frames", 1, width, hop)) return rc;
+  if (rows < 1 || rows > MAX_ROWS) return fail("basis_update_frames: rows must be in [1, 65536]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail("basis_update_frames: frames must be in [1, 2^20]");
+  if (step >= ((uint64_t)1 << 48)) return fail("basis_update_frames: step must be below 2^48 (the source pair shares its counter word)");
+  if (!(eta >= 0.0f)) return fail("basis_update_frames: eta must be non-negative");
+  if (!(std::fabs(pad) < 1e30f)) return fail("basis_update_frames: pad must be finite");
+  if (!x_dev || !g || !mixed_dev) return fail("null tensor");
+  for (int k = 0; k < nsrc; ++k)
+    if (!g[k]) return fail("null tensor");
+  const int N = frames <= width ? 1 : 1 + (frames - width + hop - 1) / hop;
+  const size_t n = (size_t)rows * frames, per_source = (size_t)N * rows * width;
+  if (floats_overlap(x_dev, nsrc * n, mixed_dev, n)) return fail("basis_update_frames: the states alias the mixture");
+  if (tiles_out_dev && (floats_overlap(tiles_out_dev, nsrc * per_source, x_dev, nsrc * n) || floats_overlap(tiles_out_dev, nsrc * per_source, mixed_dev, n)))
+    return fail("basis_update_frames: tiles_out aliases the states or the mixture");
+  for (int k = 0; k < nsrc; ++k) {
+    if (floats_overlap(g[k], per_source, x_dev, nsrc * n)) return fail("basis_update_frames: a gradient aliases the states");
+    if (tiles_out_dev && floats_overlap(g[k], per_source, tiles_out_dev, nsrc * per_source))
+      return fail("basis_update_frames: a gradient aliases tiles_out");
+    if (eps && eps[k] && (floats_overlap(eps[k], n, x_dev, nsrc * n) || (tiles_out_dev && floats_overlap(eps[k], n, tiles_out_dev, nsrc * per_source))))
+      return fail("basis_update_frames: a noise tensor aliases the states or tiles_out");
+  }
+  int dev;
+  if (int rc = audio_device({x_dev, mixed_dev, tiles_out_dev, nonfinite_dev}, &dev, "basis_update_frames")) return rc;
+  for (int k = 0; k < nsrc; ++k)
+    if (int rc = audio_device({x_dev, g[k], eps ? eps[k] : nullptr}, &dev, "basis_update_frames")) return rc;
+  DeviceGuard dg(dev);
+  BasisFramesArgs a;
+  uintptr_t bits = (uintptr_t)x_dev | (uintptr_t)mixed_dev;
+  for (int k = 0; k < nsrc; ++k) {
+    a.g[k] = g[k]; a.eps[k] = eps ? eps[k] : nullptr;
+    bits |= (uintptr_t)a.eps[k];
+  }
+  a.x = x_dev; a.mixed = mixed_dev; a.tiles_out = tiles_out_dev; a.nonfinite = nonfinite_dev; a.n = n; a.seed = seed; a.step = step;
+  a.rows = rows; a.F = frames; a.N = N; a.width = width; a.hop = hop; a.pad_cols = (N - 1) * hop + width - frames;
+  a.eta = eta; a.lambda_recon = lambda_recon; a.noise_scale = std::sqrt(2.0f * eta); a.pad = pad;
+  a.ln_s = (float)std::log((double)nsrc); a.inv_s = 1.0f / (float)nsrc; a.mixing = mixing; a.vec = (bits & 15) == 0 && n % 4 == 0;
+  a.win = stitch_window(width);
+  a.qblocks = (unsigned)(((n + 3) / 4 + 255) / 256);          // <= 2^26
+  const unsigned pad_blocks = tiles_out_dev ? (unsigned)(((size_t)rows * a.pad_cols + 255) / 256) : 0u;
+  const dim3 grid(a.qblocks + pad_blocks);
+  switch (nsrc) {
+#define GLOWK_CASE(s) case s: hipLaunchKernelGGL(k_basis_update_frames<s>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
+    GLOWK_BASIS_EACH_S(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_basis_update_frames");
   return 0;
 }
 

@@ -105,6 +105,39 @@ __device__ __forceinline__ float basis_mix_terms(float (&v)[S], int mixing, floa
   return mx + logf(den) - ln_s;
 }
 
+// The update of one thread's four elements, in two parts that k_basis_update_n and k_basis_update_frames (glowk_frames.h) share.
+// First the weights m[k][j] = m_k and r[j] = lambda (mixed - mix) of the elements from their S states; true if a mixture is not finite
+template <int S>
+__device__ __forceinline__ bool basis_quad_weights(const float (&x)[S][4], const float (&mixed)[4], int mixing, float ln_s, float inv_s,
+                                                   float lambda_recon, float (&m)[S][4], float (&r)[4]) {
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float v[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) v[k] = x[k][j];
+    float scale;
+    const float t = basis_mix_terms<S>(v, mixing, ln_s, inv_s, scale);
+#pragma unroll
+    for (int k = 0; k < S; ++k) m[k][j] = v[k];
+    r[j] = lambda_recon * fmaf(-scale, t, mixed[j]);
+    bad |= basis_bad(__fmul_rn(scale, t));
+  }
+  return bad;
+}
+
+// then y = x_k + eta (g_k + m_k r) + noise_scale z_k for one source; true if a gradient or a result is not finite
+__device__ __forceinline__ bool basis_quad_step(const float (&x)[4], const float (&m)[4], const float (&r)[4], const float (&g)[4],
+                                                const float (&z)[4], float eta, float noise_scale, float (&y)[4]) {
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    y[j] = fmaf(noise_scale, z[j], fmaf(eta, fmaf(m[j], r[j], g[j]), x[j]));
+    bad |= basis_bad(g[j]) | basis_bad(y[j]);
+  }
+  return bad;
+}
+
 // one thread = four consecutive elements of every source (one Philox call per source)
 template <int S>
 __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
@@ -131,19 +164,7 @@ __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
     }
   }
   float m[S][4], r[4];
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float v[S];
-#pragma unroll
-    for (int k = 0; k < S; ++k) v[k] = x[k][j];
-    float scale;
-    const float t = basis_mix_terms<S>(v, a.mixing, a.ln_s, a.inv_s, scale);
-#pragma unroll
-    for (int k = 0; k < S; ++k) m[k][j] = v[k];
-    r[j] = a.lambda_recon * fmaf(-scale, t, mixed[j]);
-    bad |= basis_bad(__fmul_rn(scale, t));
-  }
+  bool bad = basis_quad_weights<S>(x, mixed, a.mixing, a.ln_s, a.inv_s, a.lambda_recon, m, r);
 #pragma unroll
   for (int k = 0; k < S; ++k) {
     float g[4], z[4];
@@ -165,11 +186,7 @@ __global__ __launch_bounds__(256) void k_basis_update_n(BasisNArgs a) {
       for (int j = 0; j < 4; ++j) z[j] = e0 + j < a.n ? eps[e0 + j] : 0.0f;
     }
     float y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      y[j] = fmaf(a.noise_scale, z[j], fmaf(a.eta, fmaf(m[k][j], r[j], g[j]), x[k][j]));
-      bad |= basis_bad(g[j]) | basis_bad(y[j]);
-    }
+    bad |= basis_quad_step(x[k], m[k], r, g, z, a.eta, a.noise_scale, y);
     if (quad) {
       *reinterpret_cast<float4*>(a.x[k] + e0) = make_float4(y[0], y[1], y[2], y[3]);
     } else {

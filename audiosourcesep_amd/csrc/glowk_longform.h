@@ -72,6 +72,21 @@ struct StitchWindow {
   float w[MAX_WIDTH];
 };
 
+// The cross-fade of frame f of one row: t points at that row in tile 0 and `tile` floats lie between a tile's row and the next
+// tile's; tiles k_lo..k_hi cover the frame.  Shared with k_basis_update_frames (glowk_frames.h), which stitches gradient tiles
+__device__ __forceinline__ float stitch_frame(const float* __restrict__ t, size_t tile, int k_lo, int k_hi, int f, int hop,
+                                              const StitchWindow& win) {
+  if (k_lo == k_hi) return t[(size_t)k_lo * tile + (f - k_lo * hop)];    // one tile covers the frame: its value, bit for bit
+  float num = 0.0f, den = 0.0f;
+  for (int k = k_lo; k <= k_hi; ++k) {
+    const int j = f - k * hop;
+    const float w = win.w[j];
+    num = fmaf(w, t[(size_t)k * tile + j], num);
+    den += w;
+  }
+  return num / den;
+}
+
 // grid (signals x fblocks, 96).  Tiles k with 0 <= f - k hop < width: k from ceil((f - width + 1) / hop) to min(N - 1, f / hop);
 // F <= (N - 1) hop + width makes that range non-empty for every f < F
 __global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ tiles, int N, int width, int hop, int F, int fblocks,
@@ -81,21 +96,7 @@ __global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ t
   const int k_hi = min(N - 1, f / hop);
   const int k_lo = f < width ? 0 : (f - width) / hop + 1;
   const float* t = tiles + ((size_t)n * N * NMEL + m) * width;           // tile k's row m starts at t + k 96 width
-  const size_t tile = (size_t)NMEL * width;
-  float v;
-  if (k_lo == k_hi) {
-    v = t[(size_t)k_lo * tile + (f - k_lo * hop)];                       // one tile covers the frame: its value, bit for bit
-  } else {
-    float num = 0.0f, den = 0.0f;
-    for (int k = k_lo; k <= k_hi; ++k) {
-      const int j = f - k * hop;
-      const float w = win.w[j];
-      num = fmaf(w, t[(size_t)k * tile + j], num);
-      den += w;
-    }
-    v = num / den;
-  }
-  frames[((size_t)n * NMEL + m) * F + f] = v;
+  frames[((size_t)n * NMEL + m) * F + f] = stitch_frame(t, (size_t)NMEL * width, k_lo, k_hi, f, hop, win);
 }
 
 }  // namespace glowk_long

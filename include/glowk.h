@@ -487,6 +487,43 @@ int glowk_tile_cut(const float* frames_dev, int nsig, int frames, int width, int
  * [1, 2^20].  One launch, one thread per output cell, no allocation. */
 int glowk_tile_stitch(const float* tiles_dev, int nsig, int N, int width, int hop, int frames, float* frames_dev, void* stream);
 
+/* --- BASIS as one chain over a whole signal: the state is its frames, the priors see its overlapping tiles -------------------- */
+/* The project's own (glowk_tile_stitch above cross-fades finished estimates of chains that never hear of each other; here the
+ * tiles are coupled inside the Langevin loop).  For source k the state is x_k [rows][F]; tile t of it, c_t(x_k), holds frames
+ * [t hop, t hop + width) and `pad` at and beyond F, t = 0 .. N - 1, N = 1 if F <= width, else 1 + ceil((F - width) / hop).  The
+ * prior score of a frame is the mean of the scores the tiles that cover it give it, weighted by glowk_tile_stitch's window,
+ *     s_k[b][f] = sum_t w[f - t hop] grad log p_k(c_t(x_k))[b][f - t hop] / sum_t w[f - t hop],   w[j] = sin^2(pi (j + 1/2) / width),
+ * over the t with 0 <= f - t hop < width: glowk_tile_stitch's arithmetic on gradient tiles (the same table, t ascending, fp32
+ * fused multiply-adds; a frame under exactly one tile takes that tile's gradient, bit for bit).  The weights of a frame sum to
+ * one, so the prior pulls on every frame as hard as in a per-tile chain; at hop = width this is the per-tile chain.  Gradients
+ * with respect to pad cells are dropped.  Every tensor is float32 device memory on one device (a host pointer is refused); each
+ * call is one launch on `stream`, synchronises nothing with the host, uses no atomics and no allocation, and sums in a fixed
+ * order: bitwise reproducible.  rows in [1, 65536], frames = F in [1, 2^20], width in [2, 128], hop in [1, width], pad finite;
+ * anything else is GLOWK_ERR before anything is launched.  Added to version 480 without a new number: nothing that existed
+ * changed; a library without them lacks the symbols. */
+/* x [nsig][rows][F] -> tiles [nsig][N][rows][width]: a raw gather, `pad` at and beyond F, no floor and no clip (BASIS states
+ * leave [-100, 20]; glowk_tile_cut is the front end's cut, with both).  The first tiles of a noise level.  nsig in [0, 2^20],
+ * nsig == 0 is a successful no-op; the tiles must not overlap x. */
+int glowk_frames_to_tiles(const float* x_dev, int nsig, int rows, int frames, int width, int hop, float pad, float* tiles_dev,
+                          void* stream);
+/* One Langevin step of all nsrc sources on the frames, in place, as ONE kernel:
+ *     x_k <- x_k + eta (s_k + lambda_recon m_k (mixed - mix)) + sqrt(2 eta) N(0, I)              for k = 0 .. nsrc - 1
+ * with mix, m_k and every rounding of glowk_basis_update_n (the device code is shared) and s_k stitched from the gradient tiles
+ * as above.  x_dev: [nsrc][rows][F].  g: HOST array of nsrc DEVICE pointers, each [N][rows][width], the gradient of prior k at
+ * the tiles of x_k (glowk_log_prob_grad's output as it is).  mixed: [rows][F].  eps: NULL, or a HOST array of nsrc entries, each
+ * NULL or [rows][F] standard-normal draws; a source without draws takes the device RNG's, stream k & 1 of pair k >> 1 at
+ * (seed, step): element e = b F + f of the frame layout takes element e of that stream (glowk_random_source at offset 0).
+ * tiles_out (nullable): [nsrc][N][rows][width], receives the tiles of the updated states for the next step's gradient calls --
+ * every cell of it is written, the pad cells with `pad` -- so a step is nsrc gradient evaluations and this launch.
+ * nonfinite_dev as for glowk_basis_update: set to 1 on a non-finite stitched gradient, mixture or result.  nsrc in [2, 16],
+ * step < 2^48, eta >= 0, mixing: enum glowk_mixing; x, mixed, the gradient tiles, the noise and tiles_out must not overlap
+ * (gradient and noise tensors are only read and may repeat).  A thread moves four consecutive elements of the frame layout
+ * (one Philox call per source), as 16-byte accesses of x, mixed and eps when rows F is a multiple of 4 and they are 16-byte
+ * aligned; the tiles are read and written cell by cell, neighbouring threads at neighbouring frames. */
+int glowk_basis_update_frames(float* x_dev, const float* const* g, const float* const* eps, int nsrc, const float* mixed_dev, int rows,
+                              int frames, int width, int hop, int mixing, float eta, float lambda_recon, uint64_t seed, uint64_t step,
+                              float pad, float* tiles_out_dev, int* nonfinite_dev, void* stream);
+
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
  * checkpoint bundles (train_utils.py:62-75), whose tensors are too large for an interpreted byte loop */
