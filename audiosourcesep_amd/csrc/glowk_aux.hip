@@ -17,12 +17,22 @@
 
 using namespace glowk_eng;
 
+namespace glowk_eng {
+// elements [offset, offset + n) of an RNG stream reach past element 2^62: from there hi32(q) of the quad q = e / 4 runs into
+// the bits of the counter word that hold `which`, and the draws would be another stream's
+static bool rng_range_bad(uint64_t offset, size_t n) {
+  const uint64_t lim = (uint64_t)1 << 62;
+  return offset > lim || n > lim - offset;
+}
+}  // namespace glowk_eng
+
 extern "C" {
 
 int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int which, int uniform, uint64_t offset, void* stream) {
   if (!out_dev) return fail("null tensor");
   if (which < 0 || which > 15) return fail("random: stream id must be 0..15");
   if (offset % 4) return fail("random: the stream offset must be a multiple of 4 elements");
+  if (rng_range_bad(offset, n)) return fail("random: the stream ends at element 2^62 (offset + n is beyond it)");
   if (n == 0) return 0;
   DeviceGuard dg(ptr_device(out_dev));
   const size_t threads = (n + 3) / 4;
@@ -39,6 +49,7 @@ int glowk_random_source(float* out_dev, size_t n, uint64_t seed, uint64_t step, 
   if (pair < 0 || pair > 65535) return fail("random_source: the source pair must be 0..65535");
   if (pair && step >= ((uint64_t)1 << 48)) return fail("random_source: step must be below 2^48 (a source pair shares its counter word)");
   if (offset % 4) return fail("random_source: the stream offset must be a multiple of 4 elements");
+  if (rng_range_bad(offset, n)) return fail("random_source: the stream ends at element 2^62 (offset + n is beyond it)");
   if (n == 0) return 0;
   DeviceGuard dg(ptr_device(out_dev));
   const size_t threads = (n + 3) / 4;
@@ -67,6 +78,7 @@ int glowk_basis_update_n(float* const* x, const float* const* g, const float* co
   for (int k = 0; k < nsrc; ++k)
     if (!x[k] || !g[k]) return fail("null tensor");
   if (offset % 4) return fail("basis_update_n: the stream offset must be a multiple of 4 elements");
+  if (rng_range_bad(offset, n)) return fail("basis_update_n: the stream ends at element 2^62 (offset + n is beyond it)");
   if (step >= ((uint64_t)1 << 48)) return fail("basis_update_n: step must be below 2^48 (the source pair shares its counter word)");
   if (n > ((size_t)1 << 40)) return fail("basis_update_n: too many elements");
   if (!(eta >= 0.0f)) return fail("basis_update_n: eta must be non-negative");
@@ -137,6 +149,7 @@ int glowk_add_noise(const float* x_dev, float* out_dev, size_t n, float sigma, u
   if (!x_dev || !out_dev) return fail("null tensor");
   if (which < 0 || which > 15) return fail("add_noise: stream id must be 0..15");
   if (offset % 4) return fail("add_noise: the stream offset must be a multiple of 4 elements");
+  if (rng_range_bad(offset, n)) return fail("add_noise: the stream ends at element 2^62 (offset + n is beyond it)");
   if (n == 0) return 0;
   DeviceGuard dg(ptr_device(out_dev));
   const size_t threads = (n + 3) / 4;

@@ -14,7 +14,9 @@
 #include <type_traits>
 
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> 4 x 32 random bits.  Stateless, so element e of
-// step t of stream w always gets the same draw whatever the grid: counter = (e / 4, t, w, 0), key = seed.
+// step t of stream w always gets the same draw whatever the grid.  The counter and the key as normal4 and k_basis_noise build them
+// (include/glowk.h states the mapping next to glowk_random; tests/rng_ref.py restates it), for quad q = e / 4:
+//   c0 = lo32(q), c1 = hi32(q) ^ (which << 28), c2 = lo32(step), c3 = hi32(step) ^ (pair << 16), key = (lo32(seed), hi32(seed)).
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -38,7 +40,7 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t w
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(c[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);        // (0, 1): 24 bits, never 0
+    const float u1 = ((float)(c[2 * p] >> 8) + 0.5f) * (1.0f / 16777216.0f);        // (0, 1]: 24 bits, never 0; 1 at the largest word (r = 0)
     const float u2 = ((float)(c[2 * p + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float r = sqrtf(-2.0f * logf(u1));
     float sn, cs;
@@ -233,7 +235,8 @@ __global__ __launch_bounds__(256) void k_basis_noise(float* __restrict__ out, si
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32) ^ (which << 28), (uint32_t)step, (uint32_t)(step >> 32) ^ (pair << 16)};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 #pragma unroll
-    for (int j = 0; j < 4; ++j) z[j] = ((float)(c[j] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    for (int j = 0; j < 4; ++j)     // the 25-bit sum rounds to even from 2^23 on, 16777215.5 to 2^24: clamped to the largest float below one
+      z[j] = fminf(((float)(c[j] >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   } else {
     normal4(seed, step, which, q, z, pair);
   }

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 480
+#define GLOWK_VERSION 490
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -312,7 +312,24 @@ int glowk_basis_update_n(float* const* x, const float* const* g, const float* co
 int glowk_basis_mix_n(const float* const* x, int nsrc, float* out_dev, size_t n, int mixing, void* stream);
 /* the device RNG itself: out[e] = the draw glowk_basis_update makes for element e of (seed, step, which); uniform != 0 gives
  * U(0, 1) from the same stream instead of N(0, 1) (the chain's initial state, run_basis_sep.py:360-361); `offset` (a multiple
- * of 4): out[0] is element `offset` of the stream, as for glowk_basis_update */
+ * of 4): out[0] is element `offset` of the stream, as for glowk_basis_update.
+ * The mapping, exactly (tests/rng_ref.py restates it; the U(0, 1) draws are bit for bit a function of it).  Element e of the
+ * stream (seed, step, which, pair) sits in the quad q = (offset + e) / 4 and takes word (offset + e) % 4 of the output of
+ * Philox4x32-10 (Salmon et al., SC'11: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl increments 0x9E3779B9 and 0xBB67AE85, ten
+ * rounds, the key bumped after each round) for
+ *     c0 = lo32(q)
+ *     c1 = hi32(q) ^ (which << 28)
+ *     c2 = lo32(step)
+ *     c3 = hi32(step) ^ (pair << 16)
+ *     key = (lo32(seed), hi32(seed))
+ * with pair = 0 for glowk_random and glowk_add_noise.  A word w becomes u = (top 24 bits of w + 0.5) / 2^24 in float32,
+ * ((float)(w >> 8) + 0.5f) * 2^-24: the sum rounds to even from 2^23 on and to 2^24 at the largest word, so the U(0, 1) draws
+ * are clamped to the largest float below 1 (since version 490; the draw was 1.0 there before) and lie in [2^-25, 1 - 2^-24].
+ * The N(0, 1) draws are Box-Muller on the unclamped u: words (0, 1) of a quad give elements (0, 1) and words (2, 3) elements
+ * (2, 3) as (u1, u2) -> sqrt(-2 ln u1) (cos, sin)(fl32(2 pi) u2) in float32; u1 = 1 gives the pair (0, 0).
+ * Elements at or beyond 2^62 would carry hi32(q) into the bits of `which`: offset + n above 2^62 is GLOWK_ERR, before anything
+ * is launched, here and in glowk_random_source, glowk_add_noise, glowk_basis_update_n and glowk_basis_update (since version
+ * 490). */
 int glowk_random(float* out_dev, size_t n, uint64_t seed, uint64_t step, int which, int uniform, uint64_t offset, void* stream);
 /* the draw source k of glowk_basis_update_n makes: glowk_random with the source pair k >> 1 folded into the counter (XORed as
  * pair << 16 into the word that holds step >> 32) and which = k & 1; pair = 0 is glowk_random itself.  pair in [0, 65535]; a

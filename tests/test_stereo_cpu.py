@@ -59,7 +59,7 @@ def test_mwf_em_is_declared_exported_and_bound(lib, repo_root):
     assert re.search(r"\bint glowk_mwf_em\(const float\* x_dev, float\* v_dev, int nsrc, int nprob, int frames, int n_iter,", text)
     assert "glowk_mwf_em" in _lib.SYMBOLS and lib.glowk_mwf_em is not None
     assert len(_lib.SYMBOLS["glowk_mwf_em"][1]) == 9
-    assert lib.glowk_version() == 480
+    assert lib.glowk_version() >= 480                                           # (the version that introduced it)
 
 
 def test_mwf_em_refuses_bad_ranges_before_touching_a_device(lib):
