@@ -135,6 +135,8 @@ SYMBOLS = {
     "glowk_frames_to_tiles": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
     "glowk_basis_update_frames": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp]),
+    "glowk_median_filter": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_hpss_mask": (_i, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
 }
 
 _lib = None

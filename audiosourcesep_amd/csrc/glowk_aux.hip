@@ -1,7 +1,8 @@
 // glowk handle-free entry points: the BASIS update kernel and mixture, the Philox device RNG, CRC-32C (run_basis_sep.py:131-181, tile_io / tf_checkpoint),
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
 // systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h),
-// whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h)
+// whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h),
+// harmonic / percussive separation by median filtering (glowk_hpss.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -11,6 +12,7 @@
 #include "glowk_stereo.h"
 #include "glowk_longform.h"
 #include "glowk_frames.h"
+#include "glowk_hpss.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -995,6 +997,57 @@ int glowk_basis_update_frames(float* x_dev, const float* const* g, const float* 
 #undef GLOWK_CASE
   }
   LAUNCHCHK("k_basis_update_frames");
+  return 0;
+}
+
+// ---- harmonic / percussive separation by median filtering (glowk_hpss.h) ----------------------------------------------------------
+int glowk_median_filter(const float* s_dev, int nsig, int rows, int frames, int size, int axis, float* out_dev, void* stream) {
+  using namespace glowk_hpss;
+  if (nsig < 0 || nsig > MAX_SIG) return fail("median_filter: nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail("median_filter: rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail("median_filter: frames must be in [1, 2^20]");
+  if ((int64_t)nsig * rows * frames > (int64_t)INT32_MAX) return fail("median_filter: nsig * rows * frames must be at most 2^31 - 1");
+  if (size < 1 || size > MAX_SIZE || size % 2 == 0) return fail("median_filter: size must be odd and in [1, 127]");
+  if (axis != 0 && axis != 1) return fail("median_filter: axis must be 0 (along frames) or 1 (along rows)");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!s_dev || !out_dev) return fail("null tensor");
+  const size_t n = (size_t)nsig * rows * frames;
+  if (floats_overlap(s_dev, n, out_dev, n)) return fail("median_filter: out_dev must not be s_dev (the filter does not run in place)");
+  int dev;
+  if (int rc = audio_device({s_dev, out_dev}, &dev, "median_filter")) return rc;
+  DeviceGuard dg(dev);
+  const int ftiles = (frames + TILE_F - 1) / TILE_F;
+  if (axis == 0) {
+    const int64_t lines = (int64_t)nsig * rows;                  // workgroups: <= lines * ftiles <= nsig * rows * frames < 2^31
+    hipLaunchKernelGGL(k_median_frames, dim3((unsigned)(((lines + LINES - 1) / LINES) * ftiles)), dim3(LINES * 64), 0, (hipStream_t)stream,
+                       s_dev, lines, frames, ftiles, size, out_dev);
+    LAUNCHCHK("k_median_frames");
+  } else {
+    const int rchunks = (rows + ROW_CHUNK - 1) / ROW_CHUNK;
+    const size_t lds = (size_t)(ROW_CHUNK + size - 1) * TILE_F * sizeof(float);   // <= 48 640 bytes
+    hipLaunchKernelGGL(k_median_rows, dim3((unsigned)((int64_t)nsig * rchunks * ftiles)), dim3(ROW_WAVES * 64), lds, (hipStream_t)stream, s_dev, rows,
+                       frames, ftiles, rchunks, size, out_dev);
+    LAUNCHCHK("k_median_rows");
+  }
+  return 0;
+}
+
+int glowk_hpss_mask(const float* harm_dev, const float* perc_dev, const float* s_dev, size_t n, float power, float margin_h,
+                    float margin_p, float* out_h_dev, float* out_p_dev, void* stream) {
+  using namespace glowk_hpss;
+  if (n > ((size_t)1 << 40)) return fail("hpss_mask: n must be at most 2^40");
+  if (!(power > 0.0f)) return fail("hpss_mask: power must be > 0 (+inf: the hard mask)");
+  if (!(margin_h >= 1.0f && margin_h < INFINITY && margin_p >= 1.0f && margin_p < INFINITY))
+    return fail("hpss_mask: both margins must be finite and >= 1");
+  if (n == 0) return 0;                        // empty tensors have no storage: their pointers may be null
+  if (!harm_dev || !perc_dev || !out_h_dev || !out_p_dev) return fail("null tensor");
+  if (floats_overlap(out_h_dev, n, out_p_dev, n)) return fail("hpss_mask: the two outputs must be distinct buffers");
+  int dev;
+  if (int rc = audio_device({harm_dev, perc_dev, s_dev, out_h_dev, out_p_dev}, &dev, "hpss_mask")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_hpss_mask, dim3(stride_grid((int64_t)n)), dim3(256), 0, (hipStream_t)stream, harm_dev, perc_dev, s_dev, n, power,
+                     margin_h, margin_p, out_h_dev, out_p_dev);
+  LAUNCHCHK("k_hpss_mask");
   return 0;
 }
 

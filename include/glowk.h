@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 490
+#define GLOWK_VERSION 500
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -540,6 +540,33 @@ int glowk_frames_to_tiles(const float* x_dev, int nsig, int rows, int frames, in
 int glowk_basis_update_frames(float* x_dev, const float* const* g, const float* const* eps, int nsrc, const float* mixed_dev, int rows,
                               int frames, int width, int hop, int mixing, float eta, float lambda_recon, uint64_t seed, uint64_t step,
                               float pad, float* tiles_out_dev, int* nonfinite_dev, void* stream);
+
+/* --- harmonic / percussive separation by median filtering (Fitzgerald 2010; librosa.decompose.hpss) ------------------------- */
+/* Handle-free, the prior-free baseline: no trained flows, no true sources.  s [nsig][rows][frames] float32, frames contiguous --
+ * |STFT| with rows = 1025 or the 96 mel rows; no geometry is compiled in.  Every tensor is float32 device memory on one device (a
+ * host pointer is refused); each call is one launch on `stream`, with no atomics, no allocation and no host synchronisation:
+ * bitwise reproducible.  Anything outside the stated ranges is GLOWK_ERR with a glowk_last_error message before anything is
+ * launched.  Inputs are finite; what a NaN does is unspecified.  audiosourcesep_amd/hpss.py drives the calls.  Since version 500.
+ */
+/* The running median of odd length `size` along the frame axis (axis = 0: the harmonic filter) or the row axis (axis = 1: the
+ * percussive filter), out [nsig][rows][frames].  Edges as scipy.ndimage.median_filter(mode='reflect'), the half-sample symmetric
+ * extension d c b a | a b c d | d c b a: sample j of an axis of length n (j in [-size / 2, n + size / 2), so j may be negative)
+ * reads index r = j mod 2 n (mathematical mod), then r if r < n, else 2 n - 1 - r; right for windows many times longer than the
+ * axis.  The output is the window element v with #(w < v) <= size / 2 < #(w <= v): a selection by compares, no arithmetic on the
+ * values, so ties, runs of equal values and zeros give the same bits as sorting the window (of elements that compare equal but
+ * differ in bits, -0 and +0, the first in window order).  A (signal, row) or (signal, frame) line depends on nothing outside its
+ * signal: a batch gives what its signals give alone.  nsig in [0, 65535] (0 is a successful no-op), rows in [1, 4096], frames in
+ * [1, 2^20], nsig * rows * frames <= 2^31 - 1, size odd in [1, 127] (1 is the identity), axis in {0, 1}, out_dev != s_dev (the two
+ * must not overlap). */
+int glowk_median_filter(const float* s_dev, int nsig, int rows, int frames, int size, int axis, float* out_dev, void* stream);
+/* The two soft masks of librosa.util.softmask from the two filtered spectra, elementwise over n floats, in fp32.  For (X, R):
+ *   Z = max(X, R), bad = Z < FLT_MIN (1.17549435e-38), Z = 1 where bad; m = (X / Z)^power, r = (R / Z)^power; mask = m / (m + r),
+ *   and where bad mask = 0.5 if both margins are exactly 1 (split_zeros), else 0;  power = +inf: the hard mask X > R (1.0 / 0.0).
+ * out_h uses X = harm, R = perc * margin_h; out_p uses X = perc, R = harm * margin_p.  With a non-null s the outputs are s * mask
+ * instead of the masks (one more fp32 product).  power > 0 (+inf allowed, NaN not), both margins finite and >= 1, n <= 2^40 (0 is
+ * a successful no-op); the two outputs must not overlap each other. */
+int glowk_hpss_mask(const float* harm_dev, const float* perc_dev, const float* s_dev, size_t n, float power, float margin_h,
+                    float margin_p, float* out_h_dev, float* out_p_dev, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
