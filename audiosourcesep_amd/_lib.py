@@ -38,6 +38,12 @@ class GlowkProfile(ctypes.Structure):
     _fields_ = [("net_ms", ctypes.c_double * 4), ("net_launches", ctypes.c_int64 * 4)]
 
 
+class GlowkNetRecord(ctypes.Structure):
+    """``glowk_net_record`` of include/glowk.h: one coupling-network launch of the launch trace."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("level", "dir", "arith", "store", "Q", "family", "passes", "split", "np", "co", "q",
+                                              "fused_px", "presum")]
+
+
 # tensor ids (enum glowk_tensor_id) keyed by the flat parameter names used across the repo
 STEP_TENSOR_IDS = {
     "actnorm/log_scale": 0, "actnorm/shift": 1,
@@ -91,6 +97,8 @@ SYMBOLS = {
     "glowk_kernel_families": (_i, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     "glowk_profile_begin": (_i, [_vp]),
     "glowk_profile_end": (_i, [_vp, ctypes.POINTER(GlowkProfile)]),
+    "glowk_net_trace_begin": (_i, [_vp]),
+    "glowk_net_trace_end": (_i, [_vp, ctypes.POINTER(GlowkNetRecord), _i, ctypes.POINTER(_i)]),
     "glowk_squeeze": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "glowk_unsqueeze": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "glowk_preprocess_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

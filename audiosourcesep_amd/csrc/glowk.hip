@@ -65,6 +65,16 @@ NetLaunch launch_net_raw(int c, int F, const NetArgs& a, NetCall call, hipStream
   return glowk_detail::net_failed("unsupported (channels, n_filters) combination: c=" + std::to_string(c) + " F=" + std::to_string(F));
 }
 
+// One record of the launch trace (glowk_net_trace_begin): the request and what the launch functions report they took (NetLaunch);
+// nothing is derived a second time here.  Called only while the trace is armed.
+static void trace_net(glowk_handle* h, int level, const NetArgs& a, NetCall call, const NetLaunch& r) {
+  glowk_net_record rec;
+  rec.level = level; rec.dir = call.dir; rec.arith = (int)call.arith; rec.store = call.store ? 1 : 0; rec.Q = a.Q;
+  rec.family = r.family; rec.passes = r.passes; rec.split = r.split ? 1 : 0; rec.np = r.np; rec.co = r.co ? 1 : 0; rec.q = r.q ? 1 : 0;
+  rec.fused_px = r.fused_px; rec.presum = r.presum ? 1 : 0;
+  h->net_trace.push_back(rec);
+}
+
 // out: what the launch took (NetLaunch::np partial P buffers, for the consumer).  Counts the launch into glowk_kernel_families; the
 // calls of launch_net_raw alone (the recompute launch of the training sweep, dry queries) are not counted.
 int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipStream_t s, NetCall call, NetLaunch* out = nullptr) {
@@ -81,6 +91,7 @@ int launch_net(glowk_handle* h, int level, int c, int F, const NetArgs& a, hipSt
     ++h->family_launches[r.family];
     if (r.co) ++h->family_launches[FAM_CO];
     if (r.q) ++h->family_launches[FAM_Q];
+    if (h->net_tracing) trace_net(h, level, a, call, r);
   }
   if (h->profiling) {
     HIPCHK(hipEventRecord(h->ev_pool[h->ev_used + 1], s));
@@ -547,7 +558,10 @@ int run_backward(glowk_handle* h, const float* x, const float* z, int N, float* 
         else {
           NetArgs nf = net_args(h, lv, sd, h->saveV + h->offV[sidx], lv.c, lv.c / 2, N);
           nf.P = h->bufP + 2 * h->pstride; nf.st1 = h->trR1; nf.st2 = h->trR1 + (size_t)cfg.F * Q;
-          if (launch_net_raw(lv.c, cfg.F, nf, net_call(h, NET_FWD, true), s).failed) return 1;   // (exact fp32: a split sweep keeps its hiddens)
+          const NetCall rcall = net_call(h, NET_FWD, true);
+          const NetLaunch rr = launch_net_raw(lv.c, cfg.F, nf, rcall, s);   // (exact fp32: a split sweep keeps its hiddens)
+          if (rr.failed) return 1;
+          if (h->net_tracing) trace_net(h, lvl, nf, rcall, rr);
         }
         if (int rc = train_network_grads(h, tc, lvl, k, 1, h->saveV + h->offV[sidx], 0, go_k, 0, R1, 0, h->trM1, h->trM2, 0, N, s, bfac)) return rc;
       }
@@ -1196,6 +1210,24 @@ int glowk_profile_end(glowk_handle* h, glowk_profile* out) {
   }
   h->ev_used = 0;
   h->ev_level.clear();
+  return 0;
+}
+
+int glowk_net_trace_begin(glowk_handle* h) {
+  if (!h) return fail("null handle");
+  h->net_trace.clear();
+  h->net_tracing = true;
+  return 0;
+}
+
+int glowk_net_trace_end(glowk_handle* h, glowk_net_record* out, int cap, int* count) {
+  if (!h || !count || cap < 0 || (cap > 0 && !out)) return fail("bad argument");
+  h->net_tracing = false;
+  const size_t n = h->net_trace.size();
+  if (n > (size_t)INT32_MAX) return fail("more launches traced than the count can hold");
+  for (size_t i = 0; i < n && i < (size_t)cap; ++i) out[i] = h->net_trace[i];
+  *count = (int)n;
+  if (n <= (size_t)cap) std::vector<glowk_net_record>().swap(h->net_trace);   // (a caller whose buffer was too small asks again)
   return 0;
 }
 

@@ -186,6 +186,9 @@ struct glowk_handle {
   std::vector<OwnedEvent> ev_pool;
   size_t ev_used = 0;
   std::vector<int> ev_level;   // level of each (start, stop) pair
+  // launch trace of the coupling-network kernels (glowk_net_trace_begin .. end): what every launch took, in launch order
+  bool net_tracing = false;
+  std::vector<glowk_net_record> net_trace;
 };
 
 #define CDISPATCH(c, CALL)                                                                     \

@@ -36,6 +36,8 @@ struct NetLaunch {
   bool failed = false;      // launch_fail() has set glowk_last_error()
   bool presum = false;      // P was written with conv3's horizontal taps already added: [3 c][Q] per partial (NetArgs::pw; the forward
                             // launches of the 16x16x32 families at c = 8, 16) -- the coupling kernel is told (CoupleArgs::presum)
+  int passes = 0;           // passes over the hidden width of the instance that ran: 2 or 4; 0: the exact kernel (one sweep, no passes)
+  bool split = false;       // ... each pass as workgroups of its own (grid.y = passes) rather than all in one workgroup
   explicit operator bool() const { return np > 0 || fused_px > 0; }   // a form was taken
 };
 
@@ -83,6 +85,8 @@ NetLaunch launch_f32(const NetArgs& a, hipStream_t s, bool dry) {
 // workgroups per wgs still fit the CUs in one round the passes become workgroups of their own (split): 1/NP of the latency per launch.
 // np = NP partial P buffers; 0: no instance fits.
 struct Passes { int np; bool split; };
+// r, with the passes of the instance that ran and whether they were workgroups of their own (what the launch trace reports)
+inline NetLaunch took(NetLaunch r, int passes, bool split) { r.passes = passes; r.split = split; return r; }
 inline Passes pick_passes(bool fits4, bool fits2, int wgs, int max_np) {
   const int cus = num_cus();
   if (fits4 && max_np >= 4 && (4 * wgs <= cus || !fits2)) return {4, 4 * wgs <= cus};
@@ -104,13 +108,13 @@ NetLaunch launch_h3(const NetArgs& a, hipStream_t s, bool dry) {
   if constexpr (F4) {
     if (p.np == 4) {
       if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3, MODE, 4, p.split);
-      return {4, FAM_H3};
+      return took({4, FAM_H3}, 4, p.split);
     }
   }
   if constexpr (F2) {
     if (p.np == 2) {
       if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3, MODE, 2, p.split);
-      return {2, FAM_H3};
+      return took({2, FAM_H3}, 2, p.split);
     }
   }
   return {};
@@ -137,7 +141,7 @@ NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
   if constexpr (F4) {
     if (p.np == 4) {
       if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE, 4, p.split);
-      return {4, FAM_H3S};
+      return took({4, FAM_H3S}, 4, p.split);
     }
   }
   if constexpr (F2) {
@@ -160,34 +164,34 @@ NetLaunch launch_h3s(const NetArgs& a, hipStream_t s, bool dry) {
           if constexpr (RingC<KIN, MOUT, NF, MODE | NET_FUSE>::DB) {
             if (a.fuse && env().co_ring3 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false, true>)) {
               if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false, true>), dim3(wgc), dim3(256), 0, s, a);
-              return {0, FAM_FUSED, true, false, CO_PX};
+              return took({0, FAM_FUSED, true, false, CO_PX}, 2, false);
             }
           }
           if (a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>)) {
             if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE | NET_FUSE, false>), dim3(wgc), dim3(256), 0, s, a);
-            return {0, FAM_FUSED, true, false, CO_PX};
+            return took({0, FAM_FUSED, true, false, CO_PX}, 2, false);
           }
         }
         if (!a.fuse && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, false>)) {
           if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, false>), dim3(wgc), dim3(256), 0, s, a);
-          return {RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2, FAM_H3S, true};
+          return took({RingC<KIN, MOUT, NF, MODE>::MERGE ? 1 : 2, FAM_H3S, true}, 2, false);
         }
       }
       if (co_ok && p.split && wgc <= cus && a.max_np >= 2 && co_two_per_cu(k_net_h3c<KIN, MOUT, NF, MODE, true>)) {
         if (!dry) hipLaunchKernelGGL((k_net_h3c<KIN, MOUT, NF, MODE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
-        return {2, FAM_H3S, true};
+        return took({2, FAM_H3S, true}, 2, true);
       }
     }
     if constexpr ((MODE == NET_FWD || MODE == NET_FWD2 || MODE == NET_FWD_SAVE) && MOUT == 36) {
       if constexpr (RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::FITS && RingS<KIN, MOUT, NF, MODE | NET_FUSE, 2>::MERGE) {
         if (a.fuse && !p.split) {
           if (!dry) hipLaunchKernelGGL((k_net_h3s<KIN, MOUT, NF, MODE | NET_FUSE, 2, false>), dim3(wgs), dim3(512), 0, s, a);
-          return {0, FAM_FUSED, false, false, 256};
+          return took({0, FAM_FUSED, false, false, 256}, 2, false);
         }
       }
     }
     if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE, 2, p.split);
-    return {(!p.split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2, FAM_H3S};   // (merged: the two passes' sums leave the kernel as one buffer)
+    return took({(!p.split && RingS<KIN, MOUT, NF, MODE, 2>::MERGE) ? 1 : 2, FAM_H3S}, 2, p.split);   // (merged: the two passes' sums leave the kernel as one buffer)
   }
   return {};
 }
@@ -208,11 +212,11 @@ NetLaunch launch_h3s_half(const NetArgs& a, hipStream_t s, bool dry) {
     if constexpr (RingQ<KIN, MOUT, NF, MODE>::FITS) {
       if (p.split && !env().q_off) {
         if (!dry) hipLaunchKernelGGL((k_net_h3q<KIN, MOUT, NF, MODE>), dim3(wgs, 4), dim3(512), 0, s, a);
-        return {4, FAM_H3S_HALF, false, true};
+        return took({4, FAM_H3S_HALF, false, true}, 4, true);
       }
     }
     if (!dry) GLOWK_LAUNCH_PASSES(k_net_h3s, MODE | NET_HALF, 4, p.split);
-    return {4, FAM_H3S_HALF};
+    return took({4, FAM_H3S_HALF}, 4, p.split);
   }
   return {};
 }
@@ -289,11 +293,11 @@ NetLaunch launch_co_train(const NetArgs& a, hipStream_t s, bool dry) {
     if (wgc > cus) {
       if (!(co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, FS, false>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, BS, false>))) return {};
       if (!dry) hipLaunchKernelGGL((k_net_h3c<Sh::KIN, Sh::MOUT, NF, DIR | NET_STORE, false>), dim3(wgc), dim3(256), 0, s, a);
-      return {1, FAM_H3S, true};
+      return took({1, FAM_H3S, true}, 2, false);
     }
     if (!(co_two_per_cu(k_net_h3c<CI, 18 * CI, NF, FS, true>) && co_two_per_cu(k_net_h3c<2 * CI, 9 * CI, NF, BS, true>))) return {};
     if (!dry) hipLaunchKernelGGL((k_net_h3c<Sh::KIN, Sh::MOUT, NF, DIR | NET_STORE, true>), dim3(wgc, 2), dim3(256), 0, s, a);
-    return {2, FAM_H3S, true};
+    return took({2, FAM_H3S, true}, 2, true);
   }
   return {};
 }

@@ -4,6 +4,7 @@ PyTorch-ROCm is used for storage and streams only: tensors are ``torch.cuda`` fl
 ``data_ptr()`` is handed to the C ABI together with the current HIP stream; all arithmetic happens in
 ``libglowk.so``.  No CPU fallback: construction raises if the library is missing or no GPU is present.
 """
+import contextlib
 import ctypes
 import os
 import warnings
@@ -249,6 +250,27 @@ class GlowEngine:
         p = _lib.GlowkProfile()
         _lib.check(self.lib.glowk_profile_end(self.h, ctypes.byref(p)))
         return [(p.net_ms[i], int(p.net_launches[i])) for i in range(self.cfg.L)]
+
+    @contextlib.contextmanager
+    def net_trace(self):
+        """``with eng.net_trace() as records:`` -- the coupling-network launches of the calls inside the block, in launch order
+        (``glowk_net_trace_begin`` / ``glowk_net_trace_end``): ``records`` is a list that is filled when the block ends, one dict per
+        launch with the fields of ``glowk_net_record`` (include/glowk.h).  Host-side bookkeeping only; the results of the calls
+        are what they are without it."""
+        records = []
+        _lib.check(self.lib.glowk_net_trace_begin(self.h))
+        try:
+            yield records
+        finally:
+            count, cap = ctypes.c_int(0), 256
+            buf = (_lib.GlowkNetRecord * cap)()
+            _lib.check(self.lib.glowk_net_trace_end(self.h, buf, cap, ctypes.byref(count)))
+            if count.value > cap:       # (kept by the engine until a call with room for them)
+                cap = count.value
+                buf = (_lib.GlowkNetRecord * cap)()
+                _lib.check(self.lib.glowk_net_trace_end(self.h, buf, cap, ctypes.byref(count)))
+            names = [f[0] for f in _lib.GlowkNetRecord._fields_]
+            records.extend({n: int(getattr(buf[i], n)) for n in names} for i in range(count.value))
 
     # ---- helpers ----------------------------------------------------------------------------------
     def _in(self, x, shape_tail):

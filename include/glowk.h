@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 500
+#define GLOWK_VERSION 510
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -221,6 +221,35 @@ int64_t glowk_fused_steps(const glowk_handle* h);
  * in a split arithmetic whose out7[0] stays put ran no level on the exact kernels. */
 int glowk_kernel_families(const glowk_handle* h, int64_t* out7);
 int glowk_profile_end(glowk_handle* h, glowk_profile* out);
+/* Launch trace of the coupling-network kernels (since version 510; no reference counterpart).  Which of the ~100 kernel instances a
+ * launch takes is decided at run time from the level shape, the direction and arithmetic, the pixel count against the device's
+ * compute units and the host's flags; the seven counters above cannot tell two or four passes, passes as workgroups of their own
+ * or not, merged or pre-summed outputs apart.  Between glowk_net_trace_begin and glowk_net_trace_end the handle keeps one record
+ * per coupling-network launch of its compute calls, in launch order -- the recompute launch of a training sweep that does not keep
+ * its hiddens included, dry queries of the policy not.  Every field but the request is what the launch function itself reports it
+ * took.  Host memory only: no device call, no synchronisation, the kernels and their arguments are untouched; off by default, and an
+ * unarmed handle pays one untaken branch per launch. */
+typedef struct glowk_net_record {
+  int32_t level;      /* block of the flow, from 0 */
+  int32_t dir;        /* the request: 0 plain forward network, 1 the gradient path's saving forward network, 2 backward network */
+  int32_t arith;      /* ... 0 exact fp32, 1 the three-term fp16 split, 2 the two-term split */
+  int32_t store;      /* ... 1: a training launch that also stores its hidden tensors */
+  int32_t Q;          /* pixels of the launch: N * h * w of the level */
+  int32_t family;     /* index into glowk_kernel_families' out7: 0 k_net_f32, 1 k_net_h3, 2 k_net_h3s, 3 its half-wave form, 4 fused */
+  int32_t passes;     /* passes over the hidden width of the instance: 2 or 4; 0 for the exact kernel */
+  int32_t split;      /* 1: every pass ran as workgroups of its own (grid.y = passes), 0: all passes in one workgroup */
+  int32_t np;         /* partial output buffers written (1: the passes' sums were merged in the kernel; 0: the coupling was fused) */
+  int32_t co;         /* 1: the co-resident form (k_net_h3c) */
+  int32_t q;          /* 1: the small-grid form with all conv1 blocks first (k_net_h3q) */
+  int32_t fused_px;   /* > 0: the coupling ran inside the kernel, in workgroups of this many pixels */
+  int32_t presum;     /* 1: conv3's horizontal taps were added in registers */
+} glowk_net_record;
+/* arms the trace and drops what an earlier one left */
+int glowk_net_trace_begin(glowk_handle* h);
+/* disarms it; *count = the number of launches since glowk_net_trace_begin, whatever cap is; out[0 .. min(cap, *count)) receive the
+ * first records (out may be NULL when cap is 0).  When *count <= cap the records are dropped; otherwise they are kept until a
+ * second call with room for them (or the next glowk_net_trace_begin). */
+int glowk_net_trace_end(glowk_handle* h, glowk_net_record* out, int cap, int* count);
 
 /* --- sub-bijectors, as exercised one by one by unittest_flow_models.py:124-186 --------------------- */
 /* Squeeze._forward / _inverse (flow_tfp_bijectors.py:170-180); no handle needed */

@@ -48,6 +48,27 @@ def test_config_struct_matches_header(repo_root):
     assert ctypes.sizeof(_lib.GlowkConfigStruct) == 12 * 4
 
 
+def test_net_record_struct_matches_header_and_an_idle_trace_is_empty(lib, repo_root):
+    text = open(os.path.join(repo_root, "include", "glowk.h")).read()
+    body = re.search(r"typedef struct glowk_net_record \{(.*?)\} glowk_net_record;", text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = [d.split() for d in body.split(";") if d.strip()]
+    assert all(d[0] == "int32_t" and len(d) == 2 for d in decls)
+    assert [d[1] for d in decls] == [f[0] for f in _lib.GlowkNetRecord._fields_]
+    assert ctypes.sizeof(_lib.GlowkNetRecord) == 4 * len(decls)
+    # host-only: arming, reading and disarming a handle that launched nothing; bad arguments are refused
+    rc, h = _create(lib, BASE)
+    assert rc == 0
+    count, buf = ctypes.c_int(-1), (_lib.GlowkNetRecord * 2)()
+    assert lib.glowk_net_trace_end(h, buf, 2, ctypes.byref(count)) == 0 and count.value == 0      # never armed: nothing recorded
+    assert lib.glowk_net_trace_begin(h) == 0
+    assert lib.glowk_net_trace_end(h, None, 0, ctypes.byref(count)) == 0 and count.value == 0
+    assert lib.glowk_net_trace_end(h, None, 2, ctypes.byref(count)) != 0
+    assert lib.glowk_net_trace_end(h, buf, 2, None) != 0
+    assert lib.glowk_net_trace_begin(None) != 0
+    assert lib.glowk_destroy(h) == 0
+
+
 def test_tensor_ids_match_header(repo_root):
     text = open(os.path.join(repo_root, "include", "glowk.h")).read()
     enum = dict((k, int(v)) for k, v in re.findall(r"(GLOWK_[A-Z0-9_]+) = (\d+)", text))
