@@ -145,6 +145,9 @@ SYMBOLS = {
                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, _vp, _vp, _vp]),
     "glowk_median_filter": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "glowk_hpss_mask": (_i, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
+    "glowk_nn_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "glowk_nn_neighbors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nn_median": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

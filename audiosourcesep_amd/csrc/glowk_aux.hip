@@ -2,7 +2,7 @@
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
 // systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h),
 // whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h),
-// harmonic / percussive separation by median filtering (glowk_hpss.h)
+// harmonic / percussive separation by median filtering (glowk_hpss.h), REPET-SIM's nearest-neighbour filter (glowk_repet.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -13,6 +13,7 @@
 #include "glowk_longform.h"
 #include "glowk_frames.h"
 #include "glowk_hpss.h"
+#include "glowk_repet.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1048,6 +1049,97 @@ int glowk_hpss_mask(const float* harm_dev, const float* perc_dev, const float* s
   hipLaunchKernelGGL(k_hpss_mask, dim3(stride_grid((int64_t)n)), dim3(256), 0, (hipStream_t)stream, harm_dev, perc_dev, s_dev, n, power,
                      margin_h, margin_p, out_h_dev, out_p_dev);
   LAUNCHCHK("k_hpss_mask");
+  return 0;
+}
+
+
+// ---- REPET-SIM: nearest-neighbour median filtering (glowk_repet.h) ------------------------------------------------------------------
+namespace {
+// the ranges the three entries share; 0 or an error
+int nn_ranges(const char* what, int nsig, int rows, int frames, int k) {
+  using namespace glowk_repet;
+  const std::string w(what);
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (k < 1 || k > MAX_K) return fail(w + ": k must be in [1, 512]");
+  if ((int64_t)nsig * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * rows * frames must be at most 2^31 - 1");
+  if ((int64_t)nsig * frames * k > (int64_t)INT32_MAX) return fail(w + ": nsig * frames * k must be at most 2^31 - 1");
+  return 0;
+}
+// the workspace: the norms [nsig][frames], then the frame-major copy [nsig][frames][rows]
+size_t nn_work_floats(int nsig, int rows, int frames) { return (size_t)nsig * frames * ((size_t)rows + 1); }
+bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p < q + nb && q < p + na;
+}
+}  // namespace
+
+size_t glowk_nn_workspace_bytes(int nsig, int rows, int frames, int k) {
+  if (nn_ranges("nn_workspace_bytes", nsig, rows, frames, k)) return 0;
+  return nn_work_floats(nsig, rows, frames) * sizeof(float);
+}
+
+int glowk_nn_neighbors(const float* s_dev, int nsig, int rows, int frames, int k, int width, int32_t* idx_dev, float* sim_dev,
+                       void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_repet;
+  if (int rc = nn_ranges("nn_neighbors", nsig, rows, frames, k)) return rc;
+  if (width < 1 || width > MAX_WIDTH) return fail("nn_neighbors: width must be in [1, 2^20]");
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!s_dev || !idx_dev || !work_dev) return fail("null tensor");
+  const size_t need = nn_work_floats(nsig, rows, frames) * sizeof(float);
+  if (work_bytes < need) return fail("nn_neighbors: work_bytes is smaller than glowk_nn_workspace_bytes says");
+  const size_t n = (size_t)nsig * rows * frames * 4, nk = (size_t)nsig * frames * k * 4;
+  if (bytes_overlap(s_dev, n, idx_dev, nk) || (sim_dev && bytes_overlap(s_dev, n, sim_dev, nk)) || (sim_dev && bytes_overlap(idx_dev, nk, sim_dev, nk)))
+    return fail("nn_neighbors: s_dev, idx_dev and sim_dev must not overlap");
+  if (bytes_overlap(work_dev, need, s_dev, n) || bytes_overlap(work_dev, need, idx_dev, nk) || (sim_dev && bytes_overlap(work_dev, need, sim_dev, nk)))
+    return fail("nn_neighbors: work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({s_dev, idx_dev, sim_dev, work_dev}, &dev, "nn_neighbors")) return rc;
+  DeviceGuard dg(dev);
+  float* norm = (float*)work_dev;
+  const int64_t total = (int64_t)nsig * frames;
+  hipLaunchKernelGGL(k_nn_norms, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s_dev, total, rows, frames, norm);
+  LAUNCHCHK("k_nn_norms");
+  const int qtiles = (frames + QT - 1) / QT;
+  const dim3 grid((unsigned)((int64_t)nsig * qtiles));        // <= 65535 * 1024
+  if (k <= K_SMALL)
+    hipLaunchKernelGGL((k_nn_topk<K_SMALL, 2>), grid, dim3(256), 0, (hipStream_t)stream, s_dev, (const float*)norm, rows, frames, k, width, qtiles,
+                       idx_dev, sim_dev);
+  else
+    hipLaunchKernelGGL((k_nn_topk<MAX_K, 1>), grid, dim3(256), 0, (hipStream_t)stream, s_dev, (const float*)norm, rows, frames, k, width, qtiles,
+                       idx_dev, sim_dev);
+  LAUNCHCHK("k_nn_topk");
+  return 0;
+}
+
+int glowk_nn_median(const float* s_dev, const int32_t* idx_dev, int nsig, int rows, int frames, int k, float* out_dev, void* work_dev,
+                    size_t work_bytes, void* stream) {
+  using namespace glowk_repet;
+  if (int rc = nn_ranges("nn_median", nsig, rows, frames, k)) return rc;
+  if (nsig == 0) return 0;
+  if (!s_dev || !idx_dev || !out_dev || !work_dev) return fail("null tensor");
+  const size_t need = nn_work_floats(nsig, rows, frames) * sizeof(float);
+  if (work_bytes < need) return fail("nn_median: work_bytes is smaller than glowk_nn_workspace_bytes says");
+  const size_t n = (size_t)nsig * rows * frames * 4, nk = (size_t)nsig * frames * k * 4;
+  if (bytes_overlap(s_dev, n, out_dev, n)) return fail("nn_median: out_dev must not be s_dev (the filter does not run in place)");
+  if (bytes_overlap(idx_dev, nk, out_dev, n)) return fail("nn_median: out_dev must not overlap idx_dev");
+  if (bytes_overlap(work_dev, need, s_dev, n) || bytes_overlap(work_dev, need, idx_dev, nk) || bytes_overlap(work_dev, need, out_dev, n))
+    return fail("nn_median: work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({s_dev, idx_dev, out_dev, work_dev}, &dev, "nn_median")) return rc;
+  DeviceGuard dg(dev);
+  float* st = (float*)work_dev + (size_t)nsig * frames;
+  const int rtiles = (rows + 31) / 32, ftiles = (frames + 31) / 32;    // workgroups: <= nsig * rows * frames < 2^31 in both launches
+  hipLaunchKernelGGL(k_nn_transpose, dim3((unsigned)((int64_t)nsig * rtiles * ftiles)), dim3(256), 0, (hipStream_t)stream, s_dev, rows, frames,
+                     rtiles, ftiles, st);
+  LAUNCHCHK("k_nn_transpose");
+  const int ll = k <= 192 ? 0 : k <= 384 ? 1 : 2;                // lanes per output 1 << ll: (k + 1) * (64 >> ll) floats of LDS stay within 49 KiB
+  const int no = 64 >> ll, rchunks = (rows + no - 1) / no;
+  const size_t lds = ((size_t)k + 1) * no * sizeof(float);       // a spare slot for the entries that are not neighbours
+  hipLaunchKernelGGL(k_nn_median, dim3((unsigned)((int64_t)nsig * rchunks * frames)), dim3(64), lds, (hipStream_t)stream, s_dev, (const float*)st,
+                     idx_dev, rows, frames, k, rchunks, ll, out_dev);
+  LAUNCHCHK("k_nn_median");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 510
+#define GLOWK_VERSION 520
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -596,6 +596,37 @@ int glowk_median_filter(const float* s_dev, int nsig, int rows, int frames, int 
  * a successful no-op); the two outputs must not overlap each other. */
 int glowk_hpss_mask(const float* harm_dev, const float* perc_dev, const float* s_dev, size_t n, float power, float margin_h,
                     float margin_p, float* out_h_dev, float* out_p_dev, void* stream);
+
+/* --- REPET-SIM: nearest-neighbour median filtering (Rafii & Pardo 2012; librosa.decompose.nn_filter) ------------------------- */
+/* Handle-free, the prior-free baseline for a foreground over a repeating accompaniment: every frame is replaced by the per-row
+ * median of its most similar frames elsewhere in the signal; what repeats survives.  s [nsig][rows][frames] float32, frames
+ * contiguous, real and non-negative.  Every tensor is device memory on one device (a host pointer is refused); the calls launch on
+ * `stream` with no atomics, no allocation and no host synchronisation, the number of launches depends on the shapes alone, and
+ * the results are bitwise reproducible; a batch gives what its signals give alone.  Anything outside the stated ranges is
+ * GLOWK_ERR with a glowk_last_error message before anything is launched.  Inputs are finite.  Ranges of all three: nsig in
+ * [0, 65535] (0 is a successful no-op of valid arguments), rows in [1, 4096], frames in [1, 32768], k in [1, 512], nsig * rows *
+ * frames and nsig * frames * k at most 2^31 - 1.  audiosourcesep_amd/repet.py drives the calls; the two masks of REPET-SIM are
+ * glowk_hpss_mask(harm = min(s, filt), perc = s - min(s, filt)).  Since version 520. */
+/* The bytes of work_dev that glowk_nn_neighbors and glowk_nn_median need for these shapes: the frame norms and a frame-major copy
+ * of s, 4 nsig frames (rows + 1) -- linear in frames; there is no frames x frames matrix anywhere.  0 for arguments out of range. */
+size_t glowk_nn_workspace_bytes(int nsig, int rows, int frames, int k);
+/* The neighbours of every frame.  sim(i, j) = <s[:, i], s[:, j]> / max(|s[:, i]| |s[:, j]|, FLT_MIN), so a silent frame has
+ * similarity 0 to everything; the dot product is an fp32 fma chain over the rows in row order on the fp32 matrix cores, the same
+ * bits for (i, j) and (j, i).  The candidates of frame i are the frames j with |i - j| >= width; with k_i = min(k, #candidates),
+ * idx[i][:k_i] holds the k_i candidates of largest similarity in decreasing similarity, equal similarities to the lower index,
+ * and idx[i][k_i:] = -1 (librosa's recurrence_matrix rule: the k + 2 width nearest, the band removed, the top k kept).  sim_dev
+ * (nullable) receives the similarities, 0 where idx is -1.  width in [1, 2^20]; work_bytes at least glowk_nn_workspace_bytes;
+ * s, idx, sim and work must not overlap.  Two launches. */
+int glowk_nn_neighbors(const float* s_dev, int nsig, int rows, int frames, int k, int width,
+                       int32_t* idx_dev /* [nsig][frames][k] */, float* sim_dev /* same shape, may be null; 0 where idx is -1 */,
+                       void* work_dev, size_t work_bytes, void* stream);
+/* The filter: out[r][i] = the median over the neighbours j = idx[i][t] of s[r][j], gathered from a frame-major copy of s in
+ * work_dev.  The neighbours of a frame are its entries in [0, frames); any other entry (-1, or a caller's error) is skipped and
+ * never read through.  With n of them: n odd, the middle element -- a selection by compares, the bits a sort gives; n even,
+ * (a + b) * 0.5f of the two middle elements in fp32, the only arithmetic on the values; n = 0, out[r][i] = s[r][i].  out_dev must
+ * not overlap s_dev; work_bytes at least glowk_nn_workspace_bytes.  Two launches. */
+int glowk_nn_median(const float* s_dev, const int32_t* idx_dev, int nsig, int rows, int frames, int k,
+                    float* out_dev /* [nsig][rows][frames], not s_dev */, void* work_dev, size_t work_bytes, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
