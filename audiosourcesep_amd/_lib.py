@@ -148,6 +148,10 @@ SYMBOLS = {
     "glowk_nn_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "glowk_nn_neighbors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_nn_median": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_beat_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "glowk_beat_spectrum": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_beat_period": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_period_neighbors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

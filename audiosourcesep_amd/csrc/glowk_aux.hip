@@ -2,7 +2,8 @@
 // the audio front end and mel inversion (glowk_audio.h), the BSS Eval v4 metrics (glowk_bsseval.h), the oracle separation
 // systems (glowk_oracle.h), the sample-rate converter (glowk_resample.h), the stereo EM Wiener filter (glowk_stereo.h),
 // whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h),
-// harmonic / percussive separation by median filtering (glowk_hpss.h), REPET-SIM's nearest-neighbour filter (glowk_repet.h)
+// harmonic / percussive separation by median filtering (glowk_hpss.h), REPET-SIM's nearest-neighbour filter (glowk_repet.h),
+// REPET's beat spectrum, period and periodic neighbours (glowk_beat.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -14,6 +15,7 @@
 #include "glowk_frames.h"
 #include "glowk_hpss.h"
 #include "glowk_repet.h"
+#include "glowk_beat.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1140,6 +1142,101 @@ int glowk_nn_median(const float* s_dev, const int32_t* idx_dev, int nsig, int ro
   hipLaunchKernelGGL(k_nn_median, dim3((unsigned)((int64_t)nsig * rchunks * frames)), dim3(64), lds, (hipStream_t)stream, s_dev, (const float*)st,
                      idx_dev, rows, frames, k, rchunks, ll, out_dev);
   LAUNCHCHK("k_nn_median");
+  return 0;
+}
+
+// ---- REPET and adaptive REPET: beat spectrum, period, periodic neighbours (glowk_beat.h) --------------------------------------------
+namespace {
+// the ranges glowk_beat_workspace_bytes and glowk_beat_spectrum share; 0 or an error
+int beat_ranges(const char* what, int nsig, int rows, int frames, int nlags, int win, int step) {
+  using namespace glowk_beat;
+  const std::string w(what);
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (nlags < 1 || nlags > frames) return fail(w + ": nlags must be in [1, frames]");
+  if (win != 0 && (win < 2 || win > frames)) return fail(w + ": win must be 0 (one window, the whole signal) or in [2, frames]");
+  if (win != 0 && (step < 1 || step > win)) return fail(w + ": step must be in [1, win]");
+  if ((int64_t)nsig * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * rows * frames must be at most 2^31 - 1");
+  const BeatPlan p = beat_plan(frames, nlags, win, step);
+  if ((int64_t)nsig * p.nwin * nlags > (int64_t)INT32_MAX) return fail(w + ": nsig * nwin * nlags must be at most 2^31 - 1");
+  if ((int64_t)nsig * p.nwin * p.nu * p.nch > (int64_t)INT32_MAX) return fail(w + ": nsig * nwin * nu * nch (the workgroups) must be at most 2^31 - 1");
+  return 0;
+}
+size_t beat_work_bytes(int nsig, const glowk_beat::BeatPlan& p) {
+  return (size_t)nsig * p.nwin * p.nu * p.nch * glowk_beat::NLP * sizeof(double);
+}
+}  // namespace
+
+size_t glowk_beat_workspace_bytes(int nsig, int rows, int frames, int nlags, int win, int step) {
+  if (beat_ranges("beat_workspace_bytes", nsig, rows, frames, nlags, win, step)) return 0;
+  return beat_work_bytes(nsig, glowk_beat::beat_plan(frames, nlags, win, step));
+}
+
+int glowk_beat_spectrum(const float* s_dev, int nsig, int rows, int frames, int nlags, int win, int step, float* beat_dev, void* work_dev,
+                        size_t work_bytes, void* stream) {
+  using namespace glowk_beat;
+  if (int rc = beat_ranges("beat_spectrum", nsig, rows, frames, nlags, win, step)) return rc;
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!s_dev || !beat_dev || !work_dev) return fail("null tensor");
+  const BeatPlan p = beat_plan(frames, nlags, win, step);
+  const size_t need = beat_work_bytes(nsig, p);
+  if (work_bytes < need) return fail("beat_spectrum: work_bytes is smaller than glowk_beat_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8) return fail("beat_spectrum: work_dev must be aligned to 8 bytes");
+  const size_t n = (size_t)nsig * rows * frames * 4, nb = (size_t)nsig * p.nwin * nlags * 4;
+  if (bytes_overlap(s_dev, n, beat_dev, nb)) return fail("beat_spectrum: s_dev and beat_dev must not overlap");
+  if (bytes_overlap(work_dev, need, s_dev, n) || bytes_overlap(work_dev, need, beat_dev, nb))
+    return fail("beat_spectrum: work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({s_dev, beat_dev, work_dev}, &dev, "beat_spectrum")) return rc;
+  DeviceGuard dg(dev);
+  double* part = (double*)work_dev;
+  hipLaunchKernelGGL(k_beat_gram, dim3((unsigned)((int64_t)nsig * p.nwin * p.nu * p.nch)), dim3(256), 0, (hipStream_t)stream, s_dev, rows, frames, win,
+                     step, p.nwin, p.nu, p.nch, p.tpw, nlags, part);
+  LAUNCHCHK("k_beat_gram");
+  const int64_t total = (int64_t)nsig * p.nwin * nlags;
+  hipLaunchKernelGGL(k_beat_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const double*)part, total, rows, frames,
+                     win, step, p.nwin, p.nu, p.nch, nlags, beat_dev);
+  LAUNCHCHK("k_beat_reduce");
+  return 0;
+}
+
+int glowk_beat_period(const float* beat_dev, int nseg, int nlags, int pmin, int pmax, int32_t* period_dev, void* stream) {
+  using namespace glowk_beat;
+  if (nseg < 0) return fail("beat_period: nseg must be in [0, 2^31 - 1]");
+  if (nlags < 2 || nlags > MAX_FRAMES) return fail("beat_period: nlags must be in [2, 32768]");
+  if (pmin < 1 || pmin > pmax || pmax > nlags - 1) return fail("beat_period: 1 <= pmin <= pmax <= nlags - 1 is required");
+  if ((int64_t)nseg * nlags > (int64_t)INT32_MAX) return fail("beat_period: nseg * nlags must be at most 2^31 - 1");
+  if (nseg == 0) return 0;
+  if (!beat_dev || !period_dev) return fail("null tensor");
+  if (bytes_overlap(beat_dev, (size_t)nseg * nlags * 4, period_dev, (size_t)nseg * 4)) return fail("beat_period: beat_dev and period_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({beat_dev, period_dev}, &dev, "beat_period")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_beat_period, dim3((unsigned)nseg), dim3(64), 0, (hipStream_t)stream, beat_dev, nlags, pmin, pmax, period_dev);
+  LAUNCHCHK("k_beat_period");
+  return 0;
+}
+
+int glowk_period_neighbors(const int32_t* period_dev, int nsig, int frames, int nper, int step, int k, int32_t* idx_dev, void* stream) {
+  using namespace glowk_beat;
+  if (nsig < 0 || nsig > MAX_SIG) return fail("period_neighbors: nsig must be in [0, 65535]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail("period_neighbors: frames must be in [1, 32768]");
+  if (nper < 1 || nper > MAX_FRAMES) return fail("period_neighbors: nper must be in [1, 32768]");
+  if (step < 1 || step > MAX_FRAMES) return fail("period_neighbors: step must be in [1, 32768]");
+  if (k < 1 || k > MAX_K) return fail("period_neighbors: k must be in [1, 512]");
+  if ((int64_t)nsig * frames * k > (int64_t)INT32_MAX) return fail("period_neighbors: nsig * frames * k must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!period_dev || !idx_dev) return fail("null tensor");
+  if (bytes_overlap(period_dev, (size_t)nsig * nper * 4, idx_dev, (size_t)nsig * frames * k * 4))
+    return fail("period_neighbors: period_dev and idx_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({period_dev, idx_dev}, &dev, "period_neighbors")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t total = (int64_t)nsig * frames;
+  hipLaunchKernelGGL(k_period_neighbors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, period_dev, total, frames, nper, step,
+                     k, idx_dev);
+  LAUNCHCHK("k_period_neighbors");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 520
+#define GLOWK_VERSION 530
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -627,6 +627,52 @@ int glowk_nn_neighbors(const float* s_dev, int nsig, int rows, int frames, int k
  * not overlap s_dev; work_bytes at least glowk_nn_workspace_bytes.  Two launches. */
 int glowk_nn_median(const float* s_dev, const int32_t* idx_dev, int nsig, int rows, int frames, int k,
                     float* out_dev /* [nsig][rows][frames], not s_dev */, void* work_dev, size_t work_bytes, void* stream);
+
+/* --- REPET and adaptive REPET: beat spectrum, period, periodic neighbours (Rafii & Pardo 2013; Liutkus et al. 2012) ----------- */
+/* The front end of the original REPET: the repeating period from the beat spectrum (or one period per window from the beat
+ * spectrogram), and per frame the list of the frames whole periods away, which glowk_nn_median then filters over -- the segment
+ * median of REPET with a long list, the adaptive REPET's filter of a given order with a short one; the ratio mask of the
+ * publication is glowk_hpss_mask(harm = min(s, filt), perc = s - min(s, filt), power = 1, both margins 1).  The conventions are
+ * those of the REPET-SIM section: handle-free, every tensor device memory on one device (a host pointer is refused), launches on
+ * `stream` with no atomics, no allocation and no host synchronisation, a launch count that depends on the shapes alone, bitwise
+ * reproducible results, a batch gives what its signals give alone.  Anything outside the stated ranges is GLOWK_ERR with a
+ * glowk_last_error message before anything is launched; nsig = 0 (nseg = 0) is a successful no-op of otherwise valid arguments.
+ * Inputs are finite.  audiosourcesep_amd/repet.py drives the calls.  Since version 530. */
+/* The bytes of work_dev that glowk_beat_spectrum needs: 768 nsig nwin nu nch, the fp64 partial sums of 96 lags per workgroup, with
+ * nwin as below, nmax = frames (win = 0) or win, nu = (min(nlags, nmax) + 30) / 64 + 1, units = sum over u < nu of
+ * ceil(max(nmax - 64 u, 0) / 32), tpw = min(16, max(1, ceil(units / 4096))), nch = ceil(ceil(nmax / 32) / (4 tpw)) (integer
+ * divisions) -- about 12 nlags nmax / tpw bytes per window against the 4 nmax^2 of a Gram matrix, which exists nowhere.  0 for
+ * arguments out of range (and for nsig = 0). */
+size_t glowk_beat_workspace_bytes(int nsig, int rows, int frames, int nlags, int win, int step);
+/* The beat spectrum (win = 0: one window, the whole signal, nwin = 1) or the beat spectrogram (win in [2, frames], step in
+ * [1, win], nwin = ceil(frames / step); window t covers the frames [t step - win / 2, t step - win / 2 + win) that lie in
+ * [0, frames), n_t >= 1 of them from frame a on).  With P = s * s in fp32, for l < n_t
+ *   acf[l] = sum_r sum_{j = a .. a + n_t - 1 - l} P[r][j] P[r][j + l],   raw[l] = acf[l] / (rows (n_t - l)),
+ *   beat[t][l] = raw[l] / raw[0]
+ * (both frames of a pair inside the window), beat[t][l] = 0 for l >= n_t, and all zeros where raw[0] = 0.  sum_r P[r][i] P[r][j]
+ * is one element of the frame Gram matrix of P: an fp32 fma chain over the rows in row order on the fp32 matrix cores, as in
+ * glowk_nn_neighbors, and only the band 0 <= j - i < nlags of the upper triangle is computed.  Everything after it -- the sums
+ * along the diagonals, across tiles and workgroups in a fixed order, the divisions -- is fp64, rounded to float32 once.  Every term
+ * is non-negative, so the error is relative per lag: at most 2 (rows + 2) 2^-24 of the value.  nlags in [1, frames]; beside the
+ * ranges of glowk_nn_* (nsig in [0, 65535], rows in [1, 4096], frames in [1, 32768], nsig * rows * frames <= 2^31 - 1)
+ * nsig * nwin * nlags and the workgroup count nsig * nwin * nu * nch are at most 2^31 - 1.  work_bytes at least
+ * glowk_beat_workspace_bytes, work_dev aligned to 8 bytes; s, beat and work must not overlap.  Nothing is read outside s.  Two
+ * launches. */
+int glowk_beat_spectrum(const float* s_dev, int nsig, int rows, int frames, int nlags, int win, int step,
+                        float* beat_dev /* [nsig][nwin][nlags] */, void* work_dev, size_t work_bytes, void* stream);
+/* period[g] = the lag in [pmin, pmax] of largest beat[g][lag] for each of the nseg segments of nlags values, equal values to the
+ * lower lag (all zeros give pmin): the maximum of one key, the value's bits as an ordered integer above and ~lag below.
+ * 1 <= pmin <= pmax <= nlags - 1, nlags <= 32768, nseg * nlags <= 2^31 - 1.  One launch. */
+int glowk_beat_period(const float* beat_dev /* [nseg][nlags] */, int nseg, int nlags, int pmin, int pmax,
+                      int32_t* period_dev /* [nseg] */, void* stream);
+/* The periodic neighbours.  Frame j uses p = max(1, period[sig][min((j + step / 2) / step, nper - 1)]) (integer division; nper = 1
+ * for one period per signal), and idx[j] lists the frames j + i p for i = 0, -1, +1, -2, +2, .. in that order: those in
+ * [0, frames) are kept until k are kept, the remaining entries are -1.  With k >= ceil(frames / p) that is every frame congruent
+ * to j mod p (REPET's segment median, since a median ignores the order); with a small k the k nearest repetitions (the adaptive
+ * REPET's filter order).  nsig in [0, 65535], frames, nper and step in [1, 32768], k in [1, 512], nsig * frames * k <= 2^31 - 1;
+ * period and idx must not overlap.  One launch. */
+int glowk_period_neighbors(const int32_t* period_dev /* [nsig][nper] */, int nsig, int frames, int nper, int step, int k,
+                           int32_t* idx_dev /* [nsig][frames][k] */, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
