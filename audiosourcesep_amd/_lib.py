@@ -152,6 +152,13 @@ SYMBOLS = {
     "glowk_beat_spectrum": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_beat_period": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "glowk_period_neighbors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_dft2_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_rdft2": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_irdft2": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_plane_std_workspace_bytes": (ctypes.c_size_t, [_i, ctypes.c_int64]),
+    "glowk_plane_std": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_peak_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_peak_mask": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 // whole-signal mel frames and overlapping tiles (glowk_longform.h), BASIS as one chain over a whole signal's frames (glowk_frames.h),
 // harmonic / percussive separation by median filtering (glowk_hpss.h), REPET-SIM's nearest-neighbour filter (glowk_repet.h),
 // REPET's beat spectrum, period and periodic neighbours (glowk_beat.h)
+// the 2DFT separation: the 2-D DFT GEMMs, the plane's std and the peak mask (glowk_dft2.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -16,6 +17,7 @@
 #include "glowk_hpss.h"
 #include "glowk_repet.h"
 #include "glowk_beat.h"
+#include "glowk_dft2.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1237,6 +1239,196 @@ int glowk_period_neighbors(const int32_t* period_dev, int nsig, int frames, int 
   hipLaunchKernelGGL(k_period_neighbors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, period_dev, total, frames, nper, step,
                      k, idx_dev);
   LAUNCHCHK("k_period_neighbors");
+  return 0;
+}
+
+// ---- 2DFT separation: real 2-D DFT and inverse, plane std, peak mask (glowk_dft2.h) --------------------------------------------------
+namespace {
+int dft2_ranges(const char* what, int nsig, int rows, int frames) {
+  using namespace glowk_dft2;
+  const std::string w(what);
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if ((int64_t)nsig * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+// the two twiddle tables filled; 0 or an error.  The launches of both transforms begin with this.
+int dft2_tables(const glowk_dft2::Dft2Plan& p, int rows, int frames, void* work_dev, hipStream_t s) {
+  using namespace glowk_dft2;
+  char* w = (char*)work_dev;
+  hipLaunchKernelGGL(k_dft2_table, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, s, (float2*)(w + p.tab_t_off), frames);
+  LAUNCHCHK("k_dft2_table");
+  hipLaunchKernelGGL(k_dft2_table, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (float2*)(w + p.tab_r_off), rows);
+  LAUNCHCHK("k_dft2_table");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_dft2_workspace_bytes(int nsig, int rows, int frames) {
+  if (dft2_ranges("dft2_workspace_bytes", nsig, rows, frames) || nsig == 0) return 0;
+  return glowk_dft2::dft2_plan(nsig, rows, frames).bytes;
+}
+
+int glowk_rdft2(const float* s_dev, int nsig, int rows, int frames, float* spec_dev, float* mag_dev, void* work_dev, size_t work_bytes,
+                void* stream) {
+  using namespace glowk_dft2;
+  if (int rc = dft2_ranges("rdft2", nsig, rows, frames)) return rc;
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!s_dev || !spec_dev || !work_dev) return fail("null tensor");
+  const Dft2Plan p = dft2_plan(nsig, rows, frames);
+  if (work_bytes < p.bytes) return fail("rdft2: work_bytes is smaller than glowk_dft2_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8 || (uintptr_t)spec_dev % 8) return fail("rdft2: work_dev and spec_dev must be aligned to 8 bytes");
+  const size_t n = (size_t)nsig * rows * frames * 4, ns = (size_t)nsig * rows * p.fc * 8;
+  if (bytes_overlap(s_dev, n, spec_dev, ns) || (mag_dev && (bytes_overlap(s_dev, n, mag_dev, n) || bytes_overlap(spec_dev, ns, mag_dev, n))))
+    return fail("rdft2: s_dev, spec_dev and mag_dev must not overlap");
+  if (bytes_overlap(work_dev, p.bytes, s_dev, n) || bytes_overlap(work_dev, p.bytes, spec_dev, ns) || (mag_dev && bytes_overlap(work_dev, p.bytes, mag_dev, n)))
+    return fail("rdft2: work_dev must not overlap the tensors");
+  if (p.fwd_frames_blocks > (int64_t)INT32_MAX || p.rows_blocks > (int64_t)INT32_MAX) return fail("rdft2: too many workgroups");
+  int dev;
+  if (int rc = audio_device({s_dev, spec_dev, mag_dev, work_dev}, &dev, "rdft2")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = dft2_tables(p, rows, frames, work_dev, st)) return rc;
+  char* w = (char*)work_dev;
+  const float2 *tab_t = (const float2*)(w + p.tab_t_off), *tab_r = (const float2*)(w + p.tab_r_off);
+  float2* mid = (float2*)(w + p.mid_off);
+  const int ng = (int)groups_of(p.fc, NT_FWD);
+  if (frames <= LDS_TAB_MAX)
+    hipLaunchKernelGGL(k_rdft_frames<true>, dim3((unsigned)p.fwd_frames_blocks), dim3(256), (size_t)frames * 8, st, s_dev, p.m_frames, frames, p.fc, ng,
+                       tab_t, mid);
+  else
+    hipLaunchKernelGGL(k_rdft_frames<false>, dim3((unsigned)p.fwd_frames_blocks), dim3(256), 0, st, s_dev, p.m_frames, frames, p.fc, ng, tab_t, mid);
+  LAUNCHCHK("k_rdft_frames");
+  hipLaunchKernelGGL(k_cdft_rows, dim3((unsigned)p.rows_blocks), dim3(256), (size_t)rows * 8, st, (const float2*)mid, (const float*)nullptr, rows, p.fc, frames,
+                     (int)ceil_div64(rows, TILE), (int)groups_of(p.fc, NT_ROWS), tab_r, 1.0f, (float2*)spec_dev, mag_dev);
+  LAUNCHCHK("k_cdft_rows");
+  if (mag_dev) {
+    const int nself = frames % 2 == 0 && frames > 1 ? 2 : 1;
+    const int64_t total = (int64_t)nsig * rows * (frames - p.fc + nself);
+    hipLaunchKernelGGL(k_mag_mirror, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, mag_dev, total, rows, frames, p.fc, nself);
+    LAUNCHCHK("k_mag_mirror");
+  }
+  return 0;
+}
+
+int glowk_irdft2(const float* spec_dev, const float* mask_dev, int nsig, int rows, int frames, float* out_dev, void* work_dev,
+                 size_t work_bytes, void* stream) {
+  using namespace glowk_dft2;
+  if (int rc = dft2_ranges("irdft2", nsig, rows, frames)) return rc;
+  if (nsig == 0) return 0;
+  if (!spec_dev || !out_dev || !work_dev) return fail("null tensor");
+  const Dft2Plan p = dft2_plan(nsig, rows, frames);
+  if (work_bytes < p.bytes) return fail("irdft2: work_bytes is smaller than glowk_dft2_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8 || (uintptr_t)spec_dev % 8) return fail("irdft2: work_dev and spec_dev must be aligned to 8 bytes");
+  const size_t n = (size_t)nsig * rows * frames * 4, ns = (size_t)nsig * rows * p.fc * 8;
+  if (bytes_overlap(out_dev, n, spec_dev, ns) || (mask_dev && bytes_overlap(out_dev, n, mask_dev, n)))
+    return fail("irdft2: out_dev must not overlap spec_dev or mask_dev");
+  if (bytes_overlap(work_dev, p.bytes, out_dev, n) || bytes_overlap(work_dev, p.bytes, spec_dev, ns) || (mask_dev && bytes_overlap(work_dev, p.bytes, mask_dev, n)))
+    return fail("irdft2: work_dev must not overlap the tensors");
+  if (p.inv_frames_blocks > (int64_t)INT32_MAX || p.rows_blocks > (int64_t)INT32_MAX) return fail("irdft2: too many workgroups");
+  int dev;
+  if (int rc = audio_device({spec_dev, mask_dev, out_dev, work_dev}, &dev, "irdft2")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = dft2_tables(p, rows, frames, work_dev, st)) return rc;
+  char* w = (char*)work_dev;
+  const float2 *tab_t = (const float2*)(w + p.tab_t_off), *tab_r = (const float2*)(w + p.tab_r_off);
+  float2* mid = (float2*)(w + p.mid_off);
+  hipLaunchKernelGGL(k_cdft_rows, dim3((unsigned)p.rows_blocks), dim3(256), (size_t)rows * 8, st, (const float2*)spec_dev, mask_dev, rows, p.fc, frames,
+                     (int)ceil_div64(rows, TILE), (int)groups_of(p.fc, NT_ROWS), tab_r, -1.0f, mid, (float*)nullptr);
+  LAUNCHCHK("k_cdft_rows");
+  const float scale = (float)(1.0 / ((double)rows * (double)frames));
+  const int ngi = (int)groups_of(frames, NT_INV);
+  if (frames <= LDS_TAB_MAX)
+    hipLaunchKernelGGL(k_irdft_frames<true>, dim3((unsigned)p.inv_frames_blocks), dim3(256), (size_t)frames * 8, st, (const float2*)mid, p.m_frames,
+                       frames, p.fc, ngi, tab_t, scale, out_dev);
+  else
+    hipLaunchKernelGGL(k_irdft_frames<false>, dim3((unsigned)p.inv_frames_blocks), dim3(256), 0, st, (const float2*)mid, p.m_frames, frames, p.fc, ngi,
+                       tab_t, scale, out_dev);
+  LAUNCHCHK("k_irdft_frames");
+  return 0;
+}
+
+size_t glowk_plane_std_workspace_bytes(int nsig, int64_t n) {
+  if (nsig < 1 || nsig > glowk_dft2::MAX_SIG || n < 1 || (int64_t)nsig * n > (int64_t)INT32_MAX) return 0;
+  return (size_t)nsig * glowk_dft2::std_blocks(n) * 2 * sizeof(double);
+}
+
+int glowk_plane_std(const float* plane_dev, int nsig, int64_t n, double* out_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_dft2;
+  if (nsig < 0 || nsig > MAX_SIG) return fail("plane_std: nsig must be in [0, 65535]");
+  if (n < 1 || n > (int64_t)INT32_MAX) return fail("plane_std: n must be in [1, 2^31 - 1]");
+  if ((int64_t)nsig * n > (int64_t)INT32_MAX) return fail("plane_std: nsig * n must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!plane_dev || !out_dev || !work_dev) return fail("null tensor");
+  const int nb = std_blocks(n);
+  const size_t need = (size_t)nsig * nb * 2 * sizeof(double), np = (size_t)nsig * n * 4, no = (size_t)nsig * 16;
+  if (work_bytes < need) return fail("plane_std: work_bytes is smaller than glowk_plane_std_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8 || (uintptr_t)out_dev % 8) return fail("plane_std: work_dev and out_dev must be aligned to 8 bytes");
+  if (bytes_overlap(plane_dev, np, out_dev, no)) return fail("plane_std: plane_dev and out_dev must not overlap");
+  if (bytes_overlap(work_dev, need, plane_dev, np) || bytes_overlap(work_dev, need, out_dev, no)) return fail("plane_std: work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({plane_dev, out_dev, work_dev}, &dev, "plane_std")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  double *sums = (double*)work_dev, *sq = sums + (size_t)nsig * nb;
+  hipLaunchKernelGGL(k_plane_sum, dim3((unsigned)(nsig * nb)), dim3(256), 0, st, plane_dev, n, nb, (const double*)sums, 0, sums);
+  LAUNCHCHK("k_plane_sum");
+  hipLaunchKernelGGL(k_plane_sum, dim3((unsigned)(nsig * nb)), dim3(256), 0, st, plane_dev, n, nb, (const double*)sums, 1, sq);
+  LAUNCHCHK("k_plane_sum");
+  hipLaunchKernelGGL(k_plane_std_final, dim3((unsigned)((nsig + 63) / 64)), dim3(64), 0, st, (const double*)sums, (const double*)sq, n, nb, nsig, out_dev);
+  LAUNCHCHK("k_plane_std_final");
+  return 0;
+}
+
+namespace {
+int peak_ranges(const char* what, int nsig, int rows, int cols, int nb_r, int nb_c) {
+  using namespace glowk_dft2;
+  const std::string w(what);
+  if (int rc = dft2_ranges(what, nsig, rows, cols)) return rc;
+  if (nb_r < 1 || nb_r > MAX_NB || !(nb_r & 1)) return fail(w + ": nb_r must be odd and in [1, 127]");
+  if (nb_c < 1 || nb_c > MAX_NB || !(nb_c & 1)) return fail(w + ": nb_c must be odd and in [1, 127]");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_peak_workspace_bytes(int nsig, int rows, int cols) {
+  if (dft2_ranges("peak_workspace_bytes", nsig, rows, cols)) return 0;
+  return (size_t)nsig * rows * cols * 8;
+}
+
+int glowk_peak_mask(const float* plane_dev, int nsig, int rows, int cols, int nb_r, int nb_c, const float* thr_dev, float* mask_dev,
+                    float* max_dev, float* min_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_dft2;
+  if (int rc = peak_ranges("peak_mask", nsig, rows, cols, nb_r, nb_c)) return rc;
+  if (nsig == 0) return 0;
+  if (!plane_dev || !mask_dev || !work_dev) return fail("null tensor");
+  const size_t n = (size_t)nsig * rows * cols * 4, need = 2 * n;
+  if (work_bytes < need) return fail("peak_mask: work_bytes is smaller than glowk_peak_workspace_bytes says");
+  if ((uintptr_t)work_dev % 4) return fail("peak_mask: work_dev must be aligned to 4 bytes");
+  const void* outs[3] = {mask_dev, max_dev, min_dev};
+  for (int i = 0; i < 3; ++i) {
+    if (!outs[i]) continue;
+    if (bytes_overlap(plane_dev, n, outs[i], n) || (thr_dev && bytes_overlap(thr_dev, (size_t)nsig * 4, outs[i], n)))
+      return fail("peak_mask: the outputs must not overlap plane_dev or thr_dev");
+    if (bytes_overlap(work_dev, need, outs[i], n)) return fail("peak_mask: work_dev must not overlap the tensors");
+    for (int j = i + 1; j < 3; ++j)
+      if (outs[j] && bytes_overlap(outs[i], n, outs[j], n)) return fail("peak_mask: the outputs must be distinct buffers and not overlap");
+  }
+  if (bytes_overlap(work_dev, need, plane_dev, n) || (thr_dev && bytes_overlap(work_dev, need, thr_dev, (size_t)nsig * 4)))
+    return fail("peak_mask: work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({plane_dev, thr_dev, mask_dev, max_dev, min_dev, work_dev}, &dev, "peak_mask")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  float *hmax = (float*)work_dev, *hmin = hmax + (size_t)nsig * rows * cols;
+  const int nseg = (cols + PK_SEG - 1) / PK_SEG, rtiles = (rows + PK_TR - 1) / PK_TR, ctiles = (cols + PK_TC - 1) / PK_TC;
+  hipLaunchKernelGGL(k_peak_cols, dim3((unsigned)((int64_t)nsig * rows * nseg)), dim3(256), 0, st, plane_dev, cols, nseg, nb_c, hmax, hmin);
+  LAUNCHCHK("k_peak_cols");
+  hipLaunchKernelGGL(k_peak_rows, dim3((unsigned)((int64_t)nsig * rtiles * ctiles)), dim3(256), 0, st, plane_dev, (const float*)hmax, (const float*)hmin,
+                     rows, cols, rtiles, ctiles, nb_r, thr_dev, mask_dev, max_dev, min_dev);
+  LAUNCHCHK("k_peak_rows");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 530
+#define GLOWK_VERSION 540
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -673,6 +673,56 @@ int glowk_beat_period(const float* beat_dev /* [nseg][nlags] */, int nseg, int n
  * period and idx must not overlap.  One launch. */
 int glowk_period_neighbors(const int32_t* period_dev /* [nsig][nper] */, int nsig, int frames, int nper, int step, int k,
                            int32_t* idx_dev /* [nsig][frames][k] */, void* stream);
+
+/* --- 2DFT separation: real 2-D DFT and inverse, plane std, peak mask (Seetharaman, Pishdadian & Pardo 2017) ------------------ */
+/* Repetition as peaks of the 2-D Fourier transform of the magnitude spectrogram: no period, no window.  With R = rows,
+ * T = frames, fc = T / 2 + 1: F = rfft2(s) (numpy's layout, [R][fc]), mag the full Hermitian plane of |F|, std its population
+ * standard deviation, M the peaks of mag (below), B = irfft2(F M) the background, |s - B| the foreground's model, and the masks
+ * are glowk_hpss_mask(harm = |B|, perc = |s - B|).  The conventions are those of the REPET sections: handle-free, every tensor
+ * device memory on one device (a host pointer is refused), launches on `stream` with no atomics, no allocation and no host
+ * synchronisation, a launch count that depends on the shapes (and on which optional tensors are given) alone, bitwise
+ * reproducible results, a batch gives what its signals give alone.  Anything outside the stated ranges is GLOWK_ERR with a
+ * glowk_last_error message before anything is launched; nsig = 0 is a successful no-op of otherwise valid arguments.  Ranges:
+ * nsig in [0, 65535], rows in [1, 4096], frames (cols) in [1, 32768], nsig * rows * frames <= 2^31 - 1.  Inputs are finite.
+ * audiosourcesep_amd/ft2d.py drives the calls.  Since version 540. */
+/* The bytes of work_dev of both transforms: 8 (frames + rows + nsig rows fc) -- the two tables (cos, sin)(2 pi m / N), evaluated in
+ * fp64 and rounded once, and the [nsig][rows][fc] complex plane between the two stages.  0 out of range and for nsig = 0. */
+size_t glowk_dft2_workspace_bytes(int nsig, int rows, int frames);
+/* spec[u][v] = sum_r sum_t s[r][t] exp(-2 pi i (u r / R + v t / T)), u in [0, R), v in [0, fc): two GEMMs on the fp32 matrix
+ * cores, along frames (an fp32 fma chain of T terms in t order per component) then along rows (a chain of 2 R terms in r order),
+ * the twiddles from the tables at the exact integer index (v t) mod T.  Per component |error| <= (2 R + 2 T + 8) 2^-24 sum |s| of
+ * the signal.  mag_dev (nullable) receives the full plane: (float) sqrt((double) re re + (double) im im) for v < fc, and the
+ * bitwise copies mag[u][v] = mag[(R - u) % R][(T - v) % T] for v >= fc and, inside the self-conjugate columns (v = 0, and v = T / 2
+ * for even T), for the rows 2 u > R -- so the plane is Hermitian in its bits everywhere.  spec and work aligned to 8 bytes; s,
+ * spec, mag and work must not overlap.  Nothing is read outside s.  Four launches, five with mag_dev. */
+int glowk_rdft2(const float* s_dev, int nsig, int rows, int frames, float* spec_dev /* [nsig][rows][fc] interleaved complex64 */,
+                float* mag_dev /* [nsig][rows][frames], may be null */, void* work_dev, size_t work_bytes, void* stream);
+/* out = numpy.fft.irfft2(spec * mask[:, :fc], s = (R, T)): the complex inverse along rows, then complex-to-real along frames, where
+ * the imaginary parts of column 0 and (T even) column T / 2 are dropped.  mask_dev (nullable: all ones) is a full plane of which
+ * only the columns < fc are read, multiplied in as spec is loaded (one fp32 product; exact for a 0 / 1 mask); the masked spectrum
+ * is never written.  The scaling 1 / (R T) and the column weights 1 or 2 are folded into the last stage.  Per element
+ * |error| <= (2 R + 2 T + 8) 2^-24 sum |F| / (R T) over the full Hermitian plane.  out must not overlap spec, mask or work.  Four
+ * launches. */
+int glowk_irdft2(const float* spec_dev, const float* mask_dev /* [nsig][rows][frames], may be null */, int nsig, int rows, int frames,
+                 float* out_dev /* [nsig][rows][frames] */, void* work_dev, size_t work_bytes, void* stream);
+/* out[sig] = (mean, population standard deviation) of the n floats of plane[sig], in fp64: per-workgroup partial sums in
+ * work_dev added in index order, two passes (the sum, then the squared deviations from the mean).  The workgroups per signal
+ * depend on n alone.  n in [1, 2^31 - 1], nsig * n <= 2^31 - 1; work_bytes at least glowk_plane_std_workspace_bytes (16 nsig
+ * min(256, ceil(n / 4096)); 0 out of range); out and work aligned to 8 bytes.  Three launches. */
+size_t glowk_plane_std_workspace_bytes(int nsig, int64_t n);
+int glowk_plane_std(const float* plane_dev /* [nsig][n] */, int nsig, int64_t n, double* out_dev /* [nsig][2] */, void* work_dev,
+                    size_t work_bytes, void* stream);
+/* The peak rule.  mx and mn are the largest and smallest value of the periodic nb_r x nb_c neighbourhood of (u, v) (both sizes odd
+ * in [1, 127]; indices wrap modulo rows and cols, as often as a long neighbourhood needs: scipy.ndimage.maximum_filter /
+ * minimum_filter(size = (nb_r, nb_c), mode = 'wrap')); mask = 1.0f where plane == mx and (mx - mn) > thr[sig] (one fp32
+ * subtraction, strict), else 0.0f; with thr_dev null there is no threshold test.  Compares select and nothing else computes, so
+ * max_dev / min_dev (nullable) carry input elements' bits; which of -0 and +0 is returned is unspecified.  A separable running
+ * max / min: along the columns into work_dev (glowk_peak_workspace_bytes = 8 nsig rows cols), then along the rows.  The tensors
+ * must not overlap.  Two launches. */
+size_t glowk_peak_workspace_bytes(int nsig, int rows, int cols);
+int glowk_peak_mask(const float* plane_dev, int nsig, int rows, int cols, int nb_r, int nb_c, const float* thr_dev /* [nsig], may be null */,
+                    float* mask_dev, float* max_dev /* may be null */, float* min_dev /* may be null */, void* work_dev, size_t work_bytes,
+                    void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
