@@ -61,7 +61,7 @@ OK, ERR, ERR_RANGE = 0, 1, 2                       # enum glowk_status
 RANGE_IGNORE, RANGE_ERROR, RANGE_FALLBACK = 0, 1, 2   # enum glowk_range_policy
 MIX_DB, MIX_MEAN = 0, 1                            # enum glowk_mixing
 
-_vp, _i, _fp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
+_vp, _i, _fp, _d = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_double
 
 # every symbol include/glowk.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -159,6 +159,14 @@ SYMBOLS = {
     "glowk_plane_std": (_i, [_vp, _i, ctypes.c_int64, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_peak_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "glowk_peak_mask": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_duet_features": (_i, [_vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "glowk_duet_hist_workspace_bytes": (ctypes.c_size_t, [_i, ctypes.c_int64, _i, _i]),
+    "glowk_duet_histogram": (_i, [_vp, _vp, _vp, _i, ctypes.c_int64, _d, _d, _i, _d, _d, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_duet_histogram_stft": (_i, [_vp, _i, _i, _i, _d, _d, _d, _d, _i, _d, _d, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_duet_peaks_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_duet_peaks": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_duet_assign_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_duet_assign": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _d, _d, _i, _d, _d, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

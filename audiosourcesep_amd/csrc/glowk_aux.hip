@@ -5,6 +5,7 @@
 // harmonic / percussive separation by median filtering (glowk_hpss.h), REPET-SIM's nearest-neighbour filter (glowk_repet.h),
 // REPET's beat spectrum, period and periodic neighbours (glowk_beat.h)
 // the 2DFT separation: the 2-D DFT GEMMs, the plane's std and the peak mask (glowk_dft2.h)
+// DUET: the attenuation-delay histogram, its peaks and the assignment of a two-channel STFT (glowk_duet.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -18,6 +19,7 @@
 #include "glowk_repet.h"
 #include "glowk_beat.h"
 #include "glowk_dft2.h"
+#include "glowk_duet.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1429,6 +1431,242 @@ int glowk_peak_mask(const float* plane_dev, int nsig, int rows, int cols, int nb
   hipLaunchKernelGGL(k_peak_rows, dim3((unsigned)((int64_t)nsig * rtiles * ctiles)), dim3(256), 0, st, plane_dev, (const float*)hmax, (const float*)hmin,
                      rows, cols, rtiles, ctiles, nb_r, thr_dev, mask_dev, max_dev, min_dev);
   LAUNCHCHK("k_peak_rows");
+  return 0;
+}
+
+// ---- DUET: features, the attenuation-delay histogram, its peaks, the assignment (glowk_duet.h) --------------------------------------
+namespace {
+int duet_shape(const std::string& w, int nsig, int rows, int frames) {
+  using namespace glowk_duet;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if ((int64_t)nsig * 2 * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * 2 * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int duet_bins(const std::string& w, int n_a, int n_d) {
+  if (n_a < 1 || n_d < 1 || (int64_t)n_a * n_d > glowk_duet::MAX_BINS) return fail(w + ": n_a and n_d must be at least 1 and n_a * n_d at most 16384");
+  return 0;
+}
+int duet_grid(const std::string& w, double a_lo, double a_hi, int n_a, double d_lo, double d_hi, int n_d) {
+  if (int rc = duet_bins(w, n_a, n_d)) return rc;
+  if (!(std::isfinite(a_lo) && std::isfinite(a_hi) && a_lo < a_hi && std::isfinite(a_hi - a_lo)))
+    return fail(w + ": the attenuation range must be finite with a_lo < a_hi");
+  if (!(std::isfinite(d_lo) && std::isfinite(d_hi) && d_lo < d_hi && std::isfinite(d_hi - d_lo)))
+    return fail(w + ": the delay range must be finite with d_lo < d_hi");
+  return 0;
+}
+int duet_exponents(const std::string& w, double p, double q) {
+  if (!std::isfinite(p) || !std::isfinite(q)) return fail(w + ": the exponents p and q must be finite");
+  return 0;
+}
+int duet_smooth(const std::string& w, int smooth) {
+  if (smooth < 0 || smooth > glowk_duet::MAX_SMOOTH) return fail(w + ": smooth must be in [0, 3]");
+  return 0;
+}
+// the two passes of the histogram, staged (x null) or fused (the planes null)
+int duet_hist_launch(const float* x_dev, const double* a_dev, const double* d_dev, const double* w_dev, int nsig, int64_t cells, int rows, int frames,
+                     double p, double q, const glowk_duet::Ranges& rg, int smooth, int64_t* hist_dev, int32_t* es_dev, void* work_dev, hipStream_t st) {
+  using namespace glowk_duet;
+  const HistPlan pl = hist_plan(nsig, cells, rg.n_a, rg.n_d);
+  const int shift = hist_shift(cells, smooth);
+  double* partial = (double*)work_dev;
+  const dim3 grid((unsigned)((int64_t)nsig * pl.groups)), block(HIST_THREADS);
+  static std::once_flag lds_once;                              // a plane of more than 64 KB needs the attribute on some runtimes
+  std::call_once(lds_once, [] {
+    (void)hipFuncSetAttribute((const void*)k_duet_hist<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_BINS * 8);
+    (void)hipFuncSetAttribute((const void*)k_duet_hist<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_BINS * 8);
+    (void)hipGetLastError();
+  });
+  if (hipMemsetAsync(hist_dev, 0, (size_t)nsig * rg.n_a * rg.n_d * 8, st) != hipSuccess) return fail("duet_histogram: hipMemsetAsync failed");
+  if (x_dev) {
+    hipLaunchKernelGGL(k_duet_wmax<true>, grid, block, 0, st, (const float2*)x_dev, a_dev, d_dev, w_dev, cells, rows, frames, p, q, rg, pl.groups, partial);
+    LAUNCHCHK("k_duet_wmax");
+    hipLaunchKernelGGL(k_duet_hist<true>, grid, block, pl.lds_bytes, st, (const float2*)x_dev, a_dev, d_dev, w_dev, cells, rows, frames, p, q, rg, pl.groups,
+                       shift, (const double*)partial, (unsigned long long*)hist_dev, es_dev);
+  } else {
+    hipLaunchKernelGGL(k_duet_wmax<false>, grid, block, 0, st, (const float2*)x_dev, a_dev, d_dev, w_dev, cells, rows, frames, p, q, rg, pl.groups, partial);
+    LAUNCHCHK("k_duet_wmax");
+    hipLaunchKernelGGL(k_duet_hist<false>, grid, block, pl.lds_bytes, st, (const float2*)x_dev, a_dev, d_dev, w_dev, cells, rows, frames, p, q, rg, pl.groups,
+                       shift, (const double*)partial, (unsigned long long*)hist_dev, es_dev);
+  }
+  LAUNCHCHK("k_duet_hist");
+  return 0;
+}
+}  // namespace
+
+int glowk_duet_features(const float* x_dev, int nsig, int rows, int frames, double p, double q, double* alpha_dev, double* delta_dev, double* w_dev,
+                        void* stream) {
+  using namespace glowk_duet;
+  if (int rc = duet_shape("duet_features", nsig, rows, frames)) return rc;
+  if (int rc = duet_exponents("duet_features", p, q)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !alpha_dev || !delta_dev || !w_dev) return fail("null tensor");
+  const int64_t total = (int64_t)nsig * rows * frames;
+  const size_t nx = (size_t)total * 16, nf = (size_t)total * 8;
+  if ((uintptr_t)x_dev % 8 || (uintptr_t)alpha_dev % 8 || (uintptr_t)delta_dev % 8 || (uintptr_t)w_dev % 8)
+    return fail("duet_features: the tensors must be aligned to 8 bytes");
+  const void* outs[3] = {alpha_dev, delta_dev, w_dev};
+  for (int i = 0; i < 3; ++i) {
+    if (bytes_overlap(x_dev, nx, outs[i], nf)) return fail("duet_features: the outputs must not overlap x_dev");
+    for (int j = i + 1; j < 3; ++j)
+      if (bytes_overlap(outs[i], nf, outs[j], nf)) return fail("duet_features: the outputs must be distinct buffers and not overlap");
+  }
+  int dev;
+  if (int rc = audio_device({x_dev, alpha_dev, delta_dev, w_dev}, &dev, "duet_features")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_duet_features, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float2*)x_dev, total, rows, frames, p, q,
+                     alpha_dev, delta_dev, w_dev);
+  LAUNCHCHK("k_duet_features");
+  return 0;
+}
+
+size_t glowk_duet_hist_workspace_bytes(int nsig, int64_t cells, int n_a, int n_d) {
+  using namespace glowk_duet;
+  if (nsig < 1 || nsig > MAX_SIG || cells < 1 || cells > (int64_t)MAX_ROWS * MAX_FRAMES || n_a < 1 || n_d < 1 || (int64_t)n_a * n_d > MAX_BINS) return 0;
+  return hist_plan(nsig, cells, n_a, n_d).bytes;
+}
+
+int glowk_duet_histogram(const double* alpha_dev, const double* delta_dev, const double* w_dev, int nsig, int64_t cells, double a_lo, double a_hi,
+                         int n_a, double d_lo, double d_hi, int n_d, int smooth, int64_t* hist_dev, int32_t* es_dev, void* work_dev,
+                         size_t work_bytes, void* stream) {
+  using namespace glowk_duet;
+  const std::string me("duet_histogram");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (cells < 1 || cells > (int64_t)MAX_ROWS * MAX_FRAMES) return fail(me + ": cells must be in [1, 2^27]");
+  if ((int64_t)nsig * cells > (int64_t)INT32_MAX) return fail(me + ": nsig * cells must be at most 2^31 - 1");
+  if (int rc = duet_grid(me, a_lo, a_hi, n_a, d_lo, d_hi, n_d)) return rc;
+  if (int rc = duet_smooth(me, smooth)) return rc;
+  if (nsig == 0) return 0;
+  if (!alpha_dev || !delta_dev || !w_dev || !hist_dev || !es_dev || !work_dev) return fail("null tensor");
+  const HistPlan pl = hist_plan(nsig, cells, n_a, n_d);
+  if (work_bytes < pl.bytes) return fail(me + ": work_bytes is smaller than glowk_duet_hist_workspace_bytes says");
+  if ((uintptr_t)alpha_dev % 8 || (uintptr_t)delta_dev % 8 || (uintptr_t)w_dev % 8 || (uintptr_t)hist_dev % 8 || (uintptr_t)work_dev % 8 || (uintptr_t)es_dev % 4)
+    return fail(me + ": the tensors must be aligned to 8 bytes (es_dev to 4)");
+  const size_t nf = (size_t)nsig * cells * 8, nh = (size_t)nsig * n_a * n_d * 8, ne = (size_t)nsig * 8;
+  const void* ins[3] = {alpha_dev, delta_dev, w_dev};
+  for (int i = 0; i < 3; ++i)
+    if (bytes_overlap(ins[i], nf, hist_dev, nh) || bytes_overlap(ins[i], nf, es_dev, ne) || bytes_overlap(ins[i], nf, work_dev, pl.bytes))
+      return fail(me + ": hist_dev, es_dev and work_dev must not overlap the features");
+  if (bytes_overlap(hist_dev, nh, es_dev, ne) || bytes_overlap(hist_dev, nh, work_dev, pl.bytes) || bytes_overlap(es_dev, ne, work_dev, pl.bytes))
+    return fail(me + ": hist_dev, es_dev and work_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({alpha_dev, delta_dev, w_dev, hist_dev, es_dev, work_dev}, &dev, "duet_histogram")) return rc;
+  DeviceGuard dg(dev);
+  const Ranges rg = {a_lo, a_hi, d_lo, d_hi, n_a, n_d};
+  return duet_hist_launch(nullptr, alpha_dev, delta_dev, w_dev, nsig, cells, 1, 1, 1.0, 0.0, rg, smooth, hist_dev, es_dev, work_dev, (hipStream_t)stream);
+}
+
+int glowk_duet_histogram_stft(const float* x_dev, int nsig, int rows, int frames, double p, double q, double a_lo, double a_hi, int n_a, double d_lo,
+                              double d_hi, int n_d, int smooth, int64_t* hist_dev, int32_t* es_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_duet;
+  const std::string me("duet_histogram_stft");
+  if (int rc = duet_shape(me, nsig, rows, frames)) return rc;
+  if (int rc = duet_exponents(me, p, q)) return rc;
+  if (int rc = duet_grid(me, a_lo, a_hi, n_a, d_lo, d_hi, n_d)) return rc;
+  if (int rc = duet_smooth(me, smooth)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !hist_dev || !es_dev || !work_dev) return fail("null tensor");
+  const int64_t cells = (int64_t)rows * frames;
+  const HistPlan pl = hist_plan(nsig, cells, n_a, n_d);
+  if (work_bytes < pl.bytes) return fail(me + ": work_bytes is smaller than glowk_duet_hist_workspace_bytes says");
+  if ((uintptr_t)x_dev % 8 || (uintptr_t)hist_dev % 8 || (uintptr_t)work_dev % 8 || (uintptr_t)es_dev % 4)
+    return fail(me + ": the tensors must be aligned to 8 bytes (es_dev to 4)");
+  const size_t nx = (size_t)nsig * cells * 16, nh = (size_t)nsig * n_a * n_d * 8, ne = (size_t)nsig * 8;
+  if (bytes_overlap(x_dev, nx, hist_dev, nh) || bytes_overlap(x_dev, nx, es_dev, ne) || bytes_overlap(x_dev, nx, work_dev, pl.bytes))
+    return fail(me + ": hist_dev, es_dev and work_dev must not overlap x_dev");
+  if (bytes_overlap(hist_dev, nh, es_dev, ne) || bytes_overlap(hist_dev, nh, work_dev, pl.bytes) || bytes_overlap(es_dev, ne, work_dev, pl.bytes))
+    return fail(me + ": hist_dev, es_dev and work_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({x_dev, hist_dev, es_dev, work_dev}, &dev, "duet_histogram_stft")) return rc;
+  DeviceGuard dg(dev);
+  const Ranges rg = {a_lo, a_hi, d_lo, d_hi, n_a, n_d};
+  return duet_hist_launch(x_dev, nullptr, nullptr, nullptr, nsig, cells, rows, frames, p, q, rg, smooth, hist_dev, es_dev, work_dev, (hipStream_t)stream);
+}
+
+size_t glowk_duet_peaks_workspace_bytes(int nsig, int n_a, int n_d) {
+  using namespace glowk_duet;
+  if (nsig < 1 || nsig > MAX_SIG || n_a < 1 || n_d < 1 || (int64_t)n_a * n_d > MAX_BINS) return 0;
+  return peaks_bytes(nsig, n_a, n_d);
+}
+
+int glowk_duet_peaks(const int64_t* hist_dev, int nsig, int n_a, int n_d, int smooth, int num_sources, int dist_a, int dist_d, int64_t* smooth_dev,
+                     int32_t* peaks_dev, int32_t* nfound_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_duet;
+  const std::string me("duet_peaks");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (int rc = duet_bins(me, n_a, n_d)) return rc;
+  if (int rc = duet_smooth(me, smooth)) return rc;
+  if (num_sources < 1 || num_sources > MAX_SRC) return fail(me + ": num_sources must be in [1, 16]");
+  if (dist_a < 0 || dist_d < 0) return fail(me + ": min_distance must not be negative");
+  if (nsig == 0) return 0;
+  if (!hist_dev || !peaks_dev || !nfound_dev || !work_dev) return fail("null tensor");
+  const size_t need = peaks_bytes(nsig, n_a, n_d), nh = need / 2, np = (size_t)nsig * num_sources * 8, nn = (size_t)nsig * 4;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_duet_peaks_workspace_bytes says");
+  if ((uintptr_t)hist_dev % 8 || (uintptr_t)smooth_dev % 8 || (uintptr_t)work_dev % 8 || (uintptr_t)peaks_dev % 4 || (uintptr_t)nfound_dev % 4)
+    return fail(me + ": the planes and work_dev must be aligned to 8 bytes, the peaks to 4");
+  const void* outs[4] = {smooth_dev, peaks_dev, nfound_dev, work_dev};
+  const size_t sizes[4] = {nh, np, nn, need};
+  for (int i = 0; i < 4; ++i) {
+    if (!outs[i]) continue;
+    if (bytes_overlap(hist_dev, nh, outs[i], sizes[i])) return fail(me + ": the outputs and work_dev must not overlap hist_dev");
+    for (int j = i + 1; j < 4; ++j)
+      if (outs[j] && bytes_overlap(outs[i], sizes[i], outs[j], sizes[j])) return fail(me + ": the outputs and work_dev must not overlap each other");
+  }
+  int dev;
+  if (int rc = audio_device({hist_dev, smooth_dev, peaks_dev, nfound_dev, work_dev}, &dev, "duet_peaks")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(k_duet_peaks, dim3((unsigned)nsig), dim3(PEAK_THREADS), 0, (hipStream_t)stream, (const long long*)hist_dev, n_a, n_d, smooth, num_sources,
+                     dist_a, dist_d, (long long*)work_dev, (long long*)smooth_dev, peaks_dev, nfound_dev);
+  LAUNCHCHK("k_duet_peaks");
+  return 0;
+}
+
+size_t glowk_duet_assign_workspace_bytes(int nsig, int rows, int num_sources) {
+  using namespace glowk_duet;
+  if (nsig < 1 || nsig > MAX_SIG || rows < 1 || rows > MAX_ROWS || num_sources < 1 || num_sources > MAX_SRC) return 0;
+  return assign_bytes(nsig, num_sources, rows);
+}
+
+int glowk_duet_assign(const float* x_dev, int nsig, int rows, int frames, const int32_t* peaks_dev, const int32_t* nfound_dev, int num_sources,
+                      double a_lo, double a_hi, int n_a, double d_lo, double d_hi, int n_d, float* mask_dev, float* spec_dev, void* work_dev,
+                      size_t work_bytes, void* stream) {
+  using namespace glowk_duet;
+  const std::string me("duet_assign");
+  if (int rc = duet_shape(me, nsig, rows, frames)) return rc;
+  if (int rc = duet_grid(me, a_lo, a_hi, n_a, d_lo, d_hi, n_d)) return rc;
+  if (num_sources < 1 || num_sources > MAX_SRC) return fail(me + ": num_sources must be in [1, 16]");
+  if (nsig == 0) return 0;
+  if (!x_dev || !peaks_dev || !nfound_dev || !mask_dev || !spec_dev || !work_dev) return fail("null tensor");
+  const int64_t cells = (int64_t)rows * frames, total = (int64_t)nsig * cells;
+  const size_t need = assign_bytes(nsig, num_sources, rows);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_duet_assign_workspace_bytes says");
+  if ((uintptr_t)x_dev % 8 || (uintptr_t)spec_dev % 8 || (uintptr_t)work_dev % 16 || (uintptr_t)mask_dev % 4 || (uintptr_t)peaks_dev % 4 || (uintptr_t)nfound_dev % 4)
+    return fail(me + ": x_dev and spec_dev must be aligned to 8 bytes, work_dev to 16, the others to 4");
+  const size_t nx = (size_t)total * 16, nm = (size_t)total * num_sources * 4, ns = (size_t)total * num_sources * 16,
+               np = (size_t)nsig * num_sources * 8, nn = (size_t)nsig * 4;
+  const void* ins[3] = {x_dev, peaks_dev, nfound_dev};
+  const size_t in_sizes[3] = {nx, np, nn};
+  const void* outs[3] = {mask_dev, spec_dev, work_dev};
+  const size_t out_sizes[3] = {nm, ns, need};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      if (bytes_overlap(ins[j], in_sizes[j], outs[i], out_sizes[i])) return fail(me + ": mask_dev, spec_dev and work_dev must not overlap the inputs");
+    for (int j = i + 1; j < 3; ++j)
+      if (bytes_overlap(outs[i], out_sizes[i], outs[j], out_sizes[j])) return fail(me + ": mask_dev, spec_dev and work_dev must not overlap each other");
+  }
+  int dev;
+  if (int rc = audio_device({x_dev, peaks_dev, nfound_dev, mask_dev, spec_dev, work_dev}, &dev, "duet_assign")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  const Ranges rg = {a_lo, a_hi, d_lo, d_hi, n_a, n_d};
+  const int64_t entries = (int64_t)nsig * num_sources * rows;
+  hipLaunchKernelGGL(k_duet_table, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, peaks_dev, nfound_dev, entries, num_sources, rows, rg,
+                     (double*)work_dev);
+  LAUNCHCHK("k_duet_table");
+  hipLaunchKernelGGL(k_duet_assign, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float2*)x_dev, total, rows, frames, nfound_dev, num_sources,
+                     (const double*)work_dev, mask_dev, (float2*)spec_dev);
+  LAUNCHCHK("k_duet_assign");
   return 0;
 }
 

@@ -724,6 +724,56 @@ int glowk_peak_mask(const float* plane_dev, int nsig, int rows, int cols, int nb
                     float* mask_dev, float* max_dev /* may be null */, float* min_dev /* may be null */, void* work_dev, size_t work_bytes,
                     void* stream);
 
+/* --- DUET: blind separation of a two-channel STFT from its attenuation-delay histogram (glowk_duet.h) ------------------------------
+ * Handle-free; every call enqueues on `stream`, synchronises with nothing, refuses host pointers and overlapping buffers before it
+ * launches anything, and returns GLOWK_OK at once for nsig == 0.  x: [nsig][2][rows][frames] complex64 (re, im interleaved), the
+ * STFT of two channels; rows in [1, 4096], frames in [1, 32768], nsig * 2 * rows * frames <= 2^31 - 1.  n_fft = 2 (rows - 1),
+ * omega_r = 2 pi r / n_fft.  All arithmetic after the load is fp64.
+ *
+ * Features, rows r >= 1, m1 = |X1|, m2 = |X2|: a cell with m1 == 0 or m2 == 0, and every cell of row 0, has alpha = delta = w = 0;
+ * otherwise alpha = (m2^2 - m1^2) / (m1 m2) (the symmetric attenuation a - 1/a), delta = -arg(X2 conj X1) / omega_r (samples),
+ * w = (m1 m2)^p omega_r^q (p == 1 and q == 0 skip their pow). */
+int glowk_duet_features(const float* x_dev, int nsig, int rows, int frames, double p, double q, double* alpha_dev /* [nsig][rows][frames] */,
+                        double* delta_dev, double* w_dev, void* stream);
+/* The weighted histogram.  A cell counts when its weight is finite and > 0 and i = floor((alpha - a_lo) n_a / (a_hi - a_lo)),
+ * j = floor((delta - d_lo) n_d / (d_hi - d_lo)) (fp64) satisfy 0 <= i < n_a, 0 <= j < n_d (half-open; a non-finite coordinate never
+ * does).  wmax: the largest counted weight of the signal; e: wmax < 2^e <= 2 wmax; s = min(40, 62 - ceil_log2(max(cells, 2)) -
+ * 4 smooth).  hist[sig][i][j] = the int64 sum of rint(w 2^(s - e)) over the cells counted there; es[sig] = (e, s), e = 0 and an
+ * all-zero plane for a signal without a counted weight.  Integer sums: the same bits every run, and in a batch what the signal
+ * gives alone.  n_a, n_d >= 1, n_a n_d <= 16384; finite ranges with lo < hi; smooth in [0, 3] is the number of smoothing passes
+ * glowk_duet_peaks will make, for which s leaves headroom (every smoothed sum stays at or below 2^62).  work_bytes at least
+ * glowk_duet_hist_workspace_bytes (0 out of range); 8-byte alignment.  A memset and two launches: the maximum, then the plane
+ * (per-workgroup LDS planes of 64-bit cells, integer LDS adds, flushed with 64-bit integer global adds).
+ * glowk_duet_histogram reads three fp64 planes of `cells` elements per signal (nsig * cells <= 2^31 - 1); glowk_duet_histogram_stft
+ * reads x and computes the features in registers (cells = rows * frames): bit for bit the plane of glowk_duet_features followed by
+ * glowk_duet_histogram. */
+size_t glowk_duet_hist_workspace_bytes(int nsig, int64_t cells, int n_a, int n_d);
+int glowk_duet_histogram(const double* alpha_dev, const double* delta_dev, const double* w_dev, int nsig, int64_t cells, double a_lo, double a_hi,
+                         int n_a, double d_lo, double d_hi, int n_d, int smooth, int64_t* hist_dev /* [nsig][n_a][n_d] */,
+                         int32_t* es_dev /* [nsig][2] */, void* work_dev, size_t work_bytes, void* stream);
+int glowk_duet_histogram_stft(const float* x_dev, int nsig, int rows, int frames, double p, double q, double a_lo, double a_hi, int n_a, double d_lo,
+                              double d_hi, int n_d, int smooth, int64_t* hist_dev, int32_t* es_dev, void* work_dev, size_t work_bytes, void* stream);
+/* Peaks of non-negative int64 planes.  `smooth` passes of the separable binomial kernel [1 2 1] x [1 2 1] in int64, zero beyond the
+ * edges, no division (the caller keeps 16^smooth times the plane's sum below 2^63); then num_sources (1..16) times: the largest
+ * value among the cells not yet excluded, ties to the lowest row-major index; stop if it is <= 0; record the cell; exclude every
+ * cell with |di| <= dist_a and |dj| <= dist_d.  peaks[sig][k] = (i, j), (-1, -1) from n_found[sig] on; smooth_dev (nullable) gets
+ * the smoothed plane.  One workgroup per signal, one launch; work_bytes at least glowk_duet_peaks_workspace_bytes
+ * (16 nsig n_a n_d). */
+size_t glowk_duet_peaks_workspace_bytes(int nsig, int n_a, int n_d);
+int glowk_duet_peaks(const int64_t* hist_dev, int nsig, int n_a, int n_d, int smooth, int num_sources, int dist_a, int dist_d,
+                     int64_t* smooth_dev /* may be null */, int32_t* peaks_dev /* [nsig][num_sources][2] */, int32_t* nfound_dev /* [nsig] */,
+                     void* work_dev, size_t work_bytes, void* stream);
+/* Assignment, every row including 0.  Source j < n_found has alpha_j, delta_j = the centres lo + (i + 1/2)(hi - lo) / n of its
+ * peak's bins and a_j = (alpha_j + sqrt(alpha_j^2 + 4)) / 2; J_j = |a_j e^{-i delta_j omega_r} X1 - X2|^2 / (1 + a_j^2) in fp64,
+ * the rotation and 1 / (1 + a_j^2) read from a table per (signal, source, row) that the first launch fills in work_dev
+ * (glowk_duet_assign_workspace_bytes = 32 nsig num_sources rows).  mask[sig][j] = 1.0f where j is the lowest found index that
+ * attains the minimum, else 0.0f (all 0 when n_found == 0); spec[sig][j][ch] = X_ch where the mask is 1, +0 elsewhere.  Two
+ * launches. */
+size_t glowk_duet_assign_workspace_bytes(int nsig, int rows, int num_sources);
+int glowk_duet_assign(const float* x_dev, int nsig, int rows, int frames, const int32_t* peaks_dev, const int32_t* nfound_dev, int num_sources,
+                      double a_lo, double a_hi, int n_a, double d_lo, double d_hi, int n_d, float* mask_dev /* [nsig][S][rows][frames] */,
+                      float* spec_dev /* [nsig][S][2][rows][frames] complex64 */, void* work_dev, size_t work_bytes, void* stream);
+
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
  * checkpoint bundles (train_utils.py:62-75), whose tensors are too large for an interpreted byte loop */
