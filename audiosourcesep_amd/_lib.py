@@ -167,6 +167,10 @@ SYMBOLS = {
     "glowk_duet_peaks": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_duet_assign_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "glowk_duet_assign": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _d, _d, _i, _d, _d, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmf_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "glowk_nmf_fit": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmf_divergence": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmf_masks": (_i, [_vp, _i, _vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

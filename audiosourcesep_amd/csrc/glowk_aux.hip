@@ -6,6 +6,7 @@
 // REPET's beat spectrum, period and periodic neighbours (glowk_beat.h)
 // the 2DFT separation: the 2-D DFT GEMMs, the plane's std and the peak mask (glowk_dft2.h)
 // DUET: the attenuation-delay histogram, its peaks and the assignment of a two-channel STFT (glowk_duet.h)
+// NMF: fused multiplicative updates, the beta divergence and masks of component ranges (glowk_nmf.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -20,6 +21,7 @@
 #include "glowk_beat.h"
 #include "glowk_dft2.h"
 #include "glowk_duet.h"
+#include "glowk_nmf.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1667,6 +1669,165 @@ int glowk_duet_assign(const float* x_dev, int nsig, int rows, int frames, const 
   hipLaunchKernelGGL(k_duet_assign, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float2*)x_dev, total, rows, frames, nfound_dev, num_sources,
                      (const double*)work_dev, mask_dev, (float2*)spec_dev);
   LAUNCHCHK("k_duet_assign");
+  return 0;
+}
+
+// ---- NMF: multiplicative updates, divergence, masks of component ranges (glowk_nmf.h) ---------------------------------------------------
+namespace {
+// the ranges every glowk_nmf_* call shares; 0 or an error
+int nmf_ranges(const std::string& w, int nsig, int rows, int frames, int K) {
+  using namespace glowk_nmf;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (K < 1 || K > MAX_K) return fail(w + ": K must be in [1, 128]");
+  if ((int64_t)nsig * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * rows * frames must be at most 2^31 - 1");
+  if ((int64_t)nsig * K * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * K * frames must be at most 2^31 - 1");
+  if ((int64_t)nsig * rows * K > (int64_t)INT32_MAX) return fail(w + ": nsig * rows * K must be at most 2^31 - 1");
+  const NmfPlan p = nmf_plan(rows, frames, K);
+  if ((int64_t)nsig * p.rtiles * p.nch > (int64_t)INT32_MAX || (int64_t)nsig * p.ftiles > (int64_t)INT32_MAX)
+    return fail(w + ": the workgroup count must be at most 2^31 - 1");
+  return 0;
+}
+int nmf_model(const std::string& w, int nsig, int nw, int beta) {
+  if (nw != 1 && nw != nsig) return fail(w + ": nw must be 1 (one shared dictionary) or nsig");
+  if (beta < 0 || beta > 2) return fail(w + ": beta must be 0 (Itakura-Saito), 1 (Kullback-Leibler) or 2 (Euclidean)");
+  return 0;
+}
+
+#define GLOWK_NMF_EACH_KT(X) X(1) X(2) X(3) X(4)
+}  // namespace
+
+size_t glowk_nmf_workspace_bytes(int nsig, int rows, int frames, int K) {
+  if (nmf_ranges("nmf_workspace_bytes", nsig, rows, frames, K)) return 0;
+  return glowk_nmf::nmf_work_bytes(nsig, rows, frames, K);
+}
+
+int glowk_nmf_fit(const float* v_dev, int nsig, int rows, int frames, float* w_dev, int nw, float* h_dev, int K, int beta, int n_iter, int update_w,
+                  void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_nmf;
+  const std::string me("nmf_fit");
+  if (int rc = nmf_ranges(me, nsig, rows, frames, K)) return rc;
+  if (int rc = nmf_model(me, nsig, nw, beta)) return rc;
+  if (n_iter < 0 || n_iter > MAX_ITER) return fail(me + ": n_iter must be in [0, 100000]");
+  if (update_w < 0 || update_w > 2) return fail(me + ": update_w must be 0 (H alone), 1 (W, then H) or 2 (W alone)");
+  if (update_w && nw != nsig) return fail(me + ": a dictionary shared by several signals cannot be updated (nw = 1 needs update_w = 0)");
+  if (nsig == 0 || n_iter == 0) return 0;
+  if (!v_dev || !w_dev || !h_dev || (update_w && !work_dev)) return fail("null tensor");
+  const NmfPlan p = nmf_plan(rows, frames, K);
+  const size_t need = update_w ? (size_t)nsig * (size_t)nmf_w_part_floats(p, rows, K) * 4 : 0;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_nmf_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8) return fail(me + ": work_dev must be aligned to 8 bytes");
+  const size_t nv = (size_t)nsig * rows * frames * 4, nww = (size_t)nw * rows * K * 4, nh = (size_t)nsig * K * frames * 4;
+  if (bytes_overlap(v_dev, nv, w_dev, nww) || bytes_overlap(v_dev, nv, h_dev, nh) || bytes_overlap(w_dev, nww, h_dev, nh))
+    return fail(me + ": V, W and H must not overlap");
+  if (need && (bytes_overlap(work_dev, need, v_dev, nv) || bytes_overlap(work_dev, need, w_dev, nww) || bytes_overlap(work_dev, need, h_dev, nh)))
+    return fail(me + ": work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({v_dev, w_dev, h_dev, work_dev}, &dev, "nmf_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)work_dev;
+  const int64_t wstride = nw == 1 ? 0 : (int64_t)rows * K, per_sig = (int64_t)rows * K, total = (int64_t)nsig * per_sig;
+  const dim3 gw((unsigned)((int64_t)nsig * p.rtiles * p.nch)), gh((unsigned)((int64_t)nsig * p.ftiles)), gf((unsigned)((total + 255) / 256));
+  for (int it = 0; it < n_iter; ++it) {
+    if (update_w) {
+      switch (p.kt) {
+#define GLOWK_CASE(n) \
+  case n: hipLaunchKernelGGL(k_nmf_update_w<n>, gw, dim3(256), 0, st, v_dev, (const float*)w_dev, (const float*)h_dev, rows, frames, K, p, beta, part); break;
+        GLOWK_NMF_EACH_KT(GLOWK_CASE)
+#undef GLOWK_CASE
+      }
+      LAUNCHCHK("k_nmf_update_w");
+      hipLaunchKernelGGL(k_nmf_w_finish, gf, dim3(256), 0, st, (const float*)part, total, per_sig, nmf_w_part_floats(p, rows, K), p.nch, beta, w_dev);
+      LAUNCHCHK("k_nmf_w_finish");
+    }
+    if (update_w != 2) {
+      switch (p.kt) {
+#define GLOWK_CASE(n) \
+  case n: hipLaunchKernelGGL(k_nmf_update_h<n>, gh, dim3(256), 0, st, v_dev, (const float*)w_dev, wstride, h_dev, rows, frames, K, p.ftiles, beta); break;
+        GLOWK_NMF_EACH_KT(GLOWK_CASE)
+#undef GLOWK_CASE
+      }
+      LAUNCHCHK("k_nmf_update_h");
+    }
+  }
+  return 0;
+}
+
+int glowk_nmf_divergence(const float* v_dev, int nsig, int rows, int frames, const float* w_dev, int nw, const float* h_dev, int K, int beta,
+                         double* out_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_nmf;
+  const std::string me("nmf_divergence");
+  if (int rc = nmf_ranges(me, nsig, rows, frames, K)) return rc;
+  if (int rc = nmf_model(me, nsig, nw, beta)) return rc;
+  if (nsig == 0) return 0;
+  if (!v_dev || !w_dev || !h_dev || !out_dev || !work_dev) return fail("null tensor");
+  const NmfPlan p = nmf_plan(rows, frames, K);
+  const size_t need = (size_t)nsig * (size_t)nmf_div_parts(p) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_nmf_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8 || (uintptr_t)out_dev % 8) return fail(me + ": work_dev and out_dev must be aligned to 8 bytes");
+  const size_t nv = (size_t)nsig * rows * frames * 4, nww = (size_t)nw * rows * K * 4, nh = (size_t)nsig * K * frames * 4, no = (size_t)nsig * 8;
+  const void* ins[3] = {v_dev, w_dev, h_dev};
+  const size_t in_sizes[3] = {nv, nww, nh};
+  for (int i = 0; i < 3; ++i)
+    if (bytes_overlap(ins[i], in_sizes[i], out_dev, no) || bytes_overlap(ins[i], in_sizes[i], work_dev, need))
+      return fail(me + ": out_dev and work_dev must not overlap the inputs");
+  if (bytes_overlap(out_dev, no, work_dev, need)) return fail(me + ": out_dev and work_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({v_dev, w_dev, h_dev, out_dev, work_dev}, &dev, "nmf_divergence")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_nmf_divergence, dim3((unsigned)((int64_t)nsig * p.rtiles * p.nch)), dim3(256), 0, st, v_dev, w_dev, nw == 1 ? (int64_t)0 : (int64_t)rows * K,
+                     h_dev, rows, frames, K, p, beta, (double*)work_dev);
+  LAUNCHCHK("k_nmf_divergence");
+  hipLaunchKernelGGL(k_nmf_div_reduce, dim3((unsigned)nsig), dim3(64), 0, st, (const double*)work_dev, nmf_div_parts(p), out_dev);
+  LAUNCHCHK("k_nmf_div_reduce");
+  return 0;
+}
+
+int glowk_nmf_masks(const float* w_dev, int nw, const float* h_dev, int nsig, int rows, int frames, int K, const int32_t* bounds_host, int num_sources,
+                    int power, const float* x_dev, int channels, float* mask_dev, float* spec_dev, void* stream) {
+  using namespace glowk_nmf;
+  const std::string me("nmf_masks");
+  if (int rc = nmf_ranges(me, nsig, rows, frames, K)) return rc;
+  if (nw != 1 && nw != nsig) return fail(me + ": nw must be 1 (one shared dictionary) or nsig");
+  if (num_sources < 1 || num_sources > MAX_SRC) return fail(me + ": the number of sources must be in [1, 16]");
+  if (power != 1 && power != 2) return fail(me + ": power must be 1 or 2");
+  if (!bounds_host) return fail(me + ": bounds_host is null");
+  NmfBounds bd;
+  for (int s = 0; s <= MAX_SRC; ++s) bd.b[s] = s <= num_sources ? bounds_host[s] : K;
+  if (bd.b[0] != 0 || bd.b[num_sources] != K) return fail(me + ": bounds must start at 0 and end at K");
+  for (int s = 0; s < num_sources; ++s)
+    if (bd.b[s] >= bd.b[s + 1]) return fail(me + ": bounds must increase strictly (every source owns at least one component)");
+  if ((x_dev == nullptr) != (spec_dev == nullptr)) return fail(me + ": x_dev and spec_dev are given together or not at all");
+  if (x_dev && channels != 1 && channels != 2) return fail(me + ": the channel count must be 1 or 2");
+  const int C = x_dev ? channels : 0;
+  const int64_t cells = (int64_t)nsig * rows * frames;
+  if (cells * num_sources * (C ? C : 1) > (int64_t)INT32_MAX) return fail(me + ": nsig * S * C * rows * frames must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!w_dev || !h_dev || !mask_dev) return fail("null tensor");
+  if ((uintptr_t)x_dev % 8 || (uintptr_t)spec_dev % 8) return fail(me + ": x_dev and spec_dev must be aligned to 8 bytes");
+  const size_t nww = (size_t)nw * rows * K * 4, nh = (size_t)nsig * K * frames * 4, nx = (size_t)cells * C * 8,
+               nm = (size_t)cells * num_sources * 4, ns = (size_t)cells * num_sources * C * 8;
+  const void* ins[3] = {w_dev, h_dev, x_dev};
+  const size_t in_sizes[3] = {nww, nh, nx};
+  for (int i = 0; i < 3; ++i) {
+    if (!ins[i]) continue;
+    if (bytes_overlap(ins[i], in_sizes[i], mask_dev, nm) || (spec_dev && bytes_overlap(ins[i], in_sizes[i], spec_dev, ns)))
+      return fail(me + ": mask_dev and spec_dev must not overlap the inputs");
+  }
+  if (spec_dev && bytes_overlap(mask_dev, nm, spec_dev, ns)) return fail(me + ": mask_dev and spec_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({w_dev, h_dev, x_dev, mask_dev, spec_dev}, &dev, "nmf_masks")) return rc;
+  DeviceGuard dg(dev);
+  const NmfPlan p = nmf_plan(rows, frames, K);
+  const int fgroups = (p.ftiles + WAVES - 1) / WAVES;
+  if ((int64_t)nsig * p.rtiles * fgroups > (int64_t)INT32_MAX) return fail(me + ": the workgroup count must be at most 2^31 - 1");
+  hipLaunchKernelGGL(k_nmf_masks, dim3((unsigned)((int64_t)nsig * p.rtiles * fgroups)), dim3(256), 0, (hipStream_t)stream, w_dev,
+                     nw == 1 ? (int64_t)0 : (int64_t)rows * K, h_dev, rows, frames, K, p.rtiles, fgroups, bd, num_sources, power, (const float2*)x_dev, C, mask_dev,
+                     (float2*)spec_dev);
+  LAUNCHCHK("k_nmf_masks");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 540
+#define GLOWK_VERSION 550
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -773,6 +773,51 @@ size_t glowk_duet_assign_workspace_bytes(int nsig, int rows, int num_sources);
 int glowk_duet_assign(const float* x_dev, int nsig, int rows, int frames, const int32_t* peaks_dev, const int32_t* nfound_dev, int num_sources,
                       double a_lo, double a_hi, int n_a, double d_lo, double d_hi, int n_d, float* mask_dev /* [nsig][S][rows][frames] */,
                       float* spec_dev /* [nsig][S][2][rows][frames] complex64 */, void* work_dev, size_t work_bytes, void* stream);
+
+/* --- NMF: multiplicative updates for the beta divergences, ratio masks of component ranges (Lee & Seung 2001; Fevotte & Idier 2011) -- */
+/* V [nsig][rows][frames] float32, finite and >= 0, frames contiguous; W [nw][rows][K], K contiguous, nw = nsig or 1 (one dictionary
+ * shared by every signal, allowed only where W is not updated); H [nsig][K][frames]; W and H float32, finite and >= 0.
+ * FLOOR = 2^-40.  beta = 0 (Itakura-Saito), 1 (Kullback-Leibler) or 2 (Euclidean); there is no general power.
+ *   L = W H, an fp32 fma chain over K (padded with exact zeros) on v_mfma_f32_32x32x2_f32;  Le = max(L, FLOOR);
+ *   beta 2: Q = V, P = Le;   beta 1: Q = V / Le, P = 1;   beta 0: Q = V / (Le Le), P = 1 / Le;
+ *   H update: H' = H g(W^T Q / max(W^T P, FLOOR));   W update: W' = W g(Q H^T / max(P H^T, FLOOR));
+ *   g(x) = sqrt(x) for beta 0, x otherwise (the majorise-minimise exponent 1 / (2 - beta) of scikit-learn: no update increases D).
+ * The outer sums (over the rows for H, over the frames for W) are fp32 fma chains on the same instruction, in an order that the
+ * shapes fix; the division, the square root and the last product are one fp32 operation each.  Every term is non-negative, so the
+ * error of one update is relative per element: at most (3 K + 2 n + 16) 2^-24 of the value, n = rows for H and frames for W, and an
+ * exact 0 where the exact result is 0.  L, Q and P exist in registers alone.  The conventions are those of the REPET section:
+ * handle-free, every tensor device memory on one device (a host pointer is refused), launches on `stream` with no atomics, no
+ * allocation and no host synchronisation, a launch count that depends on the shapes and n_iter alone, bitwise reproducible
+ * results, a batch gives what its signals give alone.  nsig in [0, 65535] (0: a successful no-op), rows in [1, 4096], frames in
+ * [1, 32768], K in [1, 128], every tensor at most 2^31 - 1 elements; anything else is GLOWK_ERR with a glowk_last_error message
+ * before anything is launched.  audiosourcesep_amd/nmf.py drives the calls.  Since version 550. */
+/* The bytes of work_dev that glowk_nmf_fit and glowk_nmf_divergence need.  With rtiles = ceil(rows / 32), ftiles =
+ * ceil(frames / 32), want = min(max(1, 256 / rtiles), max(1, ftiles / 4)) (integer divisions), tpc = ceil(ftiles / want), nch = ceil(ftiles / tpc)
+ * (the frames are cut into nch chunks of 32 tpc; a function of rows and frames alone, never of nsig):
+ * nsig max(8 nch rows K, 8 rtiles nch).  0 for arguments out of range (and for nsig = 0). */
+size_t glowk_nmf_workspace_bytes(int nsig, int rows, int frames, int K);
+/* n_iter iterations in place.  update_w = 1: the W update (with the old H), then the H update (with the new W), scikit-learn's
+ * order; 0: H alone moves (W may be shared, nw = 1); 2: W alone moves.  n_iter in [0, 100000]; 0 is a successful no-op.  The W
+ * update writes partial numerators and denominators per chunk of frames to work_dev and a second launch adds them in chunk order:
+ * 3 n_iter launches with update_w = 1, 2 n_iter with 2, n_iter with 0 (then work_dev may be null).  V, W, H and work must not
+ * overlap; work_dev aligned to 8 bytes. */
+int glowk_nmf_fit(const float* v_dev, int nsig, int rows, int frames, float* w_dev, int nw, float* h_dev, int K, int beta, int n_iter,
+                  int update_w, void* work_dev, size_t work_bytes, void* stream);
+/* out[sig] = D_beta(V | W H), float64: the terms in fp64 from the fp32 Le, added in an order the shapes fix.
+ *   beta 2: (V - Le)^2 / 2;   beta 1: V ln(V / Le) - V + Le with 0 ln 0 = 0;   beta 0: q - ln q - 1, q = max(V, FLOOR) / Le.
+ * At most (K + 4) 2^-24 sum(w) from the exact value, w = (V + L)^2, V + L, q + 1.  Two launches. */
+int glowk_nmf_divergence(const float* v_dev, int nsig, int rows, int frames, const float* w_dev, int nw, const float* h_dev, int K, int beta,
+                         double* out_dev /* [nsig] */, void* work_dev, size_t work_bytes, void* stream);
+/* Ratio masks of num_sources <= 16 sources that own the component ranges [bounds[s], bounds[s + 1]), bounds_host[0] = 0 < .. <
+ * bounds_host[num_sources] = K (host memory, read before the call returns): L_s = the fp32 chain over the range of source s,
+ * m_s = L_s^power (power 1 or 2), mask_s = m_s / sum_s m_s (the sum in source order), and 1 / num_sources where the sum is below
+ * FLOOR.  With x_dev, a complex64 spectrum of `channels` in {1, 2} planes per signal, also spec[sig][s][ch] = mask_s X_ch (one fp32
+ * product per component); x_dev and spec_dev are both given or both null (then channels is ignored).  nsig * S * C * rows *
+ * frames <= 2^31 - 1.  The outputs must not overlap the inputs or each other.  One launch. */
+int glowk_nmf_masks(const float* w_dev, int nw, const float* h_dev, int nsig, int rows, int frames, int K, const int32_t* bounds_host,
+                    int num_sources, int power, const float* x_dev /* [nsig][C][rows][frames] complex64, or null */, int channels,
+                    float* mask_dev /* [nsig][S][rows][frames] */, float* spec_dev /* [nsig][S][C][rows][frames] complex64, or null */,
+                    void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
