@@ -170,6 +170,45 @@ int glowk_add_noise(const float* x_dev, float* out_dev, size_t n, float sigma, u
   return 0;
 }
 
+// ---- the split kernels' activation + hi/lo split, eight values per thread through the very helpers the network kernels inline
+namespace glowk_eng {
+// mode 0: ReLU, scale, split (h3s_act<NET_FWD>); 1: the two-term mode (NET_FWD2: hi only); 2: scale and split alone (the gather prologues)
+__global__ __launch_bounds__(256) void k_split_probe(const float* __restrict__ x, int n, float sc, int mode, unsigned short* __restrict__ hi,
+                                                     unsigned short* __restrict__ lo) {
+  const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 8;
+  if (i0 >= n) return;
+  f32x4 r0, r1;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = i0 + j < n ? x[i0 + j] : 0.0f;
+    if (j < 4) r0[j] = v[j]; else r1[j - 4] = v[j];
+  }
+  h8 bh, bl;
+  if (mode == 0) h3s_act<NET_FWD, false, true>(r0, r1, sc, 0u, bh, bl);
+  else if (mode == 1) h3s_act<NET_FWD2, false, true>(r0, r1, sc, 0u, bh, bl);
+  else split8(v, sc, bh, bl);
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (i0 + j < n) {
+      hi[i0 + j] = __builtin_bit_cast(unsigned short, (_Float16)bh[j]);
+      lo[i0 + j] = __builtin_bit_cast(unsigned short, (_Float16)bl[j]);
+    }
+}
+}  // namespace glowk_eng
+
+int glowk_split_probe(const float* x_dev, int n, float sc, int mode, uint16_t* hi_dev, uint16_t* lo_dev, void* stream) {
+  if (!x_dev || !hi_dev || !lo_dev) return fail("null tensor");
+  if (n < 0 || n > (1 << 30)) return fail("split_probe: n must be 0..2^30");
+  if (mode < 0 || mode > 2) return fail("split_probe: mode must be 0 (ReLU), 1 (two-term) or 2 (no activation)");
+  if (!split_scale_ok(sc)) return fail("split_probe: the scale must be a power of two (the kernels' contract, NetArgs::sc1)");
+  if (n == 0) return 0;
+  DeviceGuard dg(ptr_device(hi_dev));
+  hipLaunchKernelGGL(k_split_probe, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, x_dev, n, sc, mode, hi_dev, lo_dev);
+  LAUNCHCHK("k_split_probe");
+  return 0;
+}
+
 namespace glowk_eng {
 struct Crc32cTable {
   uint32_t t[8][256];

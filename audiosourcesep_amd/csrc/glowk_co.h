@@ -219,12 +219,12 @@ __device__ __forceinline__ void co_Z(const NetArgs& a, const H3Ctx& hc, const Co
       unsigned mask = 0, bits = 0;
       if (G::BWD) mask = hc.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];        // mask1: the ReLU after conv1
       if constexpr (G::STORE)
-        bits = h3s_act_pair<MODE7, true>(acc2[2 * fo][0], acc2[2 * fo + 1][0], acc2[2 * fo][1], acc2[2 * fo + 1][1], a.sc2, mask, bh, bl,
+        bits = h3s_act_pair<MODE7, true, split_fma<KIN>>(acc2[2 * fo][0], acc2[2 * fo + 1][0], acc2[2 * fo][1], acc2[2 * fo + 1][1], a.sc2, mask, bh, bl,
                                          uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q), ((unsigned)(4 * kq) * (unsigned)a.Q + (unsigned)q[0]) * 4u,
                                          (unsigned)a.Q * 4u);
       else {
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) bits |= h3s_act<MODE7, false>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf]) << (8 * hf);
+        for (int hf = 0; hf < 2; ++hf) bits |= h3s_act<MODE7, false, split_fma<KIN>>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf]) << (8 * hf);
       }
       if (G::SAVE && hc.wok) a.mask2[(hc.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
     }
@@ -405,7 +405,7 @@ __device__ __forceinline__ void co_Xdb(const NetArgs& a, const h8 (&xh)[(RingC<K
 #pragma unroll
   for (int j = 0; j < 4; ++j) A0[j] = buf[j * 64];      // row blocks 0, 1 (hi, lo): co_Ydb's group 0
   __builtin_amdgcn_sched_barrier(0);
-  h3s_X_act<G::MODE7>(h1, a.sc1, bh, bl);
+  h3s_X_act<G::MODE7, split_fma<KIN>>(h1, a.sc1, bh, bl);
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -430,7 +430,7 @@ __device__ __forceinline__ void co_Zdb(const NetArgs& a, const CoCtxDB& c, const
     const int fo = t / NMT, ml = t % NMT;
     if (ml == 0) {
 #pragma unroll
-      for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, 0u, bh[hf], bl[hf]);
+      for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false, split_fma<KIN>>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, 0u, bh[hf], bl[hf]);
     }
     if (fo == 0) {
 #pragma unroll
@@ -603,9 +603,7 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
         const float fac = G::STORE ? 1.0f : pixel_norm(pm, a.bnorm, hc.ub[hf]);     // (training: one scale per launch, BwdArgs::go_scale)
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[s][j] *= fac;
-          split8(v[s], xh[s][hf], xl[s][hf]);
+          split8(v[s], fac, xh[s][hf], xl[s][hf]);
         }
       } else if constexpr (S::STK) {
         xmax = gather_stacked<KIN, SGN, G::MODE7 == NET_FWD2, KS, S::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], kq, xh, xl, hf, xmax);
@@ -615,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void k_net_h3c(NetArgs a) {
           float v[8];
           gather8<KIN, true, SGN>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], 32 * s + 8 * kq, v);
           xmax = range8(xmax, v);
-          split8(v, xh[s][hf], xl[s][hf]);
+          split8(v, 1.0f, xh[s][hf], xl[s][hf]);
         }
       }
     }

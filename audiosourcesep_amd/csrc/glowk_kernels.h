@@ -54,6 +54,9 @@ struct NetArgs {
   const float4* RSp = nullptr;     // image for the 16x16x32 kernel (RingS; same constants and scales) of the network this launch runs, or null
   int fam16 = 0;             // host side: this level's saving forward and backward launches both have a 16x16x32 image
   float sc1 = 0.0f, sc2 = 0.0f, sc3 = 0.0f;   // f16x3: 2^-S of the three layers' weight scales (sc3 also undoes the activation scale)
+                         // CONTRACT: sc1 and sc2 are powers of two.  The kernels apply them as the multiplicand of the split's FMAs
+                         // (split8), which equals multiply-then-split only then; the host refuses anything else where the scales are
+                         // produced (glowk_pack.h: split_scales_ok)
   int* flag = nullptr;             // sticky range flag of the handle, or null
   float xlim = 0.0f;            // split kernels: raise the flag when a gathered input (times GLOWK_ACT_SCALE) exceeds this magnitude
   float bnorm = 1.0f;           // split kernels, backward network (linear in its input): every pixel's gathered gradient vector is scaled by the
@@ -580,21 +583,77 @@ __device__ __forceinline__ float pixel_norm(float m, float target, float& undo) 
   return ok ? __uint_as_float((unsigned)ef << 23) : 1.0f;
 }
 
-// x = hi + lo with hi = fp16(x), lo = fp16(x - hi), two values at a time: one packed conversion for the hi pair, two
-// conversions back, one packed subtraction, one packed conversion for the lo pair (3 instructions per value; hipcc's scalar
-// form of the same arithmetic converts hi twice: 4)
+// x = v * sc = hi + lo with hi = fp16(x), lo = fp16(x - hi), for sc A POWER OF TWO (the NetArgs contract).
+// NONNEG (v >= +0: a ReLU output, the hot path): the product is exact, so hi = fp16(fma(v, sc, 0)) and lo = fp16(fma(v, sc, -hi)) are
+// the bits of the multiply / convert / convert back / subtract / convert chain (x - hi is exact in fp32) at two instructions per
+// value: v_fma_mixlo / mixhi_f16 take fp32 and fp16 sources, round their fp32 result to fp16 and write their half of the packed
+// register -- no separate multiply, no conversion back, no packed fp32.
+// Signed values (the backward network's masked gradients, the gathered inputs) keep the multiply-then-split chain as it was (one packed
+// multiply, one packed conversion, two conversions back, one packed subtraction, one packed conversion per pair): with the scale
+// inside the FMAs a NEGATIVE product that underflows fp32 altogether (|v sc| < 2^-150) gives lo = -0 where the chain gives +0 --
+// fma(v, sc, +0) rounds a tiny negative sum to -0, while -0 - -0 is +0 -- and hi would need the addend -0 to keep v = -0 (measured with
+// glowk_split_probe, docs/EXPERIMENTS.md).  These are prologues and the backward network, not the headline loop.
+// Two values at a time: the hi pair is formed first, as one packed register, and the lo FMAs read its halves in place (op_sel).  The
+// empty asm keeps the pair a register to the compiler, which otherwise computes the odd element's hi twice -- once on its own as the
+// lo FMA's addend, once into the packed register: 3.5 instead of 3 instructions per value with the ReLU.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo) {
+template <bool NONNEG>
+__device__ __forceinline__ void split2(float v0, float v1, float sc, h2v& hi, h2v& lo) {
+  if constexpr (NONNEG) {
+    hi = h2v{(_Float16)__builtin_fmaf(v0, sc, 0.0f), (_Float16)__builtin_fmaf(v1, sc, 0.0f)};
+    asm("" : "+v"(hi));
+    lo = h2v{(_Float16)__builtin_fmaf(v0, sc, -(float)hi[0]), (_Float16)__builtin_fmaf(v1, sc, -(float)hi[1])};
+  } else {
+    f32x2 t = f32x2{v0, v1} * f32x2{sc, sc};
+    asm("" : "+v"(t));                 // (or the compiler contracts t - hi back into fma(v, sc, -hi))
+    hi = __builtin_convertvector(t, h2v);
+    lo = __builtin_convertvector(t - __builtin_convertvector(hi, f32x2), h2v);
+  }
+}
+template <bool NONNEG = false>
+__device__ __forceinline__ void split8(const float (&v)[8], float sc, h8& hi, h8& lo) {
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
-    const f32x2 p = {v[j], v[j + 1]};
+    h2v h, l;
+    split2<NONNEG>(v[j], v[j + 1], sc, h, l);
+    hi[j] = h[0]; hi[j + 1] = h[1];
+    lo[j] = l[0]; lo[j + 1] = l[1];
+  }
+}
+// two-term mode (NET_FWD2): hi only
+__device__ __forceinline__ void split8_hi(const float (&v)[8], float sc, h8& hi, h8& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { hi[j] = (_Float16)__builtin_fmaf(v[j], sc, 0.0f); lo[j] = (_Float16)0.0f; }
+}
+
+// Which level shapes take the FMA form: the 2- and 4-input-channel ones (levels 0 and 1 of the headline flow; -1.5 % and -0.2 % per
+// launch).  At 8 and 16 input channels the instances sit at the register limit (k_net_h3s<8,144,16,0,2,false>: 256 VGPRs) and the FMA form
+// -- each packed result tied to one register from its first half on -- made that one spill 108 bytes and run 12 % slower
+// (docs/EXPERIMENTS.md): they keep the multiply / max / convert / convert back / subtract / convert chain on scaled values.
+template <int KIN> constexpr bool split_fma = KIN <= 4;
+__device__ __forceinline__ void split8_chain(const float (&t)[8], h8& hi, h8& lo) {      // t: already scaled
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const f32x2 p = {t[j], t[j + 1]};
     const h2v h = __builtin_convertvector(p, h2v);
     const f32x2 d = p - __builtin_convertvector(h, f32x2);
     const h2v l = __builtin_convertvector(d, h2v);
     hi[j] = h[0]; hi[j + 1] = h[1];
     lo[j] = l[0]; lo[j + 1] = l[1];
   }
+}
+
+// ReLU of an accumulator value in ONE instruction: v_med3_f32(a, 0, +inf).  fmaxf(a, 0) costs two here -- the compiler cannot see
+// that an MFMA result is never a signalling NaN and first canonicalises it (v_max_f32 a, a) -- and a v_max_f32 written as inline asm is
+// invisible to the compiler's hazard tracking: it gets no wait states behind the MFMA whose result it reads, and read stale registers
+// (a small flow's log_prob came out 5e-4 off).  The median is an instruction the compiler schedules itself; the infinity is made opaque
+// (one SGPR), or the median of (a, 0, inf) is folded back into fmaxf.  A quiet NaN gives 0 and -0 gives +0, as v_max_f32 did
+// (tests/test_gpu_act_split.py holds both to the bits of the old arithmetic).
+__device__ __forceinline__ float relu1(float a) {
+  float inf = __builtin_inff();
+  asm("" : "+s"(inf));
+  return __builtin_amdgcn_fmed3f(a, 0.0f, inf);
 }
 
 __device__ __forceinline__ f32x16 mfma3(const h8& ahi, const h8& alo, const h8& bhi, const h8& blo, f32x16 acc) {
@@ -677,8 +736,8 @@ __device__ __forceinline__ float gather8_stacked(const float* base, int i, int j
       const int cbe = e == 0 ? cbv : 0;                                       // (the group at 3 K1 is never `ok`: or-ing is selecting)
       const f32x2 v = {__int_as_float((__float_as_int(x[e] * GLOWK_ACT_SCALE) & okv) | cbe), __int_as_float((__float_as_int(x[e + 1] * GLOWK_ACT_SCALE) & okv) | cbe)};
       xmax = nan_max(nan_max(xmax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));
-      const h2v hi = __builtin_convertvector(v, h2v);                         // (split8's arithmetic)
-      const h2v lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), h2v);
+      h2v hi, lo;                                                             // (split8's arithmetic)
+      split2<false>(v.x, v.y, 1.0f, hi, lo);
       const h2v z = {(_Float16)0.0f, (_Float16)0.0f};
       const h2v sel = seg == 1 ? (TWO ? z : lo) : hi;
       f[t * G + e] = sel[0]; f[t * G + e + 1] = sel[1];
@@ -738,7 +797,7 @@ struct H3Ctx {                      // wave-uniform pointers of the kernel (LDS 
 // acc * sc where the forward pass's ReLU was open
 // (MODE & NET_STORE: training -- the 16 activation values, in the scaled units they are split in, also go to a planar [F][Q] array:
 //  st_blk = wave-uniform base of the hidden block's 32 rows, st_lane = this lane's byte offset, st_row = bytes per row)
-template <int MODE>
+template <int MODE, bool FMA>
 __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned mask, h8 (&bh)[2], h8 (&bl)[2], bool do_st = false,
                                            float* st_blk = nullptr, unsigned st_lane = 0, unsigned st_row = 0, float stu = 1.0f) {
   unsigned bits = 0;
@@ -747,29 +806,27 @@ __device__ __forceinline__ unsigned h3_act(const f32x16& acc, float sc, unsigned
   for (int s = 0; s < 2; ++s) {
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; j += 2) {
+    for (int j = 0; j < 8; ++j) {      // v: the activation BEFORE the scale (sc > 0 commutes with both selections); split8 applies sc
       const int r = 8 * s + j;
-      const f32x2 t2 = f32x2{acc[r], acc[r + 1]} * f32x2{sc, sc};     // v_pk_mul_f32
-      const float t[2] = {t2.x, t2.y};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        if (net_dir<MODE> == NET_BWD) v[j + e] = __int_as_float(__float_as_int(t[e]) & __builtin_amdgcn_sbfe((int)mask, r + e, 1));   // bit ? t : 0
-        else {
-          v[j + e] = fmaxf(t[e], 0.0f);
-          if (net_dir<MODE> == NET_FWD_SAVE) bits |= (acc[r + e] > 0.0f ? 1u : 0u) << (r + e);
-        }
+      if (net_dir<MODE> == NET_BWD) v[j] = __int_as_float(__float_as_int(acc[r]) & __builtin_amdgcn_sbfe((int)mask, r, 1));   // bit ? a : 0
+      else {
+        v[j] = FMA ? relu1(acc[r]) : fmaxf(acc[r] * sc, 0.0f);      // (the chain: scaled here)
+        if (net_dir<MODE> == NET_FWD_SAVE) bits |= (acc[r] > 0.0f ? 1u : 0u) << r;
       }
     }
     if ((MODE & NET_STORE) && do_st) {
       unsigned off = st_lane + (unsigned)(16 * s) * st_row;      // rows 8 (r >> 2) + (r & 3): registers 8 s .. 8 s + 7 = rows 16 s + {0..3, 8..11}
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float sv = net_dir<MODE> == NET_BWD ? v[j] * stu : v[j];      // backward: back in the pixel's own units (NetArgs::bnorm)
+        const float t = FMA || net_dir<MODE> == NET_BWD ? v[j] * sc : v[j];      // (the stored value is the scaled one: one multiply stays)
+        const float sv = net_dir<MODE> == NET_BWD ? t * stu : t;            // backward: back in the pixel's own units (NetArgs::bnorm)
         asm volatile("global_store_dword %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(sv), "s"(st_base) : "memory");
         off += (j == 3 ? 5u : 1u) * st_row;
       }
     }
-    split8(v, bh[s], bl[s]);
+    if constexpr (net_dir<MODE> == NET_BWD) split8<false>(v, sc, bh[s], bl[s]);
+    else if constexpr (FMA) split8<true>(v, sc, bh[s], bl[s]);
+    else split8_chain(v, bh[s], bl[s]);
   }
   return bits;
 }
@@ -815,7 +872,7 @@ __device__ __forceinline__ void h3_X(const NetArgs& a, const H3Ctx& c, int fi, c
     for (int s = 0; s < G::KS; ++s) h1 = mfma3(k1[(2 * s + 0) * 64], k1[(2 * s + 1) * 64], xh[s], xl[s], h1);
   }
   const int stq = (int)c.wblk * 32 + (lane & 31);
-  const unsigned bits = h3_act<MODE>(h1, a.sc1, mask, bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+  const unsigned bits = h3_act<MODE, split_fma<KIN>>(h1, a.sc1, mask, bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
                                      (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                      ((unsigned)(4 * (lane >> 5)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u, c.ub[0]);
   if (net_dir<MODE> == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
@@ -902,7 +959,7 @@ __device__ __forceinline__ void h3_Z(const NetArgs& a, const H3Ctx& c, const flo
     if (ml == 0) {
       unsigned mask = 0;
       if (net_dir<MODE> == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
-      const unsigned bits = h3_act<MODE>(acc2[fo], a.sc2, mask, bh, bl, (MODE & NET_STORE) && qok,
+      const unsigned bits = h3_act<MODE, split_fma<KIN>>(acc2[fo], a.sc2, mask, bh, bl, (MODE & NET_STORE) && qok,
                                          (MODE & NET_STORE) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
                                          ((unsigned)(4 * hh) * (unsigned)a.Q + (unsigned)q) * 4u, (unsigned)a.Q * 4u, c.ub[0]);
       if (net_dir<MODE> == NET_FWD_SAVE && first_group && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
@@ -1056,9 +1113,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
       const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(xmax, a.bnorm, c.ub[0]);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[s][j] *= fac;
-        split8(v[s], xh[s], xl[s]);
+        split8(v[s], fac, xh[s], xl[s]);
       }
     } else {
 #pragma unroll
@@ -1066,7 +1121,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3(NetArgs a) {
         float v[8];
         gather8<KIN, true, SGN>(base, i, j0, a.h, a.w, a.in_stride, qok, 16 * s + 8 * hh, v);
         xmax = range8(xmax, v);
-        split8(v, xh[s], xl[s]);
+        split8(v, 1.0f, xh[s], xl[s]);
       }
     }
   }
@@ -1240,55 +1295,58 @@ __device__ __forceinline__ void c3_presum_group(const f32x4 (&acc3)[NA][2], int 
 // (ST: training -- the 8 values, in the scaled units they are split in, also go to a planar [F][Q] array: rows 4 kq + r of the two
 //  16-row blocks of the hidden block whose base is st_blk; st_lane = byte offset of (row 4 kq, this lane's pixel), st_row = bytes per row)
 // (the values: v = what the split B fragments are made of; returns the ReLU decisions of a saving launch)
-template <int MODE>
+// (v is the activation BEFORE the scale: sc > 0 commutes with the ReLU and with the mask, and h3s_split applies it inside the split)
+// (FMA = false, forward: v is the SCALED activation max(a sc, 0) and h3s_split converts it by the chain)
+template <int MODE, bool FMA>
 __device__ __forceinline__ unsigned h3s_act_vals(const f32x4& r0, const f32x4& r1, float sc, unsigned mask8, float (&v)[8]) {
   unsigned bits = 0;
 #pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    const f32x2 a2 = j < 4 ? f32x2{r0[j], r0[j + 1]} : f32x2{r1[j - 4], r1[j - 3]};
-    const f32x2 t2 = a2 * f32x2{sc, sc};                               // v_pk_mul_f32
-    const float t[2] = {t2.x, t2.y}, av[2] = {a2.x, a2.y};
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      if (MODE == NET_BWD) v[j + e] = __int_as_float(__float_as_int(t[e]) & __builtin_amdgcn_sbfe((int)mask8, j + e, 1));   // bit ? t : 0
-      else {
-        v[j + e] = fmaxf(t[e], 0.0f);
-        if (MODE == NET_FWD_SAVE) bits |= (av[e] > 0.0f ? 1u : 0u) << (j + e);
-      }
+  for (int j = 0; j < 8; ++j) {
+    const float a = j < 4 ? r0[j] : r1[j - 4];
+    if (MODE == NET_BWD) v[j] = __int_as_float(__float_as_int(a) & __builtin_amdgcn_sbfe((int)mask8, j, 1));   // bit ? a : 0
+    else {
+      v[j] = FMA ? relu1(a) : fmaxf(a * sc, 0.0f);
+      if (MODE == NET_FWD_SAVE) bits |= (a > 0.0f ? 1u : 0u) << j;
     }
   }
   return bits;
 }
-template <int MODE, bool ST = false>
+// ... scaled and split: forward values are ReLU outputs (never -0); the two-term mode keeps hi alone
+template <int MODE, bool FMA>
+__device__ __forceinline__ void h3s_split(const float (&v)[8], float sc, h8& bh, h8& bl) {
+  if constexpr (MODE == NET_BWD) split8<false>(v, sc, bh, bl);
+  else if constexpr (MODE == NET_FWD2) split8_hi(v, FMA ? sc : 1.0f, bh, bl);
+  else if constexpr (FMA) split8<true>(v, sc, bh, bl);
+  else split8_chain(v, bh, bl);
+}
+template <int MODE, bool ST, bool FMA>
 __device__ __forceinline__ unsigned h3s_act(const f32x4& r0, const f32x4& r1, float sc, unsigned mask8, h8& bh, h8& bl, bool do_st = false,
                                             float* st_blk = nullptr, unsigned st_lane = 0, unsigned st_row = 0) {
   float v[8];
-  const unsigned bits = h3s_act_vals<MODE>(r0, r1, sc, mask8, v);
+  const unsigned bits = h3s_act_vals<MODE, FMA>(r0, r1, sc, mask8, v);
   if constexpr (ST) {
     if (do_st) {
       const unsigned long long st_base = reinterpret_cast<unsigned long long>(st_blk);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const unsigned off = st_lane + (unsigned)((j >> 2) * 16 + (j & 3)) * st_row;
-        asm volatile("global_store_dword %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(v[j]), "s"(st_base) : "memory");
+        const float t = FMA || MODE == NET_BWD ? v[j] * sc : v[j];      // (the stored value is the scaled one: one multiply stays)
+        asm volatile("global_store_dword %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(t), "s"(st_base) : "memory");
       }
     }
   }
-  if (MODE == NET_FWD2) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { bh[j] = (_Float16)v[j]; bl[j] = (_Float16)0.0f; }
-  } else split8(v, bh, bl);
+  h3s_split<MODE, FMA>(v, sc, bh, bl);
   return bits;
 }
 // ... of BOTH pixel halves of a wave whose lane n holds the ADJACENT pixels 2 n, 2 n + 1 (k_net_h3c's training form): the stored values
 // leave as 8-byte pairs, 16 lanes x 8 B = one full 128-byte line per hidden row and instruction (st_lane: byte offset of (row 4 kq, pixel
 // 2 n)); mask16 / result: bits 8 hf + ..., as the callers of h3s_act assemble them
-template <int MODE, bool ST>
+template <int MODE, bool ST, bool FMA>
 __device__ __forceinline__ unsigned h3s_act_pair(const f32x4& r00, const f32x4& r10, const f32x4& r01, const f32x4& r11, float sc, unsigned mask16,
                                                  h8 (&bh)[2], h8 (&bl)[2], float* st_blk, unsigned st_lane, unsigned st_row) {
   float v0[8], v1[8];
-  unsigned bits = h3s_act_vals<MODE>(r00, r10, sc, mask16, v0);
-  bits |= h3s_act_vals<MODE>(r01, r11, sc, mask16 >> 8, v1) << 8;
+  unsigned bits = h3s_act_vals<MODE, FMA>(r00, r10, sc, mask16, v0);
+  bits |= h3s_act_vals<MODE, FMA>(r01, r11, sc, mask16 >> 8, v1) << 8;
   // (The CU's vector-store path takes ~24 B/clk into L2 and a single wave ~4.5 B/clk, whatever the width per lane: 21 clk per CU / ~110 clk
   //  per wave and 8-byte wave store -- scripts/store_rate_probe.hip.  Issuing the stores two at a time between the conversions below
   //  changed nothing, docs/EXPERIMENTS.md round 4.)
@@ -1297,12 +1355,18 @@ __device__ __forceinline__ unsigned h3s_act_pair(const f32x4& r00, const f32x4& 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const unsigned off = st_lane + (unsigned)((j >> 2) * 16 + (j & 3)) * st_row;
-      const f32x2 pr = {v0[j], v1[j]};
+      const float ss = FMA || MODE == NET_BWD ? sc : 1.0f;
+      const f32x2 pr = {v0[j] * ss, v1[j] * ss};                        // (the stored values are the scaled ones: one multiply each stays)
       asm volatile("global_store_dwordx2 %0, %1, %2" GLOWK_ST_MOD ::"v"(off), "v"(pr), "s"(st_base) : "memory");
     }
   }
-  split8(v0, bh[0], bl[0]);
-  split8(v1, bh[1], bl[1]);
+  if constexpr (MODE == NET_BWD || FMA) {
+    split8<MODE != NET_BWD>(v0, sc, bh[0], bl[0]);
+    split8<MODE != NET_BWD>(v1, sc, bh[1], bl[1]);
+  } else {
+    split8_chain(v0, bh[0], bl[0]);
+    split8_chain(v1, bh[1], bl[1]);
+  }
   return bits;
 }
 
@@ -1360,14 +1424,14 @@ __device__ __forceinline__ void h3s_X(const NetArgs& a, const H3Ctx& c, int fi, 
     static_assert(G::PXH == 2, "pairs: two pixel halves per wave");
     const int stq = (int)c.wblk * 32 + 2 * (lane & 15);
     if constexpr ((MODE & NET_STORE) && PASS == 0)
-      bits = h3s_act_pair<net_dir<MODE>, true>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q),
+      bits = h3s_act_pair<net_dir<MODE>, true, split_fma<KIN>>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q),
                                             ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u);
-    else bits = h3s_act_pair<net_dir<MODE>, false>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, nullptr, 0u, 0u);
+    else bits = h3s_act_pair<net_dir<MODE>, false, split_fma<KIN>>(h1[0][0], h1[1][0], h1[0][1], h1[1][1], a.sc1, mask, bh, bl, nullptr, 0u, 0u);
   } else {
 #pragma unroll
     for (int hf = 0; hf < G::PXH; ++hf) {
       const int stq = (int)c.wblk * (16 * G::PXH) + 16 * hf + (lane & 15);
-      bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0>(h1[0][hf], h1[1][hf], a.sc1, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+      bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0, split_fma<KIN>>(h1[0][hf], h1[1][hf], a.sc1, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
                                                    (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                                    ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u) << (8 * hf);
     }
@@ -1403,11 +1467,11 @@ __device__ __forceinline__ void h3s_X_mma(const h8 (&kf)[G::KSX * 2], const h8 (
       for (int hf = 0; hf < 2; ++hf)
         h1[rb][hf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[s * 2 + rb], x_frag(xh, xl, s, hf), h1[rb][hf], 0, 0, 0);
 }
-template <int MODE7>
+template <int MODE7, bool FMA>
 __device__ __forceinline__ void h3s_X_act(const f32x4 (&h1)[2][2], float sc1, h8 (&bh)[2], h8 (&bl)[2]) {
   static_assert(MODE7 == NET_FWD || MODE7 == NET_FWD2, "plain forward network");
 #pragma unroll
-  for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false>(h1[0][hf], h1[1][hf], sc1, 0u, bh[hf], bl[hf]);
+  for (int hf = 0; hf < 2; ++hf) h3s_act<MODE7, false, FMA>(h1[0][hf], h1[1][hf], sc1, 0u, bh[hf], bl[hf]);
 }
 
 // the four A fragments of group gi of a conv2 chunk / unit (buf: this lane's column of its slot): row block 2 gi hi, lo; row block 2 gi + 1 hi, lo
@@ -1516,7 +1580,7 @@ __device__ __forceinline__ void h3s_Z(const NetArgs& a, const H3Ctx& c, const fl
         if (net_dir<MODE> == NET_BWD) mask = c.mkl[((size_t)(threadIdx.x >> 6) * NF + PASS * NFH + fo) * 64 + lane];   // mask1: the ReLU after conv1
 #pragma unroll
         for (int hf = 0; hf < G::PXH; ++hf)
-          bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && qok[hf],
+          bits |= h3s_act<net_dir<MODE>, (MODE & NET_STORE) != 0, split_fma<KIN>>(acc2[2 * fo][hf], acc2[2 * fo + 1][hf], a.sc2, mask >> (8 * hf), bh[hf], bl[hf], (MODE & NET_STORE) && qok[hf],
                                                        (MODE & NET_STORE) ? uniform_fptr(a.st2 + (size_t)(PASS * NFH + fo) * 32 * a.Q) : nullptr,
                                                        ((unsigned)(4 * kq) * (unsigned)a.Q + (unsigned)q[hf]) * 4u, (unsigned)a.Q * 4u) << (8 * hf);
         if (net_dir<MODE> == NET_FWD_SAVE && t < NFH * G::G0N && c.wok) a.mask2[(c.wblk * NF + PASS * NFH + fo) * 64 + lane] = (unsigned short)bits;
@@ -1802,9 +1866,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
         const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[hf]);     // (training: one scale per launch, BwdArgs::go_scale)
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[s][j] *= fac;
-          split8(v[s], xh[s][hf], xl[s][hf]);
+          split8(v[s], fac, xh[s][hf], xl[s][hf]);
         }
       } else if constexpr (G::STK) {
         xmax = gather_stacked<KIN, SGN, net_dir<MODE> == NET_FWD2, KS, G::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], kq, xh, xl, hf, xmax);
@@ -1814,7 +1876,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3s(NetArgs a) {
           float v[8];
           gather8<KIN, true, SGN>(base, i, j0, a.h, a.w, a.in_stride, qok[hf], 32 * s + 8 * kq, v);
           xmax = range8(xmax, v);
-          split8(v, xh[s][hf], xl[s][hf]);
+          split8(v, 1.0f, xh[s][hf], xl[s][hf]);
         }
       }
     }

@@ -286,6 +286,21 @@ inline F16Codes f16_code_bases(int c, int F) {
   return q;
 }
 
+// The split kernels apply the activation scales of conv1 and conv2 (scales3[0, 1, 3, 4] -> NetArgs::sc1 / sc2) as the multiplicand of the
+// split's fused multiply-adds, which is the same arithmetic as a separate multiply only for a power of two (glowk_kernels.h: split8)
+inline bool split_scale_ok(float s) {
+  int e;
+  return s > 0.0f && std::isfinite(s) && std::frexp(s, &e) == 0.5f;
+}
+inline bool split_scales_ok(const float* scales3, std::string* err) {
+  for (int i : {0, 1, 3, 4})
+    if (!split_scale_ok(scales3[i])) {
+      if (err) *err = "activation scale " + std::to_string(i) + " of the split kernels is not a power of two";
+      return false;
+    }
+  return true;
+}
+
 bool pack_step(const glowk_config& cfg, const Level& lv, int k, float* dst, double* ld_const_out, float* scales3 /* [8]: fwd, bwd scales; fwd, bwd input limits */,
                std::string* err, int* f16_map = nullptr) {
   const int c = lv.c, F = cfg.F, CI = c / 2, CO = c, NF = F / 32, KS1 = (9 * CI) / 2, NMT = (9 * c + 31) / 32;
@@ -728,7 +743,7 @@ bool pack_step(const glowk_config& cfg, const Level& lv, int k, float* dst, doub
       }
     }
   }
-  return true;
+  return split_scales_ok(scales3, err);
 }
 
 

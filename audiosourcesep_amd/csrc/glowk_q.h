@@ -137,7 +137,7 @@ __device__ __forceinline__ void q_X_batch(const NetArgs& a, const H3Ctx& c, cons
     const int fi = B * XB + x;
     const int stq = (int)c.wblk * 16 + (lane & 15);
     h8 bh, bl;
-    const unsigned bits = h3s_act<MODE7, (MODE & NET_STORE) != 0>(h1[x][0], h1[x][1], a.sc1, mask[x], bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
+    const unsigned bits = h3s_act<MODE7, (MODE & NET_STORE) != 0, split_fma<KIN>>(h1[x][0], h1[x][1], a.sc1, mask[x], bh, bl, (MODE & NET_STORE) && PASS == 0 && stq < a.Q,
                                                          (MODE & NET_STORE) ? uniform_fptr(a.st1 + (size_t)fi * 32 * a.Q) : nullptr,
                                                          ((unsigned)(4 * (lane >> 4)) * (unsigned)a.Q + (unsigned)stq) * 4u, (unsigned)a.Q * 4u);
     if (MODE7 == NET_FWD_SAVE && PASS == 0 && c.wok) a.mask1[(c.wblk * NF + fi) * 64 + lane] = (unsigned short)bits;
@@ -335,9 +335,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
       const float fac = (MODE & NET_STORE) ? 1.0f : pixel_norm(pm, a.bnorm, c.ub[0]);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[s][j] *= fac;
-        split8(v[s], xh[s][0], xl[s][0]);
+        split8(v[s], fac, xh[s][0], xl[s][0]);
       }
     } else if constexpr (S::STK) {      // (xh[s] / xl[s] = the B fragments of stacked k-steps 2 s / 2 s + 1)
       xmax = gather_stacked<KIN, SGN, false, KS, S::KSX>(base, i, j0, a.h, a.w, a.in_stride, qok[0], kq, xh, xl, 0, xmax);
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void k_net_h3q(NetArgs a) {
         float v[8];
         gather8<KIN, true, SGN>(base, i, j0, a.h, a.w, a.in_stride, qok[0], 32 * s + 8 * kq, v);
         xmax = range8(xmax, v);
-        split8(v, xh[s][0], xl[s][0]);
+        split8(v, 1.0f, xh[s][0], xl[s][0]);
       }
     }
 #pragma unroll

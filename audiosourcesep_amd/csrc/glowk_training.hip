@@ -740,6 +740,8 @@ int glowk_apply_gradients(glowk_handle* h, const float* grad_dev, int optimizer,
     for (int k = 0; k < cfg.K; ++k) {
       StepDev& d = lv.dev[k];
       const float* q8 = pin_sc(lvl) + (size_t)k * 8;
+      std::string err;      // (the device-side repack, glowk_train.h, writes 2^-S as the host packer does: the split kernels rely on it)
+      if (!split_scales_ok(q8, &err)) return fail("level " + std::to_string(lvl) + " step " + std::to_string(k) + ": " + err);
       if (SL.slotH || SL.slotS) { d.sc1 = q8[0]; d.sc2 = q8[1]; d.sc3 = q8[2]; d.xlim_f = q8[6]; }
       if (SL.slotHB || SL.slotSB) { d.scb1 = q8[3]; d.scb2 = q8[4]; d.scb3 = q8[5]; d.xlim_b = q8[7]; }
     }

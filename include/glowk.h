@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 550
+#define GLOWK_VERSION 551
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -164,6 +164,11 @@ int glowk_range_status(glowk_handle* h, int* tripped, int64_t* fallbacks, void* 
  * diagnostic (bench.py reports it for the trained BASIS priors); off by default. */
 int glowk_range_probe_begin(glowk_handle* h);
 int glowk_range_probe_end(glowk_handle* h, float* fwd_ratio, float* bwd_ratio, void* stream);
+/* The split kernels' activation + fp16 hi/lo split on its own (handle-free; for tests): n fp32 values through the very device helpers
+ * the network kernels inline, hi_dev / lo_dev = the two fp16 halves as bit patterns.  mode 0: max(x, 0) * sc, split (the hidden
+ * activations); 1: the two-term mode, hi only and lo = 0 (f16x2); 2: x * sc, split, no activation (the gathered inputs).  sc must be a
+ * power of two, as every scale the engine hands the kernels is (GLOWK_ERR otherwise).  New in version 551. */
+int glowk_split_probe(const float* x_dev, int n, float sc, int mode, uint16_t* hi_dev, uint16_t* lo_dev, void* stream);
 /* device memory (bytes) the engine allocates for batches up to N: the forward/inverse workspace, plus -- with_grad != 0 --
  * the per-step saves and gradient scratch of glowk_log_prob_grad in the handle's current precision.  glowk_reserve allocates
  * exactly that up front, so that no later compute call of that kind with that batch size (or a smaller one in the same
