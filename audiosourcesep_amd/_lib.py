@@ -172,6 +172,18 @@ SYMBOLS = {
     "glowk_nmf_fit": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "glowk_nmf_divergence": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_nmf_masks": (_i, [_vp, _i, _vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "glowk_iva_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "glowk_iva_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_iva_covariances": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "glowk_iva_ip_update": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "glowk_auxiva_fit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "glowk_ilrma_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_iva_power": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_iva_normalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "glowk_ilrma_fit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "glowk_iva_inverse": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "glowk_iva_demix": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_iva_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

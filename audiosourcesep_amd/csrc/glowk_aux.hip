@@ -7,6 +7,7 @@
 // the 2DFT separation: the 2-D DFT GEMMs, the plane's std and the peak mask (glowk_dft2.h)
 // DUET: the attenuation-delay histogram, its peaks and the assignment of a two-channel STFT (glowk_duet.h)
 // NMF: fused multiplicative updates, the beta divergence and masks of component ranges (glowk_nmf.h)
+// AuxIVA and ILRMA: frame norms, weighted covariances with the iterative projection, demixing and images (glowk_iva.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -22,6 +23,7 @@
 #include "glowk_dft2.h"
 #include "glowk_duet.h"
 #include "glowk_nmf.h"
+#include "glowk_iva.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -1868,6 +1870,367 @@ int glowk_nmf_masks(const float* w_dev, int nw, const float* h_dev, int nsig, in
                      (float2*)spec_dev);
   LAUNCHCHK("k_nmf_masks");
   return 0;
+}
+
+// ---- AuxIVA and ILRMA: blind separation by one demixing matrix per row (glowk_iva.h) ---------------------------------------------------
+namespace {
+struct IvaBuf {
+  const void* p;
+  size_t n;
+};
+// 0 when no written buffer overlaps another buffer of the call (the first `nout` entries are written), null entries skipped
+int iva_disjoint(const std::string& w, std::initializer_list<IvaBuf> bufs, size_t nout) {
+  size_t i = 0;
+  for (const IvaBuf& a : bufs) {
+    size_t j = 0;
+    for (const IvaBuf& b : bufs) {
+      if (j > i && i < nout && a.p && b.p && a.n && b.n && bytes_overlap(a.p, a.n, b.p, b.n)) return fail(w + ": a tensor the call writes overlaps another of its tensors");
+      ++j;
+    }
+    ++i;
+  }
+  return 0;
+}
+int iva_ranges(const std::string& w, int nsig, int M, int rows, int frames) {
+  using namespace glowk_iva;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (M < 2 || M > MAX_M) return fail(w + ": the channel count M must be in [2, 4]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < M || frames > MAX_FRAMES) return fail(w + ": frames must be in [M, 32768] (fewer frames than channels leave the covariances rank-deficient)");
+  if ((int64_t)nsig * M * rows * frames > (int64_t)INT32_MAX) return fail(w + ": nsig * M * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int iva_rows_only(const std::string& w, int nsig, int M, int rows) {
+  using namespace glowk_iva;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (M < 2 || M > MAX_M) return fail(w + ": the channel count M must be in [2, 4]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  return 0;
+}
+int iva_factors(const std::string& w, int nsig, int M, int rows, int frames, int K) {
+  using namespace glowk_iva;
+  if (K < 1 || K > MAX_K) return fail(w + ": K must be in [1, 128]");
+  if ((int64_t)nsig * M > MAX_SIG) return fail(w + ": nsig * M must be at most 65535 (the factors are a batch of nsig * M spectrograms)");
+  if ((int64_t)nsig * M * rows * K > (int64_t)INT32_MAX || (int64_t)nsig * M * K * frames > (int64_t)INT32_MAX)
+    return fail(w + ": the factors must have at most 2^31 - 1 elements each");
+  return 0;
+}
+int iva_aligned(const std::string& w, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p % 8) return fail(w + ": the tensors must be aligned to 8 bytes");
+  return 0;
+}
+size_t iva_bytes_x(int nsig, int M, int rows, int frames) { return (size_t)nsig * M * rows * frames * 8; }
+size_t iva_bytes_w(int nsig, int M, int rows) { return (size_t)nsig * rows * M * M * 16; }
+// work_dev of the AuxIVA calls: the partial norms, phi [nsig][M][frames], lambda [nsig][M]; all doubles
+size_t iva_work_doubles(int nsig, int M, int rows, int frames) {
+  return glowk_iva::partial_doubles(nsig, M, rows, frames) + (size_t)nsig * M * frames + (size_t)nsig * M;
+}
+
+#define GLOWK_IVA_EACH_M(X) X(2) X(3) X(4)
+
+int iva_launch_norms(const float* x, const double* w, int nsig, int M, int rows, int frames, double* partial, hipStream_t st) {
+  using namespace glowk_iva;
+  const RowPlan rp = row_plan(rows);
+  const dim3 grid((unsigned)((int64_t)nsig * rp.nrb * frame_chunks(frames)));
+  switch (M) {
+#define GLOWK_CASE(m) case m: hipLaunchKernelGGL(k_iva_norms<m>, grid, dim3(THREADS), 0, st, (const float2*)x, w, rows, frames, rp, partial); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_norms");
+  return 0;
+}
+int iva_launch_phi(const double* partial, int nsig, int M, int rows, int frames, int model, double* phi, hipStream_t st) {
+  using namespace glowk_iva;
+  const int64_t total = (int64_t)nsig * M * frames;
+  hipLaunchKernelGGL(k_iva_phi, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, partial, total, M, rows, frames, row_plan(rows).nrb, model, phi);
+  LAUNCHCHK("k_iva_phi");
+  return 0;
+}
+// the covariances with phi (cw.phi) or the factors, followed by the row updates of w (v_out null) or stored to v_out (w null)
+int iva_launch_cov(const float* x, const glowk_iva::CovWeights& cw, int nsig, int M, int rows, int frames, double* w, double* v_out, hipStream_t st) {
+  using namespace glowk_iva;
+  const dim3 grid((unsigned)((int64_t)nsig * rows)), block(THREADS);
+  const float2* xc = (const float2*)x;
+  const int form = (cw.phi ? 0 : 2) + (v_out ? 0 : 1);
+  switch (M * 4 + form) {
+#define GLOWK_CASE(m)                                                                                                    \
+  case m * 4 + 0: hipLaunchKernelGGL((k_iva_cov<m, 0, false>), grid, block, 0, st, xc, cw, rows, frames, w, v_out); break; \
+  case m * 4 + 1: hipLaunchKernelGGL((k_iva_cov<m, 0, true>), grid, block, 0, st, xc, cw, rows, frames, w, v_out); break;  \
+  case m * 4 + 2: hipLaunchKernelGGL((k_iva_cov<m, 1, false>), grid, block, 0, st, xc, cw, rows, frames, w, v_out); break; \
+  case m * 4 + 3: hipLaunchKernelGGL((k_iva_cov<m, 1, true>), grid, block, 0, st, xc, cw, rows, frames, w, v_out); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_cov");
+  return 0;
+}
+int iva_launch_power(const float* x, const double* w, int nsig, int M, int rows, int frames, float* P, hipStream_t st) {
+  using namespace glowk_iva;
+  const dim3 grid((unsigned)((int64_t)nsig * rows * frame_chunks(frames)));
+  switch (M) {
+#define GLOWK_CASE(m) case m: hipLaunchKernelGGL(k_iva_power<m>, grid, dim3(THREADS), 0, st, (const float2*)x, w, rows, frames, P); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_power");
+  return 0;
+}
+// lambda from the refreshed y, then W's rows and the basis scaled: four launches
+int iva_launch_normalize(const float* x, double* w, float* basis, int nsig, int M, int rows, int frames, int K, double* work, hipStream_t st) {
+  using namespace glowk_iva;
+  double* partial = work;
+  double* r = work + partial_doubles(nsig, M, rows, frames);
+  double* lam = r + (size_t)nsig * M * frames;
+  if (int rc = iva_launch_norms(x, w, nsig, M, rows, frames, partial, st)) return rc;
+  if (int rc = iva_launch_phi(partial, nsig, M, rows, frames, MODEL_SUM, r, st)) return rc;
+  hipLaunchKernelGGL(k_iva_lambda, dim3((unsigned)(nsig * M)), dim3(THREADS), 0, st, (const double*)r, rows, frames, lam);
+  LAUNCHCHK("k_iva_lambda");
+  const int64_t nw = (int64_t)nsig * rows * M * M, nb = (int64_t)nsig * M * rows * K;
+  hipLaunchKernelGGL(k_iva_scale, dim3((unsigned)((nw + nb + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const double*)lam, nw, nb, M, rows, K, w, basis);
+  LAUNCHCHK("k_iva_scale");
+  return 0;
+}
+int iva_launch_demix(const float* x, const double* w, const double* winv, int nsig, int M, int rows, int frames, float* y, float* img, hipStream_t st) {
+  using namespace glowk_iva;
+  const dim3 grid((unsigned)((int64_t)nsig * rows * frame_chunks(frames)));
+  switch (M) {
+#define GLOWK_CASE(m) \
+  case m: hipLaunchKernelGGL(k_iva_demix<m>, grid, dim3(THREADS), 0, st, (const float2*)x, w, winv, rows, frames, (float2*)y, (float2*)img); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_demix");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_iva_workspace_bytes(int nsig, int M, int rows, int frames) {
+  if (iva_ranges("iva_workspace_bytes", nsig, M, rows, frames)) return 0;
+  return iva_work_doubles(nsig, M, rows, frames) * 8;
+}
+
+size_t glowk_ilrma_workspace_bytes(int nsig, int M, int rows, int frames, int K) {
+  if (iva_ranges("ilrma_workspace_bytes", nsig, M, rows, frames) || iva_factors("ilrma_workspace_bytes", nsig, M, rows, frames, K)) return 0;
+  if (nmf_ranges("ilrma_workspace_bytes", nsig * M, rows, frames, K)) return 0;
+  const size_t p = ((size_t)nsig * M * rows * frames * 4 + 7) / 8 * 8;
+  return iva_work_doubles(nsig, M, rows, frames) * 8 + p + (glowk_nmf::nmf_work_bytes(nsig * M, rows, frames, K) + 7) / 8 * 8;
+}
+
+int glowk_iva_weights(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, int model, double* phi_dev, void* work_dev,
+                      size_t work_bytes, void* stream) {
+  const std::string me("iva_weights");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (model != glowk_iva::MODEL_LAPLACE && model != glowk_iva::MODEL_GAUSS) return fail(me + ": model must be 0 (laplace) or 1 (gauss)");
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !phi_dev || !work_dev) return fail("null tensor");
+  const size_t need = iva_work_doubles(nsig, M, rows, frames) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_iva_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, phi_dev, work_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{phi_dev, (size_t)nsig * M * frames * 8}, {work_dev, need}, {x_dev, iva_bytes_x(nsig, M, rows, frames)}, {w_dev, iva_bytes_w(nsig, M, rows)}}, 2))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, phi_dev, work_dev}, &dev, "iva_weights")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = iva_launch_norms(x_dev, w_dev, nsig, M, rows, frames, (double*)work_dev, st)) return rc;
+  return iva_launch_phi((const double*)work_dev, nsig, M, rows, frames, model, phi_dev, st);
+}
+
+int glowk_iva_covariances(const float* x_dev, int nsig, int M, int rows, int frames, const double* phi_dev, const float* basis_dev, const float* act_dev,
+                          int K, double* v_dev, void* stream) {
+  const std::string me("iva_covariances");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if ((phi_dev != nullptr) == (basis_dev != nullptr || act_dev != nullptr)) return fail(me + ": give either phi_dev or both factors");
+  if (!phi_dev && (!basis_dev || !act_dev)) return fail(me + ": the factors are given together");
+  if (!phi_dev)
+    if (int rc = iva_factors(me, nsig, M, rows, frames, K)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !v_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, phi_dev, v_dev})) return rc;
+  if ((uintptr_t)basis_dev % 4 || (uintptr_t)act_dev % 4) return fail(me + ": the factors must be aligned to 4 bytes");
+  const size_t nv = iva_bytes_w(nsig, M, rows) * M;
+  if (int rc = iva_disjoint(me, {{v_dev, nv}, {x_dev, iva_bytes_x(nsig, M, rows, frames)}, {phi_dev, (size_t)nsig * M * frames * 8},
+                                 {basis_dev, phi_dev ? 0 : (size_t)nsig * M * rows * K * 4}, {act_dev, phi_dev ? 0 : (size_t)nsig * M * K * frames * 4}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, phi_dev, basis_dev, act_dev, v_dev}, &dev, "iva_covariances")) return rc;
+  DeviceGuard dg(dev);
+  const glowk_iva::CovWeights cw = {phi_dev, basis_dev, act_dev, phi_dev ? 0 : K};
+  return iva_launch_cov(x_dev, cw, nsig, M, rows, frames, nullptr, v_dev, (hipStream_t)stream);
+}
+
+int glowk_iva_ip_update(double* w_dev, const double* v_dev, int nsig, int M, int rows, void* stream) {
+  using namespace glowk_iva;
+  const std::string me("iva_ip_update");
+  if (int rc = iva_rows_only(me, nsig, M, rows)) return rc;
+  if (nsig == 0) return 0;
+  if (!w_dev || !v_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {w_dev, v_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{w_dev, iva_bytes_w(nsig, M, rows)}, {v_dev, iva_bytes_w(nsig, M, rows) * M}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({w_dev, v_dev}, &dev, "iva_ip_update")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t total = (int64_t)nsig * rows;
+  const dim3 grid((unsigned)((total + 63) / 64));
+  switch (M) {
+#define GLOWK_CASE(m) case m: hipLaunchKernelGGL(k_iva_ip<m>, grid, dim3(64), 0, (hipStream_t)stream, w_dev, v_dev, total); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_ip");
+  return 0;
+}
+
+int glowk_auxiva_fit(const float* x_dev, double* w_dev, int nsig, int M, int rows, int frames, int model, int n_iter, void* work_dev, size_t work_bytes,
+                     void* stream) {
+  using namespace glowk_iva;
+  const std::string me("auxiva_fit");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (model != MODEL_LAPLACE && model != MODEL_GAUSS) return fail(me + ": model must be 0 (laplace) or 1 (gauss)");
+  if (n_iter < 0 || n_iter > 100000) return fail(me + ": n_iter must be in [0, 100000]");
+  if (nsig == 0 || n_iter == 0) return 0;
+  if (!x_dev || !w_dev || !work_dev) return fail("null tensor");
+  const size_t need = iva_work_doubles(nsig, M, rows, frames) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_iva_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, work_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{w_dev, iva_bytes_w(nsig, M, rows)}, {work_dev, need}, {x_dev, iva_bytes_x(nsig, M, rows, frames)}}, 2)) return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, work_dev}, &dev, "auxiva_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)work_dev;
+  double* phi = partial + partial_doubles(nsig, M, rows, frames);
+  const CovWeights cw = {phi, nullptr, nullptr, 0};
+  for (int it = 0; it < n_iter; ++it) {
+    if (int rc = iva_launch_norms(x_dev, w_dev, nsig, M, rows, frames, partial, st)) return rc;
+    if (int rc = iva_launch_phi(partial, nsig, M, rows, frames, model, phi, st)) return rc;
+    if (int rc = iva_launch_cov(x_dev, cw, nsig, M, rows, frames, w_dev, nullptr, st)) return rc;
+  }
+  return 0;
+}
+
+int glowk_iva_power(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, float* p_dev, void* stream) {
+  const std::string me("iva_power");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !p_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, w_dev})) return rc;
+  if ((uintptr_t)p_dev % 4) return fail(me + ": p_dev must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{p_dev, iva_bytes_x(nsig, M, rows, frames) / 2}, {x_dev, iva_bytes_x(nsig, M, rows, frames)}, {w_dev, iva_bytes_w(nsig, M, rows)}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, p_dev}, &dev, "iva_power")) return rc;
+  DeviceGuard dg(dev);
+  return iva_launch_power(x_dev, w_dev, nsig, M, rows, frames, p_dev, (hipStream_t)stream);
+}
+
+int glowk_iva_normalize(const float* x_dev, double* w_dev, float* basis_dev, int nsig, int M, int rows, int frames, int K, void* work_dev, size_t work_bytes,
+                        void* stream) {
+  const std::string me("iva_normalize");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (int rc = iva_factors(me, nsig, M, rows, frames, K)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !basis_dev || !work_dev) return fail("null tensor");
+  const size_t need = iva_work_doubles(nsig, M, rows, frames) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_iva_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, work_dev})) return rc;
+  if ((uintptr_t)basis_dev % 4) return fail(me + ": basis_dev must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{w_dev, iva_bytes_w(nsig, M, rows)}, {basis_dev, (size_t)nsig * M * rows * K * 4}, {work_dev, need},
+                                 {x_dev, iva_bytes_x(nsig, M, rows, frames)}}, 3))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, basis_dev, work_dev}, &dev, "iva_normalize")) return rc;
+  DeviceGuard dg(dev);
+  return iva_launch_normalize(x_dev, w_dev, basis_dev, nsig, M, rows, frames, K, (double*)work_dev, (hipStream_t)stream);
+}
+
+int glowk_ilrma_fit(const float* x_dev, double* w_dev, float* basis_dev, float* act_dev, int nsig, int M, int rows, int frames, int K, int n_iter,
+                    void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_iva;
+  const std::string me("ilrma_fit");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (int rc = iva_factors(me, nsig, M, rows, frames, K)) return rc;
+  if (int rc = nmf_ranges(me, nsig * M, rows, frames, K)) return rc;
+  if (n_iter < 0 || n_iter > 100000) return fail(me + ": n_iter must be in [0, 100000]");
+  if (nsig == 0 || n_iter == 0) return 0;
+  if (!x_dev || !w_dev || !basis_dev || !act_dev || !work_dev) return fail("null tensor");
+  const size_t iva_b = iva_work_doubles(nsig, M, rows, frames) * 8, p_b = ((size_t)nsig * M * rows * frames * 4 + 7) / 8 * 8;
+  const size_t nmf_b = glowk_nmf::nmf_work_bytes(nsig * M, rows, frames, K), need = iva_b + p_b + (nmf_b + 7) / 8 * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_ilrma_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, work_dev})) return rc;
+  if ((uintptr_t)basis_dev % 4 || (uintptr_t)act_dev % 4) return fail(me + ": the factors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{w_dev, iva_bytes_w(nsig, M, rows)}, {basis_dev, (size_t)nsig * M * rows * K * 4}, {act_dev, (size_t)nsig * M * K * frames * 4},
+                                 {work_dev, need}, {x_dev, iva_bytes_x(nsig, M, rows, frames)}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, basis_dev, act_dev, work_dev}, &dev, "ilrma_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  double* work = (double*)work_dev;
+  float* P = (float*)((char*)work_dev + iva_b);
+  void* nmf_work = (char*)work_dev + iva_b + p_b;
+  const CovWeights cw = {nullptr, basis_dev, act_dev, K};
+  for (int it = 0; it < n_iter; ++it) {
+    if (int rc = iva_launch_power(x_dev, w_dev, nsig, M, rows, frames, P, st)) return rc;
+    if (int rc = glowk_nmf_fit(P, nsig * M, rows, frames, basis_dev, nsig * M, act_dev, K, 0, 1, 1, nmf_work, nmf_b, stream)) return rc;
+    if (int rc = iva_launch_cov(x_dev, cw, nsig, M, rows, frames, w_dev, nullptr, st)) return rc;
+    if (int rc = iva_launch_normalize(x_dev, w_dev, basis_dev, nsig, M, rows, frames, K, work, st)) return rc;
+  }
+  return 0;
+}
+
+int glowk_iva_inverse(const double* w_dev, int nsig, int M, int rows, double* winv_dev, void* stream) {
+  using namespace glowk_iva;
+  const std::string me("iva_inverse");
+  if (int rc = iva_rows_only(me, nsig, M, rows)) return rc;
+  if (nsig == 0) return 0;
+  if (!w_dev || !winv_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {w_dev, winv_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{winv_dev, iva_bytes_w(nsig, M, rows)}, {w_dev, iva_bytes_w(nsig, M, rows)}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({w_dev, winv_dev}, &dev, "iva_inverse")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t total = (int64_t)nsig * rows;
+  const dim3 grid((unsigned)((total + 63) / 64));
+  switch (M) {
+#define GLOWK_CASE(m) case m: hipLaunchKernelGGL(k_iva_inverse<m>, grid, dim3(64), 0, (hipStream_t)stream, w_dev, total, winv_dev); break;
+    GLOWK_IVA_EACH_M(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_iva_inverse");
+  return 0;
+}
+
+int glowk_iva_demix(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, float* y_dev, void* stream) {
+  const std::string me("iva_demix");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !y_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, y_dev})) return rc;
+  const size_t nx = iva_bytes_x(nsig, M, rows, frames);
+  if (int rc = iva_disjoint(me, {{y_dev, nx}, {x_dev, nx}, {w_dev, iva_bytes_w(nsig, M, rows)}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, y_dev}, &dev, "iva_demix")) return rc;
+  DeviceGuard dg(dev);
+  return iva_launch_demix(x_dev, w_dev, nullptr, nsig, M, rows, frames, y_dev, nullptr, (hipStream_t)stream);
+}
+
+int glowk_iva_images(const float* x_dev, const double* w_dev, const double* winv_dev, int nsig, int M, int rows, int frames, float* y_dev, float* img_dev,
+                     void* stream) {
+  const std::string me("iva_images");
+  if (int rc = iva_ranges(me, nsig, M, rows, frames)) return rc;
+  if ((int64_t)nsig * M * M * rows * frames > (int64_t)INT32_MAX) return fail(me + ": nsig * M * M * rows * frames must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !winv_dev || !img_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, winv_dev, y_dev, img_dev})) return rc;
+  const size_t nx = iva_bytes_x(nsig, M, rows, frames), nw = iva_bytes_w(nsig, M, rows);
+  if (int rc = iva_disjoint(me, {{img_dev, nx * M}, {y_dev, nx}, {x_dev, nx}, {w_dev, nw}, {winv_dev, nw}}, 2)) return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, winv_dev, y_dev, img_dev}, &dev, "iva_images")) return rc;
+  DeviceGuard dg(dev);
+  return iva_launch_demix(x_dev, w_dev, winv_dev, nsig, M, rows, frames, y_dev, img_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 551
+#define GLOWK_VERSION 552
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -823,6 +823,69 @@ int glowk_nmf_masks(const float* w_dev, int nw, const float* h_dev, int nsig, in
                     int num_sources, int power, const float* x_dev /* [nsig][C][rows][frames] complex64, or null */, int channels,
                     float* mask_dev /* [nsig][S][rows][frames] */, float* spec_dev /* [nsig][S][C][rows][frames] complex64, or null */,
                     void* stream);
+
+/* --- AuxIVA and ILRMA: blind separation of M channels by one demixing matrix per row (Ono 2011; Kitamura et al. 2016; glowk_iva.h) -- */
+/* X [nsig][M][rows][frames] complex64 (re, im interleaved), the STFT of M channels; W [nsig][rows][M][M] complex128, row k of W_f is
+ * w_{k,f}^H; y_k(f, t) = sum_m W_f[k][m] X[m][f][t], m ascending.  M in [2, 4], frames in [M, 32768] (fewer frames than channels make
+ * every weighted covariance rank-deficient), rows in [1, 4096], nsig in [0, 65535] (0: a successful no-op), nsig M rows frames <=
+ * 2^31 - 1.  FLOOR = 2^-40.  Everything after the load of X is fp64 without contraction; every sum has an order that the shapes fix
+ * (the rows in at most 32 blocks of ceil(rows / min(ceil(rows / 32), 32)) rows, block after block; the frames t = i, i + 256, .. per
+ * thread i, the 64 lanes of a wave by halving, the four waves in order; the sums behind r_k(t) and lambda_k Neumaier-compensated per
+ * thread); no atomics, no allocation, no host synchronisation: bitwise
+ * reproducible, and a batch gives what its signals give alone.  The conventions are those of the NMF section: handle-free, device
+ * memory on one device, GLOWK_ERR with a glowk_last_error message before anything is launched; tensors the call writes must not
+ * overlap its other tensors; 8-byte alignment (float32 tensors 4).  audiosourcesep_amd/iva.py drives the calls.  Since version 552.
+ *
+ * Weights (model 0 = laplace, 1 = gauss): r_k(t) = sum_f |y_k(f, t)|^2; phi_k(t) = 1 / max(sqrt(r_k(t)), FLOOR) for laplace and
+ * 1 / max(r_k(t) / rows, FLOOR) for gauss.  ILRMA's weights are phi_k(f, t) = 1 / max(rho_k(f, t), FLOOR), rho_k(f, t) = sum_l
+ * basis[k][f][l] act[k][l][t] in fp64 from the float32 factors, l ascending.
+ * Covariances: V_k(f) = (1 / frames) sum_t phi_k x(f, t) x(f, t)^H, Hermitian, stored as full matrices [nsig][rows][M(k)][M][M].
+ * Iterative projection, per row, k = 0 .. M - 1 in order with rows < k already replaced: u = (W_f V_k(f))^-1 e_k by Gaussian
+ * elimination with partial pivoting, d = Re(u^H V_k(f) u); where every component of u and d is finite and d > 0, row k of W_f becomes
+ * (u / sqrt(d))^H, else it stays.  All V_k of one iteration come from the weights at the iteration's start.
+ * Error of one iteration fed the same W, per row: max |dW_f| <= 2^-53 (frames + 64 M) (1 + c_f) max |W_f|, c_f the largest 2-norm
+ * condition number of W_f V_k(f) over k (the frame sum, then the M x M solve). */
+/* work_dev of glowk_iva_weights, glowk_auxiva_fit and glowk_iva_normalize: 8 (nsig nrb M frames + nsig M frames + nsig M) bytes, nrb the
+ * number of row blocks above.  0 for arguments out of range. */
+size_t glowk_iva_workspace_bytes(int nsig, int M, int rows, int frames);
+/* phi [nsig][M][frames] float64 from X and W.  Two launches: the partial norms per row block, then their sum and the model. */
+int glowk_iva_weights(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, int model, double* phi_dev, void* work_dev,
+                      size_t work_bytes, void* stream);
+/* V [nsig][rows][M][M][M] complex128 from X and either phi_dev [nsig][M][frames] (basis_dev and act_dev null, K ignored) or the factors
+ * basis_dev [nsig][M][rows][K] and act_dev [nsig][M][K][frames], float32, K in [1, 128] (phi_dev null).  One launch, one workgroup
+ * per row. */
+int glowk_iva_covariances(const float* x_dev, int nsig, int M, int rows, int frames, const double* phi_dev, const float* basis_dev,
+                          const float* act_dev, int K, double* v_dev, void* stream);
+/* The M sequential row updates of every W_f, in place, from stored covariances.  One launch. */
+int glowk_iva_ip_update(double* w_dev, const double* v_dev, int nsig, int M, int rows, void* stream);
+/* n_iter AuxIVA iterations in place on W: weights, covariances and iterative projection, the covariances never stored.  Three launches
+ * per iteration; n_iter in [0, 100000].  Bit for bit n_iter times glowk_iva_weights, glowk_iva_covariances, glowk_iva_ip_update. */
+int glowk_auxiva_fit(const float* x_dev, double* w_dev, int nsig, int M, int rows, int frames, int model, int n_iter, void* work_dev,
+                     size_t work_bytes, void* stream);
+/* ILRMA.  One iteration: (1) P_k = |y_k|^2, rounded once to float32 (glowk_iva_power); (2) one Itakura-Saito iteration of
+ * glowk_nmf_fit (beta 0, update_w 1) on P as a batch of nsig M spectrograms, bit for bit; (3, 4) the covariances with the factors'
+ * weights and the iterative projection; (5) with y refreshed, lambda_k = sqrt(mean_{f,t} |y_k|^2) (the sum in the orders above);
+ * where lambda_k is finite and positive, row k of every W_f is divided by lambda_k and basis_k by lambda_k^2 (in fp64, rounded once
+ * to float32) (glowk_iva_normalize: four launches).  nsig M <= 65535.  Nine launches per iteration.
+ * glowk_ilrma_workspace_bytes: glowk_iva_workspace_bytes + 4 nsig M rows frames + glowk_nmf_workspace_bytes(nsig M, rows, frames, K),
+ * each rounded up to 8 bytes; 0 out of range. */
+size_t glowk_ilrma_workspace_bytes(int nsig, int M, int rows, int frames, int K);
+int glowk_iva_power(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, float* p_dev /* [nsig][M][rows][frames] */,
+                    void* stream);
+int glowk_iva_normalize(const float* x_dev, double* w_dev, float* basis_dev, int nsig, int M, int rows, int frames, int K, void* work_dev,
+                        size_t work_bytes, void* stream);
+int glowk_ilrma_fit(const float* x_dev, double* w_dev, float* basis_dev, float* act_dev, int nsig, int M, int rows, int frames, int K, int n_iter,
+                    void* work_dev, size_t work_bytes, void* stream);
+/* Output.  glowk_iva_inverse: W_f^-1 by Gauss-Jordan elimination with partial pivoting, [nsig][rows][M][M] complex128; a row whose
+ * inverse has a non-finite entry gets an all-zero matrix.  glowk_iva_demix: Y = W X, complex64 [nsig][M][rows][frames], each
+ * component rounded once.  glowk_iva_images: img[sig][k][m][f][t] = W_f^-1[m][k] y_k(f, t) with y_k the complex64 value demix stores,
+ * the product in fp64, rounded once; complex64 [nsig][M][M][rows][frames] (source, then channel; nsig M M rows frames <= 2^31 - 1), the
+ * minimal-distortion projection: the images of one cell add up to X, and are all zero in a row without a finite inverse.  y_dev may
+ * be null; one pass over X, one launch each. */
+int glowk_iva_inverse(const double* w_dev, int nsig, int M, int rows, double* winv_dev, void* stream);
+int glowk_iva_demix(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, float* y_dev, void* stream);
+int glowk_iva_images(const float* x_dev, const double* w_dev, const double* winv_dev, int nsig, int M, int rows, int frames,
+                     float* y_dev /* may be null */, float* img_dev, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
