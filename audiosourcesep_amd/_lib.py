@@ -184,6 +184,15 @@ SYMBOLS = {
     "glowk_iva_inverse": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "glowk_iva_demix": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "glowk_iva_images": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "glowk_melody_positions": (_i, [_vp, _i, _i, _d, _i, _vp, _vp]),
+    "glowk_melody_emission_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_melody_track_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_melody_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_melody_salience": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "glowk_melody_emission": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_melody_track": (_i, [_vp, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_melody_mask": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _d, _d, _vp, _vp]),
+    "glowk_melody_fit": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@
 #include "glowk_duet.h"
 #include "glowk_nmf.h"
 #include "glowk_iva.h"
+#include "glowk_melody.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -2231,6 +2232,201 @@ int glowk_iva_images(const float* x_dev, const double* w_dev, const double* winv
   if (int rc = audio_device({x_dev, w_dev, winv_dev, y_dev, img_dev}, &dev, "iva_images")) return rc;
   DeviceGuard dg(dev);
   return iva_launch_demix(x_dev, w_dev, winv_dev, nsig, M, rows, frames, y_dev, img_dev, (hipStream_t)stream);
+}
+
+// ---- melody: harmonic salience, a Viterbi f0 track, a harmonic comb mask (glowk_melody.h) ------------------------------------------------
+namespace {
+int mel_sizes(const std::string& w, int nsig, int rows, int frames, int B) {
+  using namespace glowk_melody;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < MIN_ROWS || rows > MAX_ROWS) return fail(w + ": rows must be in [2, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (B < 1 || B > MAX_BINS) return fail(w + ": the number of f0 bins B must be in [1, 1024]");
+  if (!sizes_ok(nsig, rows, frames, B)) return fail(w + ": nsig * rows * frames and nsig * (B + 1) * frames must be at most 2^31 - 1");
+  return 0;
+}
+int mel_harm(const std::string& w, int H) {
+  if (H < 1 || H > glowk_melody::MAX_HARM) return fail(w + ": the number of harmonics H must be in [1, 32]");
+  return 0;
+}
+int mel_track_params(const std::string& w, int J, double theta, double nu) {
+  if (J < 0 || J > glowk_melody::MAX_JUMP) return fail(w + ": max_jump J must be in [0, 1023]");
+  if (!std::isfinite(theta) || !std::isfinite(nu)) return fail(w + ": threshold and voicing_penalty must be finite");
+  return 0;
+}
+int mel_mask_params(const std::string& w, int Hm, double width, double bin_hz) {
+  if (Hm < 1 || Hm > glowk_melody::MAX_MASK_HARM) return fail(w + ": n_harmonics Hm must be in [1, 1024]");
+  if (!(std::isfinite(width) && width > 0)) return fail(w + ": width must be finite and positive");
+  if (!(std::isfinite(bin_hz) && bin_hz > 0)) return fail(w + ": bin_hz must be finite and positive");
+  return 0;
+}
+size_t mel_bytes_s(int nsig, int rows, int frames) { return (size_t)nsig * rows * frames * 4; }
+
+int mel_launch_salience(const float* s, int nsig, int rows, int frames, const int32_t* idx, const double* frac, const double* w, int B, int H, float* sal,
+                        hipStream_t st) {
+  using namespace glowk_melody;
+  const int blocks = sal_blocks(B, frames);
+  hipLaunchKernelGGL(k_melody_salience, dim3((unsigned)((int64_t)nsig * blocks)), dim3(SAL_THREADS), 0, st, s, rows, frames, idx, frac, w, B, H, blocks, sal);
+  LAUNCHCHK("k_melody_salience");
+  return 0;
+}
+int mel_launch_emission(const float* sal, int nsig, int B, int frames, double* e, float* m, float* partial, hipStream_t st) {
+  using namespace glowk_melody;
+  const int64_t cells = (int64_t)B * frames;
+  const int groups = emi_groups(cells), blocks = emi_blocks(cells);
+  hipLaunchKernelGGL(k_melody_max, dim3((unsigned)((int64_t)nsig * groups)), dim3(EMI_THREADS), 0, st, sal, cells, groups, partial);
+  LAUNCHCHK("k_melody_max");
+  hipLaunchKernelGGL(k_melody_emission, dim3((unsigned)((int64_t)nsig * blocks)), dim3(EMI_THREADS), 0, st, sal, cells, groups, blocks,
+                     (const float*)partial, e, m);
+  LAUNCHCHK("k_melody_emission");
+  return 0;
+}
+int mel_launch_track(const double* e, int nsig, int B, int frames, const double* pen, int J, double theta, double nu, void* bp, int32_t* path, int64_t* ticks,
+                     hipStream_t st) {
+  using namespace glowk_melody;
+  hipLaunchKernelGGL(k_melody_track, dim3((unsigned)nsig), dim3(trk_threads(B)), 0, st, e, B, frames, pen, J, theta, nu, (uint16_t*)bp, path, ticks);
+  LAUNCHCHK("k_melody_track");
+  return 0;
+}
+int mel_launch_mask(const int32_t* path, int nsig, int frames, const double* f0, int B, int rows, int Hm, double width, double bin_hz, float* mask,
+                    hipStream_t st) {
+  using namespace glowk_melody;
+  const int blocks = msk_blocks(rows, frames);
+  hipLaunchKernelGGL(k_melody_mask, dim3((unsigned)((int64_t)nsig * blocks)), dim3(MSK_THREADS), 0, st, path, frames, f0, B, rows, Hm, width, bin_hz, blocks,
+                     mask);
+  LAUNCHCHK("k_melody_mask");
+  return 0;
+}
+}  // namespace
+
+int glowk_melody_positions(const double* f0_host, int B, int H, double bin_hz, int rows, int32_t* idx_host, double* frac_host) {
+  using namespace glowk_melody;
+  const std::string me("melody_positions");
+  if (B < 1 || B > MAX_BINS) return fail(me + ": the number of f0 bins B must be in [1, 1024]");
+  if (int rc = mel_harm(me, H)) return rc;
+  if (rows < MIN_ROWS || rows > MAX_ROWS) return fail(me + ": rows must be in [2, 4096]");
+  if (!f0_host || !idx_host || !frac_host) return fail("null tensor");
+  if (!grid_ok(f0_host, B, bin_hz)) return fail(me + ": f0 must be finite, positive and strictly ascending, bin_hz finite and positive");
+  positions(f0_host, B, H, bin_hz, rows, idx_host, frac_host);
+  return 0;
+}
+
+size_t glowk_melody_emission_workspace_bytes(int nsig, int B, int frames) {
+  if (nsig < 1 || !glowk_melody::sizes_ok(nsig, glowk_melody::MIN_ROWS, frames, B)) return 0;
+  return glowk_melody::emi_work_bytes(nsig, B, frames);
+}
+size_t glowk_melody_track_workspace_bytes(int nsig, int B, int frames) {
+  if (nsig < 1 || !glowk_melody::sizes_ok(nsig, glowk_melody::MIN_ROWS, frames, B)) return 0;
+  return glowk_melody::trk_work_bytes(nsig, B, frames);
+}
+size_t glowk_melody_workspace_bytes(int nsig, int B, int frames) {
+  if (nsig < 1 || !glowk_melody::sizes_ok(nsig, glowk_melody::MIN_ROWS, frames, B)) return 0;
+  return glowk_melody::fit_plan(nsig, B, frames).bytes;
+}
+
+int glowk_melody_salience(const float* s_dev, int nsig, int rows, int frames, const int32_t* idx_dev, const double* frac_dev, const double* w_dev, int B, int H,
+                          float* sal_dev, void* stream) {
+  const std::string me("melody_salience");
+  if (int rc = mel_sizes(me, nsig, rows, frames, B)) return rc;
+  if (int rc = mel_harm(me, H)) return rc;
+  if (nsig == 0) return 0;
+  if (!s_dev || !idx_dev || !frac_dev || !w_dev || !sal_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {frac_dev, w_dev})) return rc;
+  if ((uintptr_t)s_dev % 4 || (uintptr_t)idx_dev % 4 || (uintptr_t)sal_dev % 4) return fail(me + ": the float32 and int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{sal_dev, (size_t)nsig * B * frames * 4}, {s_dev, mel_bytes_s(nsig, rows, frames)}, {idx_dev, (size_t)B * H * 4},
+                                 {frac_dev, (size_t)B * H * 8}, {w_dev, (size_t)H * 8}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({s_dev, idx_dev, frac_dev, w_dev, sal_dev}, &dev, "melody_salience")) return rc;
+  DeviceGuard dg(dev);
+  return mel_launch_salience(s_dev, nsig, rows, frames, idx_dev, frac_dev, w_dev, B, H, sal_dev, (hipStream_t)stream);
+}
+
+int glowk_melody_emission(const float* sal_dev, int nsig, int B, int frames, double* e_dev, float* m_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_melody;
+  const std::string me("melody_emission");
+  if (int rc = mel_sizes(me, nsig, MIN_ROWS, frames, B)) return rc;
+  if (nsig == 0) return 0;
+  if (!sal_dev || !e_dev || !m_dev || !work_dev) return fail("null tensor");
+  const size_t need = emi_work_bytes(nsig, B, frames), cells = (size_t)nsig * B * frames;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_melody_emission_workspace_bytes says");
+  if (int rc = iva_aligned(me, {e_dev, work_dev})) return rc;
+  if ((uintptr_t)sal_dev % 4 || (uintptr_t)m_dev % 4) return fail(me + ": the float32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{e_dev, cells * 8}, {m_dev, (size_t)nsig * 4}, {work_dev, need}, {sal_dev, cells * 4}}, 3)) return rc;
+  int dev;
+  if (int rc = audio_device({sal_dev, e_dev, m_dev, work_dev}, &dev, "melody_emission")) return rc;
+  DeviceGuard dg(dev);
+  return mel_launch_emission(sal_dev, nsig, B, frames, e_dev, m_dev, (float*)work_dev, (hipStream_t)stream);
+}
+
+int glowk_melody_track(const double* e_dev, int nsig, int B, int frames, const double* pen_dev, int J, double theta, double nu, int32_t* path_dev,
+                       int64_t* ticks_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_melody;
+  const std::string me("melody_track");
+  if (int rc = mel_sizes(me, nsig, MIN_ROWS, frames, B)) return rc;
+  if (int rc = mel_track_params(me, J, theta, nu)) return rc;
+  if (nsig == 0) return 0;
+  if (!e_dev || !pen_dev || !path_dev || !work_dev) return fail("null tensor");
+  const size_t need = trk_work_bytes(nsig, B, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_melody_track_workspace_bytes says");
+  if (int rc = iva_aligned(me, {e_dev, pen_dev, ticks_dev, work_dev})) return rc;
+  if ((uintptr_t)path_dev % 4) return fail(me + ": path_dev must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{path_dev, (size_t)nsig * frames * 4}, {work_dev, need}, {ticks_dev, (size_t)nsig * 16},
+                                 {e_dev, (size_t)nsig * B * frames * 8}, {pen_dev, (size_t)(J + 1) * 8}}, 3))
+    return rc;
+  int dev;
+  if (int rc = audio_device({e_dev, pen_dev, path_dev, ticks_dev, work_dev}, &dev, "melody_track")) return rc;
+  DeviceGuard dg(dev);
+  return mel_launch_track(e_dev, nsig, B, frames, pen_dev, J, theta, nu, work_dev, path_dev, ticks_dev, (hipStream_t)stream);
+}
+
+int glowk_melody_mask(const int32_t* path_dev, int nsig, int frames, const double* f0_dev, int B, int rows, int Hm, double width, double bin_hz, float* mask_dev,
+                      void* stream) {
+  const std::string me("melody_mask");
+  if (int rc = mel_sizes(me, nsig, rows, frames, B)) return rc;
+  if (int rc = mel_mask_params(me, Hm, width, bin_hz)) return rc;
+  if (nsig == 0) return 0;
+  if (!path_dev || !f0_dev || !mask_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {f0_dev})) return rc;
+  if ((uintptr_t)path_dev % 4 || (uintptr_t)mask_dev % 4) return fail(me + ": the float32 and int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{mask_dev, mel_bytes_s(nsig, rows, frames)}, {path_dev, (size_t)nsig * frames * 4}, {f0_dev, (size_t)B * 8}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({path_dev, f0_dev, mask_dev}, &dev, "melody_mask")) return rc;
+  DeviceGuard dg(dev);
+  return mel_launch_mask(path_dev, nsig, frames, f0_dev, B, rows, Hm, width, bin_hz, mask_dev, (hipStream_t)stream);
+}
+
+int glowk_melody_fit(const float* s_dev, int nsig, int rows, int frames, const int32_t* idx_dev, const double* frac_dev, const double* w_dev,
+                     const double* f0_dev, int B, int H, const double* pen_dev, int J, double theta, double nu, int Hm, double width, double bin_hz,
+                     int32_t* path_dev, float* mask_dev, float* m_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_melody;
+  const std::string me("melody_fit");
+  if (int rc = mel_sizes(me, nsig, rows, frames, B)) return rc;
+  if (int rc = mel_harm(me, H)) return rc;
+  if (int rc = mel_track_params(me, J, theta, nu)) return rc;
+  if (int rc = mel_mask_params(me, Hm, width, bin_hz)) return rc;
+  if (nsig == 0) return 0;
+  if (!s_dev || !idx_dev || !frac_dev || !w_dev || !f0_dev || !pen_dev || !path_dev || !mask_dev || !m_dev || !work_dev) return fail("null tensor");
+  const FitPlan pl = fit_plan(nsig, B, frames);
+  if (work_bytes < pl.bytes) return fail(me + ": work_bytes is smaller than glowk_melody_workspace_bytes says");
+  if (int rc = iva_aligned(me, {frac_dev, w_dev, f0_dev, pen_dev, work_dev})) return rc;
+  if ((uintptr_t)s_dev % 4 || (uintptr_t)idx_dev % 4 || (uintptr_t)path_dev % 4 || (uintptr_t)mask_dev % 4 || (uintptr_t)m_dev % 4)
+    return fail(me + ": the float32 and int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{path_dev, (size_t)nsig * frames * 4}, {mask_dev, mel_bytes_s(nsig, rows, frames)}, {m_dev, (size_t)nsig * 4},
+                                 {work_dev, pl.bytes}, {s_dev, mel_bytes_s(nsig, rows, frames)}, {idx_dev, (size_t)B * H * 4}, {frac_dev, (size_t)B * H * 8},
+                                 {w_dev, (size_t)H * 8}, {f0_dev, (size_t)B * 8}, {pen_dev, (size_t)(J + 1) * 8}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({s_dev, idx_dev, frac_dev, w_dev, f0_dev, pen_dev, path_dev, mask_dev, m_dev, work_dev}, &dev, "melody_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = (char*)work_dev;
+  float* sal = (float*)(wk + pl.sal);
+  double* e = (double*)(wk + pl.emi);
+  if (int rc = mel_launch_salience(s_dev, nsig, rows, frames, idx_dev, frac_dev, w_dev, B, H, sal, st)) return rc;
+  if (int rc = mel_launch_emission(sal, nsig, B, frames, e, m_dev, (float*)(wk + pl.part), st)) return rc;
+  if (int rc = mel_launch_track(e, nsig, B, frames, pen_dev, J, theta, nu, wk + pl.bp, path_dev, nullptr, st)) return rc;
+  return mel_launch_mask(path_dev, nsig, frames, f0_dev, B, rows, Hm, width, bin_hz, mask_dev, st);
 }
 
 }  // extern "C"

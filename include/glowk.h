@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 552
+#define GLOWK_VERSION 553
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -886,6 +886,54 @@ int glowk_iva_inverse(const double* w_dev, int nsig, int M, int rows, double* wi
 int glowk_iva_demix(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, float* y_dev, void* stream);
 int glowk_iva_images(const float* x_dev, const double* w_dev, const double* winv_dev, int nsig, int M, int rows, int frames,
                      float* y_dev /* may be null */, float* img_dev, void* stream);
+
+/* --- melody: harmonic salience, a Viterbi f0 track, a harmonic comb mask (Salamon & Gomez 2012; Hsu & Jang 2010; glowk_melody.h) ---- */
+/* s [nsig][rows][frames] float32 magnitudes, frames contiguous; f0 [B] float64, the grid of candidate fundamentals, strictly ascending
+ * and positive; everything is per signal.  nsig in [0, 65535] (0: a successful no-op), rows in [2, 4096], frames in [1, 32768], B in
+ * [1, 1024], H in [1, 32]; nsig rows frames and nsig (B + 1) frames <= 2^31 - 1.  The library takes tables, not formulas: the grid, the
+ * harmonic weights w [H], the jump penalties pen [J + 1] and the interpolation positions are float64 (int32) device tables that all the
+ * signals of a call share.  fp64 without contraction after the loads, every order fixed by the shapes, no atomics, no allocation, no
+ * host synchronisation: bitwise reproducible, and a batch gives what its signals give alone.  The conventions are those of the NMF and
+ * IVA sections: handle-free, device memory on one device, GLOWK_ERR with a glowk_last_error message before anything is launched;
+ * tensors a call writes must not overlap its other tensors; float64 tensors and workspaces 8-byte aligned, the others 4.  Inputs are
+ * finite and non-negative.  audiosourcesep_amd/melody.py drives the calls.  Since version 553.
+ *
+ * Positions (host): for h = 1 .. H, p = h f0_b / bin_hz in IEEE fp64, i = floor(p), a = p - i; term (b, h) is live iff i + 1 <= rows - 1.
+ * glowk_melody_positions fills idx_host [B][H] (i, or -1 for a dead term) and frac_host [B][H] (a); it refuses a grid that is not finite,
+ * positive and strictly ascending and a bin_hz that is not finite and positive.  The caller copies both to the device.
+ * Salience: sal[b][t] = sum_h w_h ((1 - a) s[i][t] + a s[i + 1][t]) over the live terms, h ascending, rounded once to float32.
+ * Emission: m = the maximum of the signal's salience plane (exact), e = (double) sal / max((double) m, 2^-40).
+ * Track: states 0 .. B - 1 are the bins, state B is "unvoiced"; only fp64 add, subtract and compare.  D_0[b] = e[b][0], D_0[B] = theta.
+ * For t >= 1 a candidate replaces the best only if strictly greater, in this order: voiced b: state B with D[B] - nu, then b' = max(0,
+ * b - J) .. min(B - 1, b + J) ascending with D[b'] - pen[|b - b'|]; D_t[b] = e[b][t] + best.  Unvoiced: state B with D[B], then b' = 0 ..
+ * B - 1 ascending with D[b'] - nu; D_t[B] = theta + best.  The path ends in the first maximum of D_{T-1}[0 .. B] and follows the back
+ * pointers.  J in [0, 1023]; theta and nu finite.
+ * Mask: 0 where path[t] is not in [0, B); else with x = f bin_hz and g = f0[path[t]], max(0, 1 - min_{h = 1 .. Hm} |x - h g| / width),
+ * rounded once.  Hm in [1, 1024], width and bin_hz finite and positive. */
+int glowk_melody_positions(const double* f0_host, int B, int H, double bin_hz, int rows, int32_t* idx_host, double* frac_host);
+/* Workspaces: emission 4 nsig groups bytes (groups = min(256, ceil(B frames / 4096)) partial maxima), track nsig frames (B + 1) uint16
+ * back pointers, the fused call both and the salience and emission planes (12 nsig B frames bytes); each part rounded up to 8 bytes.
+ * 0 for arguments out of range. */
+size_t glowk_melody_emission_workspace_bytes(int nsig, int B, int frames);
+size_t glowk_melody_track_workspace_bytes(int nsig, int B, int frames);
+size_t glowk_melody_workspace_bytes(int nsig, int B, int frames);
+/* sal [nsig][B][frames] float32.  One launch: a thread per (bin, frame), the frame fastest. */
+int glowk_melody_salience(const float* s_dev, int nsig, int rows, int frames, const int32_t* idx_dev, const double* frac_dev, const double* w_dev,
+                          int B, int H, float* sal_dev, void* stream);
+/* e [nsig][B][frames] float64 and m [nsig] float32.  Two launches. */
+int glowk_melody_emission(const float* sal_dev, int nsig, int B, int frames, double* e_dev, float* m_dev, void* work_dev, size_t work_bytes,
+                          void* stream);
+/* path [nsig][frames] int32 in [0, B].  One launch, one workgroup per signal, one barrier per frame.  ticks_dev (may be null): [nsig][2]
+ * int64, the ticks of the constant 100 MHz clock the recursion and the back-trace took. */
+int glowk_melody_track(const double* e_dev, int nsig, int B, int frames, const double* pen_dev, int J, double theta, double nu, int32_t* path_dev,
+                       int64_t* ticks_dev, void* work_dev, size_t work_bytes, void* stream);
+/* mask [nsig][rows][frames] float32.  One launch. */
+int glowk_melody_mask(const int32_t* path_dev, int nsig, int frames, const double* f0_dev, int B, int rows, int Hm, double width, double bin_hz,
+                      float* mask_dev, void* stream);
+/* Salience, emission, track and mask in one call (five launches): bit for bit the four calls above. */
+int glowk_melody_fit(const float* s_dev, int nsig, int rows, int frames, const int32_t* idx_dev, const double* frac_dev, const double* w_dev,
+                     const double* f0_dev, int B, int H, const double* pen_dev, int J, double theta, double nu, int Hm, double width, double bin_hz,
+                     int32_t* path_dev, float* mask_dev, float* m_dev, void* work_dev, size_t work_bytes, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
