@@ -193,6 +193,16 @@ SYMBOLS = {
     "glowk_melody_track": (_i, [_vp, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_melody_mask": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _d, _d, _vp, _vp]),
     "glowk_melody_fit": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _d, _d, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_rpca_gemm_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_rpca_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_rpca_eigh_workspace_bytes": (ctypes.c_size_t, [_i, _i]),
+    "glowk_rpca_eigh": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_rpca_shrink": (_i, [_vp, ctypes.c_size_t, _d, _vp, _vp]),
+    "glowk_rpca_svt_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_rpca_svt": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_rpca_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "glowk_rpca_fit": (_i, [_vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_rpca_binary_mask": (_i, [_vp, _vp, _vp, ctypes.c_size_t, _d, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -25,6 +25,7 @@
 #include "glowk_nmf.h"
 #include "glowk_iva.h"
 #include "glowk_melody.h"
+#include "glowk_rpca.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -2427,6 +2428,304 @@ int glowk_melody_fit(const float* s_dev, int nsig, int rows, int frames, const i
   if (int rc = mel_launch_emission(sal, nsig, B, frames, e, m_dev, (float*)(wk + pl.part), st)) return rc;
   if (int rc = mel_launch_track(e, nsig, B, frames, pen_dev, J, theta, nu, wk + pl.bp, path_dev, nullptr, st)) return rc;
   return mel_launch_mask(path_dev, nsig, frames, f0_dev, B, rows, Hm, width, bin_hz, mask_dev, st);
+}
+
+
+// ---- RPCA: low-rank plus sparse by inexact ALM; fp64 GEMM on the matrix cores, Jacobi eigensolver (glowk_rpca.h) ------------------------------
+namespace {
+enum { RPCA_GRAM = 0, RPCA_SCALED = 1, RPCA_APPLY = 2 };
+
+int rpca_sizes(const std::string& w, int nsig, int rows, int frames) {
+  using namespace glowk_rpca;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 2049]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 65535]");
+  if (!sizes_ok(nsig, rows, frames)) return fail(w + ": nsig * rows * frames and nsig * rows * rows must be at most 2^31 - 1");
+  return 0;
+}
+bool rpca_gemm_ok(int nsig, int M, int N, int K, int form) {
+  using namespace glowk_rpca;
+  if (form < RPCA_GRAM || form > RPCA_APPLY) return false;
+  if (nsig < 0 || nsig > MAX_SIG || M < 1 || M > MAX_ROWS || N < 1 || N > MAX_FRAMES || K < 1 || K > MAX_FRAMES) return false;
+  if (form != RPCA_APPLY && N != M) return false;
+  return (int64_t)nsig * M * N <= MAX_ELEMENTS && (int64_t)nsig * M * K <= MAX_ELEMENTS && (int64_t)nsig * N * K <= MAX_ELEMENTS;
+}
+int rpca_blocks(int64_t cells) { return (int)((cells + glowk_rpca::EW_THREADS - 1) / glowk_rpca::EW_THREADS); }
+
+// C = A A^T (GRAM, K split by the index header's rule), A diag(scale) A^T (SCALED) or A B (APPLY)
+int rpca_launch_gemm(int form, const double* A, const double* B, const double* scale, int nsig, int M, int N, int K, const int* active, double* C,
+                     double* partial, hipStream_t st) {
+  using namespace glowk_rpca;
+  const int nsplit = form == RPCA_GRAM ? gemm_splits(K) : 1;
+  const int len = nsplit == 1 ? K : gemm_split_len(K);
+  if (form == RPCA_APPLY) {
+    const dim3 grid((unsigned)(gemm_tiles(M) * gemm_tiles(N)), 1, (unsigned)nsig);
+    hipLaunchKernelGGL((k_rpca_gemm<false, false>), grid, dim3(GEMM_THREADS), 0, st, A, B, scale, M, N, K, 1, len, active, C, partial);
+    LAUNCHCHK("k_rpca_gemm");
+    return 0;
+  }
+  const dim3 grid((unsigned)gemm_upper_count(gemm_tiles(M)), (unsigned)nsplit, (unsigned)nsig);
+  hipLaunchKernelGGL((k_rpca_gemm<true, true>), grid, dim3(GEMM_THREADS), 0, st, A, A, scale, M, M, K, nsplit, len, active, C, partial);
+  LAUNCHCHK("k_rpca_gemm");
+  if (nsplit > 1) {
+    const int blocks = rpca_blocks((int64_t)M * M);
+    hipLaunchKernelGGL((k_rpca_gemm_reduce<true>), dim3((unsigned)((int64_t)nsig * blocks)), dim3(EW_THREADS), 0, st, (const double*)partial, M, M, nsplit,
+                       blocks, active, C);
+    LAUNCHCHK("k_rpca_gemm_reduce");
+  }
+  return 0;
+}
+
+// G -> diag(l) in place, V; two launches per round, the sweep flags read by the host after every sweep (the one synchronisation)
+int rpca_launch_eigh(double* G, int nsig, int n, const int* active, double* l, double* V, int32_t* sweeps, int32_t* status, void* work, hipStream_t st) {
+  using namespace glowk_rpca;
+  const EighPlan pl = eigh_plan(nsig, n);
+  double* cs = (double*)((char*)work + pl.cs);
+  double* floor = (double*)((char*)work + pl.floor);
+  int* flags = (int*)((char*)work + pl.flags);
+  const int blocks = rpca_blocks((int64_t)n * n), rounds = rr_rounds(n), pairs = rr_pairs(n);
+  hipLaunchKernelGGL(k_rpca_eye, dim3((unsigned)((int64_t)nsig * blocks)), dim3(EW_THREADS), 0, st, V, n, blocks, nsig, active, flags);
+  LAUNCHCHK("k_rpca_eye");
+  hipLaunchKernelGGL(k_rpca_jacobi_floor, dim3((unsigned)nsig), dim3(EW_THREADS), 0, st, (const double*)G, n, active, floor);
+  LAUNCHCHK("k_rpca_jacobi_floor");
+  int swept = 1;
+  if (rounds > 0) {
+    std::vector<int> host((size_t)nsig);
+    for (int sweep = 0; sweep < MAX_SWEEPS; ++sweep) {
+      for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(k_rpca_jacobi_rows, dim3((unsigned)pairs, (unsigned)nsig), dim3(JAC_THREADS), 0, st, G, n, nsig, sweep, r, active, (const double*)floor, cs, flags);
+        LAUNCHCHK("k_rpca_jacobi_rows");
+        hipLaunchKernelGGL(k_rpca_jacobi_cols, dim3((unsigned)n, (unsigned)nsig), dim3(JAC_THREADS), 0, st, G, V, n, nsig, sweep, r, active,
+                           (const double*)cs, (const int*)flags);
+        LAUNCHCHK("k_rpca_jacobi_cols");
+      }
+      swept = sweep + 1;
+      HIPCHK(hipMemcpyAsync(host.data(), flags + (size_t)sweep * nsig, (size_t)nsig * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      bool any = false;
+      for (int v : host) any = any || v != 0;
+      if (!any) break;
+    }
+  }
+  hipLaunchKernelGGL(k_rpca_eigh_finish, dim3((unsigned)nsig), dim3(EW_THREADS), 0, st, (const double*)G, n, nsig, swept, active, (const int*)flags, l, sweeps,
+                     status);
+  LAUNCHCHK("k_rpca_eigh_finish");
+  return 0;
+}
+
+// L = V diag(g) V^T A from the eigendecomposition of A A^T
+int rpca_launch_svt(const double* A, int nsig, int rows, int frames, const double* tau, const int* active, double* L, int32_t* sweeps, int32_t* status,
+                    void* work, hipStream_t st) {
+  using namespace glowk_rpca;
+  const SvtPlan pl = svt_plan(nsig, rows, frames);
+  char* wk = (char*)work;
+  double *G = (double*)(wk + pl.g), *V = (double*)(wk + pl.v), *P = (double*)(wk + pl.p), *l = (double*)(wk + pl.l), *gain = (double*)(wk + pl.gain);
+  if (int rc = rpca_launch_gemm(RPCA_GRAM, A, nullptr, nullptr, nsig, rows, rows, frames, active, G, (double*)(wk + pl.gemm), st)) return rc;
+  if (int rc = rpca_launch_eigh(G, nsig, rows, active, l, V, sweeps ? sweeps : (int32_t*)(wk + pl.sweeps), status, wk + pl.eigh, st)) return rc;
+  const int blocks = rpca_blocks(rows);
+  hipLaunchKernelGGL(k_rpca_gains, dim3((unsigned)((int64_t)nsig * blocks)), dim3(EW_THREADS), 0, st, (const double*)l, tau, rows, blocks, active, gain);
+  LAUNCHCHK("k_rpca_gains");
+  if (int rc = rpca_launch_gemm(RPCA_SCALED, V, nullptr, gain, nsig, rows, rows, rows, active, P, nullptr, st)) return rc;
+  return rpca_launch_gemm(RPCA_APPLY, P, A, nullptr, nsig, rows, frames, rows, active, L, nullptr, st);
+}
+}  // namespace
+
+size_t glowk_rpca_gemm_workspace_bytes(int nsig, int M, int N, int K, int form) {
+  if (nsig < 1 || !rpca_gemm_ok(nsig, M, N, K, form) || form != RPCA_GRAM) return 0;
+  return glowk_rpca::gemm_work_bytes(nsig, M, M, K);
+}
+size_t glowk_rpca_eigh_workspace_bytes(int nsig, int n) {
+  if (nsig < 1 || !glowk_rpca::sizes_ok(nsig, n, 1)) return 0;
+  return glowk_rpca::eigh_plan(nsig, n).bytes;
+}
+size_t glowk_rpca_svt_workspace_bytes(int nsig, int rows, int frames) {
+  if (nsig < 1 || !glowk_rpca::sizes_ok(nsig, rows, frames)) return 0;
+  return glowk_rpca::svt_plan(nsig, rows, frames).bytes;
+}
+size_t glowk_rpca_workspace_bytes(int nsig, int rows, int frames) {
+  if (nsig < 1 || !glowk_rpca::sizes_ok(nsig, rows, frames)) return 0;
+  return glowk_rpca::fit_plan(nsig, rows, frames).bytes;
+}
+
+int glowk_rpca_gemm(const double* a_dev, const double* b_dev, const double* scale_dev, int nsig, int M, int N, int K, int form, double* c_dev, void* work_dev,
+                    size_t work_bytes, void* stream) {
+  using namespace glowk_rpca;
+  const std::string me("rpca_gemm");
+  if (form < RPCA_GRAM || form > RPCA_APPLY) return fail(me + ": form must be 0 (A A^T), 1 (A diag(scale) A^T) or 2 (A B)");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (M < 1 || M > MAX_ROWS) return fail(me + ": M must be in [1, 2049]");
+  if (N < 1 || N > MAX_FRAMES || K < 1 || K > MAX_FRAMES) return fail(me + ": N and K must be in [1, 65535]");
+  if (form != RPCA_APPLY && N != M) return fail(me + ": the symmetric forms need N == M");
+  if (!rpca_gemm_ok(nsig, M, N, K, form)) return fail(me + ": every operand must have at most 2^31 - 1 elements");
+  if (nsig == 0) return 0;
+  const size_t need = form == RPCA_GRAM ? gemm_work_bytes(nsig, M, M, K) : 0;
+  if (!a_dev || !c_dev || (form == RPCA_APPLY && !b_dev) || (form == RPCA_SCALED && !scale_dev) || (need && !work_dev)) return fail("null tensor");
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_rpca_gemm_workspace_bytes says");
+  if (int rc = iva_aligned(me, {a_dev, b_dev, scale_dev, c_dev, work_dev})) return rc;
+  const double* b = form == RPCA_APPLY ? b_dev : nullptr;
+  const double* sc = form == RPCA_SCALED ? scale_dev : nullptr;
+  if (int rc = iva_disjoint(me, {{c_dev, (size_t)nsig * M * N * 8}, {need ? work_dev : nullptr, need}, {a_dev, (size_t)nsig * M * K * 8},
+                                 {b, (size_t)nsig * K * N * 8}, {sc, (size_t)nsig * K * 8}}, 2))
+    return rc;
+  int dev;
+  if (int rc = audio_device({a_dev, b, sc, c_dev, need ? work_dev : nullptr}, &dev, "rpca_gemm")) return rc;
+  DeviceGuard dg(dev);
+  return rpca_launch_gemm(form, a_dev, b, sc, nsig, M, N, K, nullptr, c_dev, (double*)work_dev, (hipStream_t)stream);
+}
+
+int glowk_rpca_eigh(double* g_dev, int nsig, int n, double* l_dev, double* v_dev, int32_t* sweeps_dev, int32_t* status_dev, void* work_dev, size_t work_bytes,
+                    void* stream) {
+  using namespace glowk_rpca;
+  const std::string me("rpca_eigh");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (n < 1 || n > MAX_ROWS) return fail(me + ": n must be in [1, 2049]");
+  if (!sizes_ok(nsig, n, 1)) return fail(me + ": nsig * n * n must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!g_dev || !l_dev || !v_dev || !sweeps_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = eigh_plan(nsig, n).bytes, nn = (size_t)nsig * n * n * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_rpca_eigh_workspace_bytes says");
+  if (int rc = iva_aligned(me, {g_dev, l_dev, v_dev, work_dev})) return rc;
+  if ((uintptr_t)sweeps_dev % 4 || (uintptr_t)status_dev % 4) return fail(me + ": the int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{g_dev, nn}, {v_dev, nn}, {l_dev, (size_t)nsig * n * 8}, {sweeps_dev, (size_t)nsig * 4}, {status_dev, (size_t)nsig * 4},
+                                 {work_dev, need}}, 6))
+    return rc;
+  int dev;
+  if (int rc = audio_device({g_dev, l_dev, v_dev, sweeps_dev, status_dev, work_dev}, &dev, "rpca_eigh")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(status_dev, 0, (size_t)nsig * 4, st));
+  return rpca_launch_eigh(g_dev, nsig, n, nullptr, l_dev, v_dev, sweeps_dev, status_dev, work_dev, st);
+}
+
+int glowk_rpca_shrink(const double* t_dev, size_t count, double thr, double* out_dev, void* stream) {
+  const std::string me("rpca_shrink");
+  if (count > (size_t)glowk_rpca::MAX_ELEMENTS) return fail(me + ": count must be at most 2^31 - 1");
+  if (!(std::isfinite(thr) && thr >= 0)) return fail(me + ": thr must be finite and not negative");
+  if (count == 0) return 0;
+  if (!t_dev || !out_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {t_dev, out_dev})) return rc;
+  if (t_dev != out_dev && bytes_overlap(t_dev, count * 8, out_dev, count * 8)) return fail(me + ": out_dev must be t_dev itself or not overlap it");
+  int dev;
+  if (int rc = audio_device({t_dev, out_dev}, &dev, "rpca_shrink")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(glowk_rpca::k_rpca_shrink, dim3((unsigned)rpca_blocks((int64_t)count)), dim3(glowk_rpca::EW_THREADS), 0, (hipStream_t)stream, t_dev,
+                     (int64_t)count, thr, out_dev);
+  LAUNCHCHK("k_rpca_shrink");
+  return 0;
+}
+
+int glowk_rpca_svt(const double* a_dev, int nsig, int rows, int frames, const double* tau_dev, double* l_dev, int32_t* sweeps_dev, int32_t* status_dev,
+                   void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_rpca;
+  const std::string me("rpca_svt");
+  if (int rc = rpca_sizes(me, nsig, rows, frames)) return rc;
+  if (nsig == 0) return 0;
+  if (!a_dev || !tau_dev || !l_dev || !sweeps_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = svt_plan(nsig, rows, frames).bytes, cells = (size_t)nsig * rows * frames * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_rpca_svt_workspace_bytes says");
+  if (int rc = iva_aligned(me, {a_dev, tau_dev, l_dev, work_dev})) return rc;
+  if ((uintptr_t)sweeps_dev % 4 || (uintptr_t)status_dev % 4) return fail(me + ": the int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{l_dev, cells}, {sweeps_dev, (size_t)nsig * 4}, {status_dev, (size_t)nsig * 4}, {work_dev, need}, {a_dev, cells},
+                                 {tau_dev, (size_t)nsig * 8}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({a_dev, tau_dev, l_dev, sweeps_dev, status_dev, work_dev}, &dev, "rpca_svt")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(status_dev, 0, (size_t)nsig * 4, st));
+  return rpca_launch_svt(a_dev, nsig, rows, frames, tau_dev, nullptr, l_dev, sweeps_dev, status_dev, work_dev, st);
+}
+
+int glowk_rpca_fit(const float* m_dev, int nsig, int rows, int frames, double gain, double tol, int n_iter, double* l_dev, double* s_dev, int32_t* iters_dev,
+                   int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_rpca;
+  const std::string me("rpca_fit");
+  if (int rc = rpca_sizes(me, nsig, rows, frames)) return rc;
+  if (!(std::isfinite(gain) && gain > 0)) return fail(me + ": gain must be finite and positive");
+  if (!(std::isfinite(tol) && tol >= 0)) return fail(me + ": tol must be finite and not negative");
+  if (n_iter < 0 || n_iter > MAX_ITER) return fail(me + ": n_iter must be in [0, 100000]");
+  if (nsig == 0) return 0;
+  if (!m_dev || !l_dev || !s_dev || !iters_dev || !status_dev || !work_dev) return fail("null tensor");
+  const FitPlan pl = fit_plan(nsig, rows, frames);
+  const size_t cells8 = (size_t)nsig * rows * frames * 8;
+  if (work_bytes < pl.bytes) return fail(me + ": work_bytes is smaller than glowk_rpca_workspace_bytes says");
+  if (int rc = iva_aligned(me, {l_dev, s_dev, work_dev})) return rc;
+  if ((uintptr_t)m_dev % 4 || (uintptr_t)iters_dev % 4 || (uintptr_t)status_dev % 4) return fail(me + ": the float32 and int32 tensors must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{l_dev, cells8}, {s_dev, cells8}, {iters_dev, (size_t)nsig * 4}, {status_dev, (size_t)nsig * 4}, {work_dev, pl.bytes},
+                                 {m_dev, cells8 / 2}}, 5))
+    return rc;
+  int dev;
+  if (int rc = audio_device({m_dev, l_dev, s_dev, iters_dev, status_dev, work_dev}, &dev, "rpca_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = (char*)work_dev;
+  const SvtPlan sp = svt_plan(nsig, rows, frames);
+  double *Y = (double*)(wk + pl.y), *A = (double*)(wk + pl.a), *state = (double*)(wk + pl.state), *tau = (double*)(wk + pl.tau), *sums = (double*)(wk + pl.sums);
+  float* maxes = (float*)(wk + pl.maxes);
+  int* active = (int*)(wk + pl.active);
+  char* svt = wk + pl.svt;
+  double *G = (double*)(svt + sp.g), *V = (double*)(svt + sp.v), *l = (double*)(svt + sp.l);
+  int32_t *sweeps = (int32_t*)(svt + sp.sweeps), *solve_status = (int32_t*)(svt + sp.status);
+  const int64_t cells = (int64_t)rows * frames;
+  const int groups = ew_groups(cells), blocks = rpca_blocks(cells);
+  const double lam = gain / std::sqrt((double)(rows > frames ? rows : frames));
+
+  // the start: ||M||_2 from the Gram matrix of M itself (A holds M as float64 for the product), max |M|, then Y, L, S and the state
+  HIPCHK(hipMemsetAsync(status_dev, 0, (size_t)nsig * 4, st));
+  HIPCHK(hipMemsetAsync(solve_status, 0, (size_t)nsig * 4, st));
+  hipLaunchKernelGGL(k_rpca_widen, dim3((unsigned)rpca_blocks((int64_t)nsig * cells)), dim3(EW_THREADS), 0, st, m_dev, (int64_t)nsig * cells, A);
+  LAUNCHCHK("k_rpca_widen");
+  if (int rc = rpca_launch_gemm(RPCA_GRAM, A, nullptr, nullptr, nsig, rows, rows, frames, nullptr, G, (double*)(svt + sp.gemm), st)) return rc;
+  if (int rc = rpca_launch_eigh(G, nsig, rows, nullptr, l, V, sweeps, solve_status, svt + sp.eigh, st)) return rc;
+  hipLaunchKernelGGL(k_rpca_absmax, dim3((unsigned)((int64_t)nsig * groups)), dim3(EW_THREADS), 0, st, m_dev, cells, groups, maxes);
+  LAUNCHCHK("k_rpca_absmax");
+  hipLaunchKernelGGL(k_rpca_init, dim3((unsigned)nsig), dim3(64), 0, st, (const double*)l, rows, (const float*)maxes, groups, lam, state, tau, active, iters_dev,
+                     (const int*)solve_status, status_dev);
+  LAUNCHCHK("k_rpca_init");
+  hipLaunchKernelGGL(k_rpca_start, dim3((unsigned)((int64_t)nsig * blocks)), dim3(EW_THREADS), 0, st, m_dev, cells, blocks, (const double*)state, (const int*)active,
+                     l_dev, s_dev, Y);
+  LAUNCHCHK("k_rpca_start");
+
+  std::vector<int> host((size_t)nsig);
+  for (int it = 0; it < n_iter; ++it) {
+    HIPCHK(hipMemcpyAsync(host.data(), active, (size_t)nsig * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    bool any = false;
+    for (int v : host) any = any || v != 0;
+    if (!any) break;
+    hipLaunchKernelGGL(k_rpca_sparse, dim3((unsigned)((int64_t)nsig * blocks)), dim3(EW_THREADS), 0, st, m_dev, (const double*)l_dev, (const double*)Y, cells, blocks,
+                       (const double*)state, (const int*)active, s_dev, A);
+    LAUNCHCHK("k_rpca_sparse");
+    if (int rc = rpca_launch_svt(A, nsig, rows, frames, tau, active, l_dev, nullptr, solve_status, svt, st)) return rc;
+    hipLaunchKernelGGL(k_rpca_residual, dim3((unsigned)((int64_t)nsig * groups)), dim3(EW_THREADS), 0, st, m_dev, (const double*)l_dev, (const double*)s_dev, cells,
+                       groups, (const double*)state, (const int*)active, Y, sums);
+    LAUNCHCHK("k_rpca_residual");
+    hipLaunchKernelGGL(k_rpca_finish, dim3((unsigned)nsig), dim3(64), 0, st, (const double*)sums, groups, tol, state, tau, active, iters_dev,
+                       (const int*)solve_status, status_dev);
+    LAUNCHCHK("k_rpca_finish");
+  }
+  return 0;
+}
+
+int glowk_rpca_binary_mask(const double* l_dev, const double* s_dev, const float* x_dev, size_t count, double gain_mask, float* mask_dev, float* bg_dev,
+                           float* fg_dev, void* stream) {
+  const std::string me("rpca_binary_mask");
+  if (count > (size_t)glowk_rpca::MAX_ELEMENTS) return fail(me + ": count must be at most 2^31 - 1");
+  if (!(std::isfinite(gain_mask) && gain_mask >= 0)) return fail(me + ": gain_mask must be finite and not negative");
+  if (count == 0) return 0;
+  if (!l_dev || !s_dev || !mask_dev || (x_dev && (!bg_dev || !fg_dev))) return fail("null tensor");
+  if (int rc = iva_aligned(me, {l_dev, s_dev, x_dev, bg_dev, fg_dev})) return rc;
+  if ((uintptr_t)mask_dev % 4) return fail(me + ": mask_dev must be aligned to 4 bytes");
+  const float* bg = x_dev ? bg_dev : nullptr;
+  const float* fg = x_dev ? fg_dev : nullptr;
+  if (int rc = iva_disjoint(me, {{mask_dev, count * 4}, {bg, count * 8}, {fg, count * 8}, {l_dev, count * 8}, {s_dev, count * 8}, {x_dev, count * 8}}, 3)) return rc;
+  int dev;
+  if (int rc = audio_device({l_dev, s_dev, x_dev, mask_dev, bg, fg}, &dev, "rpca_binary_mask")) return rc;
+  DeviceGuard dg(dev);
+  hipLaunchKernelGGL(glowk_rpca::k_rpca_binary_mask, dim3((unsigned)rpca_blocks((int64_t)count)), dim3(glowk_rpca::EW_THREADS), 0, (hipStream_t)stream, l_dev, s_dev,
+                     (const float2*)x_dev, (int64_t)count, gain_mask, mask_dev, (float2*)bg, (float2*)fg);
+  LAUNCHCHK("k_rpca_binary_mask");
+  return 0;
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 553
+#define GLOWK_VERSION 554
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -934,6 +934,60 @@ int glowk_melody_mask(const int32_t* path_dev, int nsig, int frames, const doubl
 int glowk_melody_fit(const float* s_dev, int nsig, int rows, int frames, const int32_t* idx_dev, const double* frac_dev, const double* w_dev,
                      const double* f0_dev, int B, int H, const double* pen_dev, int J, double theta, double nu, int Hm, double width, double bin_hz,
                      int32_t* path_dev, float* mask_dev, float* m_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* --- RPCA: low-rank plus sparse by inexact ALM (Lin et al. 2010; Huang et al. 2012; glowk_rpca.h) ------------------------------------- */
+/* m [nsig][rows][frames] float32 magnitudes, frames contiguous; everything is per signal.  nsig in [0, 65535] (0: a successful no-op),
+ * rows in [1, 2049], frames in [1, 65535]; nsig rows frames and nsig rows rows <= 2^31 - 1.  All state and arithmetic after the load of
+ * m are fp64 without contraction; every order is fixed by the shapes, there are no atomics, no spin waits and no allocation: bitwise
+ * reproducible, and a batch gives what its signals give alone.  The eigensolver reads its sweep flags (4 nsig bytes) on the host once
+ * per sweep and glowk_rpca_fit its stop flags once per iteration; these calls synchronise the stream, the others do not.  Conventions
+ * as in the NMF, IVA and melody sections: handle-free, device memory on one device, GLOWK_ERR with a glowk_last_error message before
+ * anything is launched; tensors a call writes must not overlap its other tensors; float64 tensors and workspaces 8-byte aligned, the
+ * others 4.  Inputs are finite.  audiosourcesep_amd/rpca.py drives the calls.  Since version 554.
+ *
+ * GEMM (v_mfma_f64_16x16x4_f64, 64 x 64 tiles): form 0, c [M][M] = a a^T with a [M][K]; form 1, c [M][M] = a diag(scale) a^T with scale
+ * [K], each term a_ik (scale_k a_jk); form 2, c [M][N] = a b with b [K][N].  N == M for forms 0 and 1, whose elements i <= j are computed
+ * once and mirrored: c is exactly symmetric.  The sum over k is one fused multiply-add chain in ascending k from 0; form 0 splits K into
+ * min(8, ceil(K / 1024)) parts of ceil(K / parts) rounded up to 16, a chain each, added in ascending order from part 0 by a second
+ * launch (work_dev: 8 nsig parts M M bytes when parts > 1, else none; the other forms need none).  M in [1, 2049], N and K in [1, 65535].
+ * Error per element: at most (K + 4) 2^-53 sum_k |a_ik| |b_kj|.
+ * Eigensolver: cyclic Jacobi on g [nsig][n][n] (symmetric, overwritten; its diagonal ends as l) in round-robin order: m = n rounded up
+ * to even, position 0 holds index 0 and position j >= 1 holds 1 + (j - 1 - r) mod (m - 1) in round r = 0 .. m - 2; round r pairs
+ * positions i and m - 1 - i, i < m / 2; the pair with index n (odd n) rests.  A pair p < q is rotated when |g_pq| > 2^-52 sqrt(|g_pp
+ * g_qq|) and |g_pq| > 2^-51 max |g| (of g as given; without it the null space of a rank-deficient matrix rotates rounding noise against
+ * a diagonal of rounding noise until the cap): theta = (g_qq - g_pp) / (2 g_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) (1 for theta = 0), c = 1 / sqrt(t^2 + 1),
+ * s = t c.  All rotations of a round come from g at the round's start; then rows p and q of g become c g_p - s g_q and s g_p + c g_q
+ * (one launch), then columns p and q of g and of v likewise (a second launch).  v starts as the identity: g_in = v diag(l) v^T.  A
+ * sweep is the m - 1 rounds; the solve ends after the first sweep that rotated nothing, or after 30 sweeps, and then bit 0 of
+ * status_dev is set.  sweeps_dev [nsig]: the sweeps run, that last one included (1 for a diagonal matrix).  l is in the solver's
+ * order, not sorted.  work_dev: 16 nsig ceil(n / 2) + 8 nsig + 120 nsig bytes, rounded up to 8.
+ * Shrink: out = sign(t) max(|t| - thr, 0); out_dev may be t_dev.
+ * SVT: G = a a^T (form 0), G = v diag(l) v^T, sigma_i = sqrt(max(l_i, 0)), g_i = sigma_i > tau ? 1 - tau / sigma_i : 0, P = v diag(g)
+ * v^T (form 1), l_dev = P a (form 2); tau_dev [nsig] float64.
+ * Fit: lam = gain / sqrt(max(rows, frames)); n2 = sqrt of the largest eigenvalue of m m^T from the solver; ninf = max |m|; a signal
+ * with n2 == 0 gets L = S = 0 and 0 iterations.  Else Y = m / max(n2, ninf / lam), mu = 1.25 / n2, mu_bar = 1e7 mu, L = S = 0, and per
+ * iteration: S = shrink((m - L) + Y / mu, lam / mu); L = SVT((m - S) + Y / mu, 1 / mu); Z = (m - L) - S; Y = Y + mu Z; mu = min(1.5 mu,
+ * mu_bar); the signal stops when sqrt(sum Z^2) / sqrt(sum m^2) < tol (the sums over chunks of the cells, 256 strided threads each in
+ * ascending order, a pairwise tree, the chunks in order).  A stopped signal's L, S and count are frozen.  gain > 0, tol >= 0, n_iter in
+ * [0, 100000].  iters_dev [nsig] int32; status_dev [nsig] int32, the OR of the solves' status.
+ * Binary mask: mask = |S| > gain_mask |L| ? 1 : 0; with x_dev (complex64) also bg = (1 - mask) x and fg = mask x. */
+size_t glowk_rpca_gemm_workspace_bytes(int nsig, int M, int N, int K, int form);
+int glowk_rpca_gemm(const double* a_dev, const double* b_dev, const double* scale_dev, int nsig, int M, int N, int K, int form, double* c_dev, void* work_dev,
+                    size_t work_bytes, void* stream);
+size_t glowk_rpca_eigh_workspace_bytes(int nsig, int n);
+int glowk_rpca_eigh(double* g_dev, int nsig, int n, double* l_dev, double* v_dev, int32_t* sweeps_dev, int32_t* status_dev, void* work_dev, size_t work_bytes,
+                    void* stream);
+int glowk_rpca_shrink(const double* t_dev, size_t count, double thr, double* out_dev, void* stream);
+/* svt workspace: three n x n matrices, two n vectors and the flags per signal, the form 0 partials, the solver's.  fit workspace: two
+ * rows x frames float64 planes per signal, the state, the partial sums, and the svt workspace.  0 for arguments out of range. */
+size_t glowk_rpca_svt_workspace_bytes(int nsig, int rows, int frames);
+int glowk_rpca_svt(const double* a_dev, int nsig, int rows, int frames, const double* tau_dev, double* l_dev, int32_t* sweeps_dev, int32_t* status_dev,
+                   void* work_dev, size_t work_bytes, void* stream);
+size_t glowk_rpca_workspace_bytes(int nsig, int rows, int frames);
+int glowk_rpca_fit(const float* m_dev, int nsig, int rows, int frames, double gain, double tol, int n_iter, double* l_dev, double* s_dev, int32_t* iters_dev,
+                   int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream);
+int glowk_rpca_binary_mask(const double* l_dev, const double* s_dev, const float* x_dev, size_t count, double gain_mask, float* mask_dev, float* bg_dev,
+                           float* fg_dev, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
