@@ -203,6 +203,14 @@ SYMBOLS = {
     "glowk_rpca_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "glowk_rpca_fit": (_i, [_vp, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_rpca_binary_mask": (_i, [_vp, _vp, _vp, ctypes.c_size_t, _d, _vp, _vp, _vp, _vp]),
+    "glowk_projet_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_projet_projections": (_i, [_vp, _i, _i, _i, _vp, _i, _d, _vp, _vp]),
+    "glowk_projet_gains": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_projet_update_p": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _d, _i, _vp, _vp]),
+    "glowk_projet_update_q": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_projet_fit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_projet_divergence": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _d, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_projet_separate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -26,6 +26,7 @@
 #include "glowk_iva.h"
 #include "glowk_melody.h"
 #include "glowk_rpca.h"
+#include "glowk_projet.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -2725,6 +2726,245 @@ int glowk_rpca_binary_mask(const double* l_dev, const double* s_dev, const float
   hipLaunchKernelGGL(glowk_rpca::k_rpca_binary_mask, dim3((unsigned)rpca_blocks((int64_t)count)), dim3(glowk_rpca::EW_THREADS), 0, (hipStream_t)stream, l_dev, s_dev,
                      (const float2*)x_dev, (int64_t)count, gain_mask, mask_dev, (float2*)bg, (float2*)fg);
   LAUNCHCHK("k_rpca_binary_mask");
+  return 0;
+}
+
+// ---- PROJET: panned sources from two channels by projections; the outer sums on the fp64 matrix cores (glowk_projet.h) -------------------------
+namespace {
+int projet_sizes(const std::string& w, int nsig, int rows, int frames, int J) {
+  using namespace glowk_projet;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (J < 1 || J > MAX_J) return fail(w + ": the source count J must be in [1, 8]");
+  if (!sizes_ok(nsig, rows, frames, J)) return fail(w + ": nsig * J * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int projet_model(const std::string& w, int nsig, int M, int L, int J) {
+  using namespace glowk_projet;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (M < MIN_M || M > MAX_M) return fail(w + ": the projection count M must be in [2, 32]");
+  if (L < 1 || L > MAX_L) return fail(w + ": the pan count L must be in [1, 128]");
+  if (J < 1 || J > MAX_J) return fail(w + ": the source count J must be in [1, 8]");
+  return 0;
+}
+int projet_powers(const std::string& w, double alpha, int beta) {
+  if (!(alpha >= 1.0 && alpha <= 2.0)) return fail(w + ": alpha must be in [1, 2]");
+  if (beta < 0 || beta > 2) return fail(w + ": beta must be 0, 1 or 2");
+  return 0;
+}
+int projet_amode(double alpha) {
+  return alpha == 1.0 ? glowk_projet::ALPHA_ONE : alpha == 2.0 ? glowk_projet::ALPHA_TWO : glowk_projet::ALPHA_POW;
+}
+size_t projet_bytes_x(int nsig, int rows, int frames) { return (size_t)nsig * 2 * rows * frames * 8; }
+size_t projet_bytes_p(int nsig, int J, int rows, int frames) { return (size_t)nsig * J * rows * frames * 8; }
+
+#define GLOWK_PROJET_EACH_J(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+
+int projet_launch_gains(const double* K, const double* Q, int nsig, int M, int L, int J, double* G, hipStream_t st) {
+  using namespace glowk_projet;
+  hipLaunchKernelGGL(k_projet_gains, dim3((unsigned)nsig), dim3(THREADS), 0, st, K, Q, M, L, J, G);
+  LAUNCHCHK("k_projet_gains");
+  return 0;
+}
+// the fused pass: the P update (do_p), the partial outer sums (do_sums), or both
+int projet_launch_iterate(const float* x, double* P, int nsig, int rows, int frames, const double* U, const double* G, int M, int J, double alpha, int beta,
+                          int do_p, int do_sums, double* partial, hipStream_t st) {
+  using namespace glowk_projet;
+  const int64_t cells = (int64_t)rows * frames;
+  const dim3 grid((unsigned)((int64_t)nsig * groups(cells)));
+  switch (J) {
+#define GLOWK_CASE(j)                                                                                                                        \
+  case j:                                                                                                                                    \
+    hipLaunchKernelGGL(k_projet_iterate<j>, grid, dim3(THREADS), 0, st, (const float2*)x, P, cells, U, G, M, projet_amode(alpha), alpha / 2.0, beta, do_p, do_sums, \
+                       partial);                                                                                                             \
+    break;
+    GLOWK_PROJET_EACH_J(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_projet_iterate");
+  return 0;
+}
+int projet_launch_q(const double* partial, int nsig, int rows, int frames, const double* K, int M, int L, int J, int beta, double* Q, double* G, hipStream_t st) {
+  using namespace glowk_projet;
+  hipLaunchKernelGGL(k_projet_q, dim3((unsigned)nsig), dim3(THREADS), 0, st, partial, groups((int64_t)rows * frames), K, M, L, J, beta, Q, G);
+  LAUNCHCHK("k_projet_q");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_projet_workspace_bytes(int nsig, int M, int J, int rows, int frames) {
+  using namespace glowk_projet;
+  if (nsig < 1 || !sizes_ok(nsig, rows, frames, J) || !model_ok(M, 1, J)) return 0;
+  return work_bytes(nsig, M, J, rows, frames);
+}
+
+int glowk_projet_projections(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, int M, double alpha, double* v_dev, void* stream) {
+  using namespace glowk_projet;
+  const std::string me("projet_projections");
+  if (int rc = projet_sizes(me, nsig, rows, frames, 1)) return rc;
+  if (int rc = projet_model(me, nsig, M, 1, 1)) return rc;
+  if (int rc = projet_powers(me, alpha, 1)) return rc;
+  if ((int64_t)nsig * M * rows * frames > MAX_ELEMENTS) return fail(me + ": nsig * M * rows * frames must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!x_dev || !u_dev || !v_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, u_dev, v_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{v_dev, (size_t)nsig * M * rows * frames * 8}, {x_dev, projet_bytes_x(nsig, rows, frames)}, {u_dev, (size_t)M * 16}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, u_dev, v_dev}, &dev, "projet_projections")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t cells = (int64_t)rows * frames, total = cells * nsig;
+  hipLaunchKernelGGL(k_projet_projections, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, (const float2*)x_dev, total, cells,
+                     u_dev, M, projet_amode(alpha), alpha / 2.0, v_dev);
+  LAUNCHCHK("k_projet_projections");
+  return 0;
+}
+
+int glowk_projet_gains(const double* k_dev, const double* q_dev, int nsig, int M, int L, int J, double* g_dev, void* stream) {
+  const std::string me("projet_gains");
+  if (int rc = projet_model(me, nsig, M, L, J)) return rc;
+  if (nsig == 0) return 0;
+  if (!k_dev || !q_dev || !g_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {k_dev, q_dev, g_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{g_dev, (size_t)nsig * M * J * 8}, {k_dev, (size_t)M * L * 8}, {q_dev, (size_t)nsig * L * J * 8}}, 1)) return rc;
+  int dev;
+  if (int rc = audio_device({k_dev, q_dev, g_dev}, &dev, "projet_gains")) return rc;
+  DeviceGuard dg(dev);
+  return projet_launch_gains(k_dev, q_dev, nsig, M, L, J, g_dev, (hipStream_t)stream);
+}
+
+int glowk_projet_update_p(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, const double* g_dev, int M, int J, double alpha, int beta,
+                          double* p_dev, void* stream) {
+  const std::string me("projet_update_p");
+  if (int rc = projet_sizes(me, nsig, rows, frames, J)) return rc;
+  if (int rc = projet_model(me, nsig, M, 1, J)) return rc;
+  if (int rc = projet_powers(me, alpha, beta)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !u_dev || !g_dev || !p_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, u_dev, g_dev, p_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{p_dev, projet_bytes_p(nsig, J, rows, frames)}, {x_dev, projet_bytes_x(nsig, rows, frames)}, {u_dev, (size_t)M * 16},
+                                 {g_dev, (size_t)nsig * M * J * 8}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, u_dev, g_dev, p_dev}, &dev, "projet_update_p")) return rc;
+  DeviceGuard dg(dev);
+  return projet_launch_iterate(x_dev, p_dev, nsig, rows, frames, u_dev, g_dev, M, J, alpha, beta, 1, 0, nullptr, (hipStream_t)stream);
+}
+
+int glowk_projet_update_q(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* k_dev, int M, int L, int J,
+                          double alpha, int beta, double* q_dev, double* g_dev, void* work_dev, size_t work_bytes, void* stream) {
+  const std::string me("projet_update_q");
+  if (int rc = projet_sizes(me, nsig, rows, frames, J)) return rc;
+  if (int rc = projet_model(me, nsig, M, L, J)) return rc;
+  if (int rc = projet_powers(me, alpha, beta)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !p_dev || !u_dev || !k_dev || !q_dev || !g_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_projet::work_bytes(nsig, M, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_projet_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, p_dev, u_dev, k_dev, q_dev, g_dev, work_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{q_dev, (size_t)nsig * L * J * 8}, {g_dev, (size_t)nsig * M * J * 8}, {work_dev, need}, {p_dev, projet_bytes_p(nsig, J, rows, frames)},
+                                 {x_dev, projet_bytes_x(nsig, rows, frames)}, {u_dev, (size_t)M * 16}, {k_dev, (size_t)M * L * 8}}, 3))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, p_dev, u_dev, k_dev, q_dev, g_dev, work_dev}, &dev, "projet_update_q")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = projet_launch_iterate(x_dev, const_cast<double*>(p_dev), nsig, rows, frames, u_dev, g_dev, M, J, alpha, beta, 0, 1, (double*)work_dev, st)) return rc;
+  return projet_launch_q((const double*)work_dev, nsig, rows, frames, k_dev, M, L, J, beta, q_dev, g_dev, st);
+}
+
+int glowk_projet_fit(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, const double* k_dev, int M, int L, int J, double alpha, int beta,
+                     int n_iter, double* p_dev, double* q_dev, double* g_dev, void* work_dev, size_t work_bytes, void* stream) {
+  const std::string me("projet_fit");
+  if (int rc = projet_sizes(me, nsig, rows, frames, J)) return rc;
+  if (int rc = projet_model(me, nsig, M, L, J)) return rc;
+  if (int rc = projet_powers(me, alpha, beta)) return rc;
+  if (n_iter < 0 || n_iter > glowk_projet::MAX_ITER) return fail(me + ": n_iter must be in [0, 100000]");
+  if (nsig == 0) return 0;
+  if (!x_dev || !u_dev || !k_dev || !p_dev || !q_dev || !g_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_projet::work_bytes(nsig, M, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_projet_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, u_dev, k_dev, p_dev, q_dev, g_dev, work_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{p_dev, projet_bytes_p(nsig, J, rows, frames)}, {q_dev, (size_t)nsig * L * J * 8}, {g_dev, (size_t)nsig * M * J * 8}, {work_dev, need},
+                                 {x_dev, projet_bytes_x(nsig, rows, frames)}, {u_dev, (size_t)M * 16}, {k_dev, (size_t)M * L * 8}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, u_dev, k_dev, p_dev, q_dev, g_dev, work_dev}, &dev, "projet_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = projet_launch_gains(k_dev, q_dev, nsig, M, L, J, g_dev, st)) return rc;
+  for (int it = 0; it < n_iter; ++it) {
+    if (int rc = projet_launch_iterate(x_dev, p_dev, nsig, rows, frames, u_dev, g_dev, M, J, alpha, beta, 1, 1, (double*)work_dev, st)) return rc;
+    if (int rc = projet_launch_q((const double*)work_dev, nsig, rows, frames, k_dev, M, L, J, beta, q_dev, g_dev, st)) return rc;
+  }
+  return 0;
+}
+
+int glowk_projet_divergence(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* g_dev, int M, int J,
+                            double alpha, int beta, double* d_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_projet;
+  const std::string me("projet_divergence");
+  if (int rc = projet_sizes(me, nsig, rows, frames, J)) return rc;
+  if (int rc = projet_model(me, nsig, M, 1, J)) return rc;
+  if (int rc = projet_powers(me, alpha, beta)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !p_dev || !u_dev || !g_dev || !d_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_projet::work_bytes(nsig, M, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_projet_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, p_dev, u_dev, g_dev, d_dev, work_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{d_dev, (size_t)nsig * 8}, {work_dev, need}, {p_dev, projet_bytes_p(nsig, J, rows, frames)}, {x_dev, projet_bytes_x(nsig, rows, frames)},
+                                 {u_dev, (size_t)M * 16}, {g_dev, (size_t)nsig * M * J * 8}}, 2))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, p_dev, u_dev, g_dev, d_dev, work_dev}, &dev, "projet_divergence")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t cells = (int64_t)rows * frames;
+  const int ng = groups(cells);
+  const dim3 grid((unsigned)((int64_t)nsig * ng));
+  switch (J) {
+#define GLOWK_CASE(j)                                                                                                                              \
+  case j:                                                                                                                                          \
+    hipLaunchKernelGGL(k_projet_divergence<j>, grid, dim3(THREADS), 0, st, (const float2*)x_dev, p_dev, cells, u_dev, g_dev, M, projet_amode(alpha), alpha / 2.0, beta, \
+                       (double*)work_dev);                                                                                                         \
+    break;
+    GLOWK_PROJET_EACH_J(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_projet_divergence");
+  hipLaunchKernelGGL(k_projet_divergence_sum, dim3((unsigned)((nsig + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const double*)work_dev, nsig, ng, d_dev);
+  LAUNCHCHK("k_projet_divergence_sum");
+  return 0;
+}
+
+int glowk_projet_separate(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* up_dev, const double* g_dev,
+                          int M, int J, float* y_dev, void* stream) {
+  using namespace glowk_projet;
+  const std::string me("projet_separate");
+  if (int rc = projet_sizes(me, nsig, rows, frames, J)) return rc;
+  if (int rc = projet_model(me, nsig, M, 1, J)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !p_dev || !u_dev || !up_dev || !g_dev || !y_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, p_dev, u_dev, up_dev, g_dev, y_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{y_dev, projet_bytes_p(nsig, J, rows, frames) * 2}, {x_dev, projet_bytes_x(nsig, rows, frames)}, {p_dev, projet_bytes_p(nsig, J, rows, frames)},
+                                 {u_dev, (size_t)M * 16}, {up_dev, (size_t)M * 16}, {g_dev, (size_t)nsig * M * J * 8}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, p_dev, u_dev, up_dev, g_dev, y_dev}, &dev, "projet_separate")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t cells = (int64_t)rows * frames;
+  const int blocks = (int)((cells + THREADS - 1) / THREADS);
+  const dim3 grid((unsigned)((int64_t)nsig * blocks));
+  switch (J) {
+#define GLOWK_CASE(j)                                                                                                                                   \
+  case j:                                                                                                                                               \
+    hipLaunchKernelGGL(k_projet_separate<j>, grid, dim3(THREADS), 0, (hipStream_t)stream, (const float2*)x_dev, p_dev, cells, blocks, u_dev, up_dev, g_dev, M, \
+                       (float2*)y_dev);                                                                                                                 \
+    break;
+    GLOWK_PROJET_EACH_J(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_projet_separate");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 554
+#define GLOWK_VERSION 555
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -988,6 +988,60 @@ int glowk_rpca_fit(const float* m_dev, int nsig, int rows, int frames, double ga
                    int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream);
 int glowk_rpca_binary_mask(const double* l_dev, const double* s_dev, const float* x_dev, size_t count, double gain_mask, float* mask_dev, float* bg_dev,
                            float* fg_dev, void* stream);
+
+/* --- PROJET: panned sources from two channels by projections (Fitzgerald, Liutkus & Badeau 2016; glowk_projet.h) --------------------- */
+/* X [nsig][2][rows][frames] complex64 (re, im interleaved, frames fastest), the STFT of two channels.  nsig in [0, 65535] (0: a
+ * successful no-op), rows in [1, 4096], frames in [1, 32768], M in [2, 32] projections, L in [1, 128] pan positions, J in [1, 8] sources,
+ * alpha in [1, 2], beta in {0, 1, 2}, n_iter in [0, 100000]; nsig J rows frames <= 2^31 - 1 (and nsig M rows frames for the stored
+ * projections).  FLOOR = 2^-40.  Everything after the load of X is fp64 without contraction; every sum has an order that the shapes
+ * alone fix, never nsig or the data; no atomics, no spin waits, no allocation, no host synchronisation: bitwise reproducible, and a
+ * batch gives what its signals give alone.  Conventions as in the IVA section: handle-free, device memory on one device, enqueued on
+ * `stream`, GLOWK_ERR with a glowk_last_error message before anything is launched; tensors a call writes must not overlap its other
+ * tensors; everything 8-byte aligned.  Inputs are finite, P and Q non-negative.  audiosourcesep_amd/projet.py drives the calls and builds
+ * the tables: the library takes tables, not formulas.  Since version 555.
+ *
+ * Tables (float64, shared by the signals of a call): u [M][2], the projection directions; k [M][L], the gain of pan position l seen
+ * through projection m; up [2][M], the pseudo-inverse of u.  State: p [nsig][J][rows][frames] and q [nsig][L][J], float64; g [nsig][M][J]
+ * = k q (l ascending).
+ * Per cell: c_m = u[m][0] X_1 + u[m][1] X_2 (two products and an add per component); V_m = |c_m|^alpha: sqrt(re^2 + im^2) for alpha 1,
+ * re^2 + im^2 for alpha 2, else pow(re^2 + im^2, alpha / 2); sigma_m = max(sum_j p_j g[m][j], FLOOR), j ascending.
+ * With wn_m = V_m sigma_m^(beta - 2) and wd_m = sigma_m^(beta - 1) -- (V, sigma), (V / sigma, 1), (V / (sigma sigma), 1 / sigma) for beta
+ * 2, 1, 0 -- and g(x) = sqrt(x) for beta 0, x otherwise:
+ *   P update: p_j' = p_j g(sum_m g[m][j] wn_m / max(sum_m g[m][j] wd_m, FLOOR)), m ascending.
+ *   Outer sums, with sigma' from p' of the same cell: An[m][j] = sum_cells p_j' wn_m', Ad[m][j] = sum_cells p_j' wd_m', accumulated by
+ *   v_mfma_f64_16x16x4_f64.  A signal's cells are cut into G = ceil(cells / chunk) chunks, chunk = ceil(ceil(cells / min(1024,
+ *   ceil(cells / 256))) / 256) 256 cells, a workgroup each; a wave adds 64 consecutive cells with 16 instructions of four cells, step
+ *   after step of 256 cells; the workgroup adds its four waves in ascending order; the Q kernel adds the G partials in ascending order
+ *   from 0.0.  Longest chain of additions: 64 chunk / 256 + 4 + G.
+ *   Q update: q[l][j]' = q[l][j] g(sum_m k[m][l] An[m][j] / max(sum_m k[m][l] Ad[m][j], FLOOR)), m ascending; then g = k q'.
+ * Divergence: d[sig] = sum_{m, cells} d_beta(V_m | sigma_m) with (V - s)^2 / 2; V ln(V / s) - V + s (0 ln 0 = 0); q - ln q - 1 with q =
+ * max(V, FLOOR) / s.  A thread adds its cells' terms in order (m ascending), a halving tree adds the workgroup, the partials in
+ * ascending order from 0.0.
+ * Separation: w_mj = p_j g[m][j] / sigma_m where sum_j p_j g[m][j] >= FLOOR, else 1 / J; Y_j[ch] = sum_m (up[ch][m] w_mj) c_m, m
+ * ascending, rounded once to complex64; y [nsig][J][2][rows][frames].  up u = I and sum_j w_mj = 1: the stems of a cell add up to X. */
+/* work_dev of update_q, fit and divergence: 16 nsig G M J bytes (the partial outer sums).  0 for arguments out of range. */
+size_t glowk_projet_workspace_bytes(int nsig, int M, int J, int rows, int frames);
+/* v [nsig][M][rows][frames] float64, the same bits as the V the other calls hold in registers.  One launch. */
+int glowk_projet_projections(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, int M, double alpha, double* v_dev, void* stream);
+/* g = k q.  One launch, one workgroup per signal. */
+int glowk_projet_gains(const double* k_dev, const double* q_dev, int nsig, int M, int L, int J, double* g_dev, void* stream);
+/* The P update alone, in place.  One launch. */
+int glowk_projet_update_p(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, const double* g_dev, int M, int J, double alpha, int beta,
+                          double* p_dev, void* stream);
+/* The outer sums from p as given (sigma from g as given), then the Q update in place and g = k q'.  Two launches. */
+int glowk_projet_update_q(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* k_dev, int M, int L, int J,
+                          double alpha, int beta, double* q_dev, double* g_dev, void* work_dev, size_t work_bytes, void* stream);
+/* g = k q, then n_iter iterations in place on p, q and g: one fused pass over X and p (the P update and the outer sums of the new p),
+ * then the Q kernel.  2 n_iter + 1 launches.  Bit for bit glowk_projet_gains, then n_iter times glowk_projet_update_p,
+ * glowk_projet_update_q. */
+int glowk_projet_fit(const float* x_dev, int nsig, int rows, int frames, const double* u_dev, const double* k_dev, int M, int L, int J, double alpha, int beta,
+                     int n_iter, double* p_dev, double* q_dev, double* g_dev, void* work_dev, size_t work_bytes, void* stream);
+/* d [nsig] float64.  Two launches. */
+int glowk_projet_divergence(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* g_dev, int M, int J,
+                            double alpha, int beta, double* d_dev, void* work_dev, size_t work_bytes, void* stream);
+/* y [nsig][J][2][rows][frames] complex64.  One launch. */
+int glowk_projet_separate(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* up_dev, const double* g_dev,
+                          int M, int J, float* y_dev, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
