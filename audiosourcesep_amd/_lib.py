@@ -211,6 +211,13 @@ SYMBOLS = {
     "glowk_projet_fit": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _d, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_projet_divergence": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _d, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_projet_separate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "glowk_cluster_work_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_cluster_init": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_cluster_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_cluster_update": (_i, [_vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_cluster_fit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_cluster_posteriors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_cluster_spatial_features": (_i, [_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -27,6 +27,7 @@
 #include "glowk_melody.h"
 #include "glowk_rpca.h"
 #include "glowk_projet.h"
+#include "glowk_cluster.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -2965,6 +2966,288 @@ int glowk_projet_separate(const float* x_dev, const double* p_dev, int nsig, int
 #undef GLOWK_CASE
   }
   LAUNCHCHK("k_projet_separate");
+  return 0;
+}
+
+// ---- clustering: a weighted Gaussian mixture over time-frequency cells; the moments on the fp64 matrix cores (glowk_cluster.h) ---------------
+namespace {
+int cluster_sizes(const std::string& w, int nsig, int D, int J, int rows, int frames) {
+  using namespace glowk_cluster;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (D < 1 || D > MAX_D) return fail(w + ": the feature count D must be in [1, 8]");
+  if (J < 1 || J > MAX_J) return fail(w + ": the cluster count J must be in [1, 8]");
+  if (!sizes_ok(nsig, D, J, rows, frames)) return fail(w + ": nsig * max(D, J) * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int cluster_reg(const std::string& w, double reg) {
+  if (!(reg >= glowk_cluster::MIN_REG) || !std::isfinite(reg)) return fail(w + ": reg_covar must be finite and at least 2^-40");
+  return 0;
+}
+int cluster_aligned(const std::string& w, std::initializer_list<const void*> f64, std::initializer_list<const void*> f32) {
+  for (const void* p : f64)
+    if ((uintptr_t)p % 8) return fail(w + ": the float64 tensors and the workspace must be aligned to 8 bytes");
+  for (const void* p : f32)
+    if ((uintptr_t)p % 4) return fail(w + ": the float32 and int32 tensors must be aligned to 4 bytes");
+  return 0;
+}
+// the parts of work_dev
+struct ClusterWork {
+  double *partial, *stats, *cons, *ctl;
+};
+ClusterWork cluster_work(void* work, int nsig, int D, int J, int rows, int frames) {
+  using namespace glowk_cluster;
+  ClusterWork cw;
+  cw.partial = (double*)work;
+  cw.stats = cw.partial + work_partials(nsig, D, J, rows, frames);
+  cw.cons = cw.stats + (size_t)nsig * partial_doubles(D, J);
+  cw.ctl = cw.cons + (size_t)nsig * cons_doubles(D, J);
+  return cw;
+}
+size_t cluster_bytes_f(int nsig, int D, int rows, int frames) { return (size_t)nsig * D * rows * frames * 4; }
+size_t cluster_bytes_state(int nsig, int D, int J) { return (size_t)nsig * J * D * D * 8; }
+
+#define GLOWK_CLUSTER_EACH_D(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+
+// the statistics pass: J clusters from the constants (MODE_EM), or one cluster with r = 1 about the constants' origin or about 0
+int cluster_launch_stats(const float* f, const float* w, int nsig, int D, int J, int rows, int frames, int mode, const double* cons, int cons_stride, double* partial,
+                         hipStream_t st) {
+  using namespace glowk_cluster;
+  const int64_t cells = (int64_t)rows * frames;
+  const dim3 grid((unsigned)((int64_t)nsig * groups(cells)));
+  switch (D) {
+#define GLOWK_CASE(d)                                                                                                          \
+  case d:                                                                                                                      \
+    hipLaunchKernelGGL(k_cluster_stats<d>, grid, dim3(THREADS), 0, st, f, w, cells, J, mode, cons, cons_stride, partial);      \
+    break;
+    GLOWK_CLUSTER_EACH_D(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_cluster_stats");
+  return 0;
+}
+// pass 0: W and o (and the origin of the constants)
+int cluster_launch_pass0(const float* f, const float* w, int nsig, int D, int J, int rows, int frames, double* origin, double* total, int32_t* status,
+                         const ClusterWork& cw, hipStream_t st) {
+  using namespace glowk_cluster;
+  const int ng = groups((int64_t)rows * frames);
+  if (int rc = cluster_launch_stats(f, w, nsig, D, 1, rows, frames, MODE_UNIT_ZERO, cw.cons, cons_doubles(D, J), cw.partial, st)) return rc;
+  hipLaunchKernelGGL(k_cluster_origin, dim3((unsigned)nsig), dim3(THREADS), 0, st, (const double*)cw.partial, ng, D, J, origin, total, status, cw.cons);
+  LAUNCHCHK("k_cluster_origin");
+  return 0;
+}
+// the start from the moments about o
+int cluster_launch_start(const float* f, const float* w, int nsig, int D, int J, int rows, int frames, const double* z, double reg, const double* total, double* pi,
+                         double* mu, double* sigma, int32_t* status, const ClusterWork& cw, hipStream_t st) {
+  using namespace glowk_cluster;
+  const int ng = groups((int64_t)rows * frames);
+  if (int rc = cluster_launch_stats(f, w, nsig, D, 1, rows, frames, MODE_UNIT, cw.cons, cons_doubles(D, J), cw.partial, st)) return rc;
+  hipLaunchKernelGGL(k_cluster_start, dim3((unsigned)nsig), dim3(THREADS), 0, st, (const double*)cw.partial, ng, D, J, z, reg, total, pi, mu, sigma, status, cw.cons);
+  LAUNCHCHK("k_cluster_start");
+  return 0;
+}
+int cluster_launch_prepare(int nsig, int D, int J, const double* pi, const double* mu, const double* sigma, const double* origin, const double* total,
+                           int32_t* status, double* cons, hipStream_t st) {
+  using namespace glowk_cluster;
+  hipLaunchKernelGGL(k_cluster_prepare, dim3((unsigned)nsig), dim3(THREADS), 0, st, D, J, pi, mu, sigma, origin, total, status, cons);
+  LAUNCHCHK("k_cluster_prepare");
+  return 0;
+}
+int cluster_launch_update(const double* partial, int ngroups, int nsig, int D, int J, double reg, double tol, int it, double* pi, double* mu, double* sigma,
+                          const double* origin, const double* total, int32_t* status, double* cons, double* ctl, double* ll, int ll_stride, int32_t* iters,
+                          hipStream_t st) {
+  using namespace glowk_cluster;
+  hipLaunchKernelGGL(k_cluster_update, dim3((unsigned)nsig), dim3(THREADS), 0, st, partial, ngroups, D, J, reg, tol, it, pi, mu, sigma, origin, total, status, cons,
+                     ctl, ll, ll_stride, iters);
+  LAUNCHCHK("k_cluster_update");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_cluster_work_bytes(int nsig, int D, int J, int rows, int frames) {
+  using namespace glowk_cluster;
+  if (nsig < 1 || !sizes_ok(nsig, D, J, rows, frames)) return 0;
+  return work_bytes(nsig, D, J, rows, frames);
+}
+
+int glowk_cluster_init(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* z_dev, double reg_covar, double* pi_dev,
+                       double* mu_dev, double* sigma_dev, double* origin_dev, double* total_dev, int32_t* status_dev, void* work_dev, size_t work_bytes,
+                       void* stream) {
+  const std::string me("cluster_init");
+  if (int rc = cluster_sizes(me, nsig, D, J, rows, frames)) return rc;
+  if (int rc = cluster_reg(me, reg_covar)) return rc;
+  if (nsig == 0) return 0;
+  if (!f_dev || !w_dev || !z_dev || !pi_dev || !mu_dev || !sigma_dev || !origin_dev || !total_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_cluster::work_bytes(nsig, D, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_cluster_work_bytes says");
+  if (int rc = cluster_aligned(me, {z_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, work_dev}, {f_dev, w_dev, status_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{pi_dev, (size_t)nsig * J * 8}, {mu_dev, (size_t)nsig * J * D * 8}, {sigma_dev, cluster_bytes_state(nsig, D, J)},
+                                 {origin_dev, (size_t)nsig * D * 8}, {total_dev, (size_t)nsig * 8}, {status_dev, (size_t)nsig * 4}, {work_dev, need},
+                                 {f_dev, cluster_bytes_f(nsig, D, rows, frames)}, {w_dev, cluster_bytes_f(nsig, 1, rows, frames)}, {z_dev, (size_t)J * 8}}, 7))
+    return rc;
+  int dev;
+  if (int rc = audio_device({f_dev, w_dev, z_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, work_dev}, &dev, "cluster_init")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  const ClusterWork cw = cluster_work(work_dev, nsig, D, J, rows, frames);
+  if (int rc = cluster_launch_pass0(f_dev, w_dev, nsig, D, J, rows, frames, origin_dev, total_dev, status_dev, cw, st)) return rc;
+  return cluster_launch_start(f_dev, w_dev, nsig, D, J, rows, frames, z_dev, reg_covar, total_dev, pi_dev, mu_dev, sigma_dev, status_dev, cw, st);
+}
+
+int glowk_cluster_stats(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* pi_dev, const double* mu_dev,
+                        const double* sigma_dev, const double* origin_dev, const double* total_dev, double* stats_dev, int32_t* status_dev, void* work_dev,
+                        size_t work_bytes, void* stream) {
+  using namespace glowk_cluster;
+  const std::string me("cluster_stats");
+  if (int rc = cluster_sizes(me, nsig, D, J, rows, frames)) return rc;
+  if (nsig == 0) return 0;
+  if (!f_dev || !w_dev || !pi_dev || !mu_dev || !sigma_dev || !origin_dev || !total_dev || !stats_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_cluster::work_bytes(nsig, D, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_cluster_work_bytes says");
+  if (int rc = cluster_aligned(me, {pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, stats_dev, work_dev}, {f_dev, w_dev, status_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{stats_dev, (size_t)nsig * partial_doubles(D, J) * 8}, {status_dev, (size_t)nsig * 4}, {work_dev, need}, {pi_dev, (size_t)nsig * J * 8},
+                                 {mu_dev, (size_t)nsig * J * D * 8}, {sigma_dev, cluster_bytes_state(nsig, D, J)}, {origin_dev, (size_t)nsig * D * 8},
+                                 {total_dev, (size_t)nsig * 8}, {f_dev, cluster_bytes_f(nsig, D, rows, frames)}, {w_dev, cluster_bytes_f(nsig, 1, rows, frames)}}, 3))
+    return rc;
+  int dev;
+  if (int rc = audio_device({f_dev, w_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, stats_dev, status_dev, work_dev}, &dev, "cluster_stats")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  const ClusterWork cw = cluster_work(work_dev, nsig, D, J, rows, frames);
+  if (int rc = cluster_launch_prepare(nsig, D, J, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, cw.cons, st)) return rc;
+  if (int rc = cluster_launch_stats(f_dev, w_dev, nsig, D, J, rows, frames, MODE_EM, cw.cons, cons_doubles(D, J), cw.partial, st)) return rc;
+  hipLaunchKernelGGL(k_cluster_sum, dim3((unsigned)nsig), dim3(THREADS), 0, st, (const double*)cw.partial, groups((int64_t)rows * frames), (int)partial_doubles(D, J),
+                     stats_dev);
+  LAUNCHCHK("k_cluster_sum");
+  return 0;
+}
+
+int glowk_cluster_update(const double* stats_dev, int nsig, int D, int J, double reg_covar, double* pi_dev, double* mu_dev, double* sigma_dev,
+                         const double* origin_dev, const double* total_dev, double* ll_dev, int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_cluster;
+  const std::string me("cluster_update");
+  if (int rc = cluster_sizes(me, nsig, D, J, 1, 1)) return rc;
+  if (int rc = cluster_reg(me, reg_covar)) return rc;
+  if (nsig == 0) return 0;
+  if (!stats_dev || !pi_dev || !mu_dev || !sigma_dev || !origin_dev || !total_dev || !ll_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = (size_t)nsig * cons_doubles(D, J) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than 8 nsig (D + J (1 + D + D D))");
+  if (int rc = cluster_aligned(me, {stats_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, ll_dev, work_dev}, {status_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{pi_dev, (size_t)nsig * J * 8}, {mu_dev, (size_t)nsig * J * D * 8}, {sigma_dev, cluster_bytes_state(nsig, D, J)},
+                                 {ll_dev, (size_t)nsig * 8}, {status_dev, (size_t)nsig * 4}, {work_dev, need}, {stats_dev, (size_t)nsig * partial_doubles(D, J) * 8},
+                                 {origin_dev, (size_t)nsig * D * 8}, {total_dev, (size_t)nsig * 8}}, 6))
+    return rc;
+  int dev;
+  if (int rc = audio_device({stats_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, ll_dev, status_dev, work_dev}, &dev, "cluster_update")) return rc;
+  DeviceGuard dg(dev);
+  return cluster_launch_update(stats_dev, 1, nsig, D, J, reg_covar, 0.0, 0, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, (double*)work_dev, nullptr,
+                               ll_dev, 1, nullptr, (hipStream_t)stream);
+}
+
+int glowk_cluster_fit(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* z_dev, double reg_covar, int n_iter,
+                      double tol, double* pi_dev, double* mu_dev, double* sigma_dev, double* origin_dev, double* total_dev, double* ll_dev, int32_t* iters_dev,
+                      int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_cluster;
+  const std::string me("cluster_fit");
+  if (int rc = cluster_sizes(me, nsig, D, J, rows, frames)) return rc;
+  if (int rc = cluster_reg(me, reg_covar)) return rc;
+  if (n_iter < 0 || n_iter > MAX_ITER) return fail(me + ": n_iter must be in [0, 100000]");
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(me + ": tol must be finite and at least 0");
+  if (nsig == 0) return 0;
+  if (!f_dev || !w_dev || !pi_dev || !mu_dev || !sigma_dev || !origin_dev || !total_dev || !iters_dev || !status_dev || !work_dev || (n_iter > 0 && !ll_dev))
+    return fail("null tensor");
+  const size_t need = glowk_cluster::work_bytes(nsig, D, J, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_cluster_work_bytes says");
+  if (int rc = cluster_aligned(me, {z_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, ll_dev, work_dev}, {f_dev, w_dev, iters_dev, status_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{pi_dev, (size_t)nsig * J * 8}, {mu_dev, (size_t)nsig * J * D * 8}, {sigma_dev, cluster_bytes_state(nsig, D, J)},
+                                 {origin_dev, (size_t)nsig * D * 8}, {total_dev, (size_t)nsig * 8}, {ll_dev, (size_t)nsig * n_iter * 8}, {iters_dev, (size_t)nsig * 4},
+                                 {status_dev, (size_t)nsig * 4}, {work_dev, need}, {f_dev, cluster_bytes_f(nsig, D, rows, frames)},
+                                 {w_dev, cluster_bytes_f(nsig, 1, rows, frames)}, {z_dev, (size_t)J * 8}}, 9))
+    return rc;
+  int dev;
+  if (int rc = audio_device({f_dev, w_dev, z_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, ll_dev, iters_dev, status_dev, work_dev}, &dev, "cluster_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  const ClusterWork cw = cluster_work(work_dev, nsig, D, J, rows, frames);
+  const int ng = groups((int64_t)rows * frames);
+  if (int rc = cluster_launch_pass0(f_dev, w_dev, nsig, D, J, rows, frames, origin_dev, total_dev, status_dev, cw, st)) return rc;
+  if (z_dev) {
+    if (int rc = cluster_launch_start(f_dev, w_dev, nsig, D, J, rows, frames, z_dev, reg_covar, total_dev, pi_dev, mu_dev, sigma_dev, status_dev, cw, st)) return rc;
+  } else {
+    if (int rc = cluster_launch_prepare(nsig, D, J, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, cw.cons, st)) return rc;
+  }
+  hipLaunchKernelGGL(k_cluster_reset, dim3((unsigned)((nsig + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, nsig, cw.ctl, iters_dev);
+  LAUNCHCHK("k_cluster_reset");
+  for (int it = 0; it < n_iter; ++it) {
+    if (int rc = cluster_launch_stats(f_dev, w_dev, nsig, D, J, rows, frames, MODE_EM, cw.cons, cons_doubles(D, J), cw.partial, st)) return rc;
+    if (int rc = cluster_launch_update(cw.partial, ng, nsig, D, J, reg_covar, tol, it, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, cw.cons, cw.ctl,
+                                       ll_dev, n_iter, iters_dev, st))
+      return rc;
+  }
+  return 0;
+}
+
+int glowk_cluster_posteriors(const float* f_dev, int nsig, int D, int J, int rows, int frames, const double* pi_dev, const double* mu_dev, const double* sigma_dev,
+                             const double* origin_dev, const double* total_dev, const float* x_dev, int C, float* mask_dev, float* y_dev, int32_t* status_dev,
+                             void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_cluster;
+  const std::string me("cluster_posteriors");
+  if (int rc = cluster_sizes(me, nsig, D, J, rows, frames)) return rc;
+  if (x_dev && (C < 1 || C > 2)) return fail(me + ": the channel count C must be 1 or 2");
+  if (x_dev && (int64_t)nsig * J * C * rows * frames > MAX_ELEMENTS) return fail(me + ": nsig * J * C * rows * frames must be at most 2^31 - 1");
+  if ((x_dev == nullptr) != (y_dev == nullptr)) return fail(me + ": x_dev and y_dev go together");
+  if (nsig == 0) return 0;
+  if (!f_dev || !pi_dev || !mu_dev || !sigma_dev || !origin_dev || !total_dev || !mask_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = (size_t)nsig * cons_doubles(D, J) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than 8 nsig (D + J (1 + D + D D))");
+  if (int rc = cluster_aligned(me, {pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, work_dev, x_dev, y_dev}, {f_dev, mask_dev, status_dev})) return rc;
+  const size_t cells = (size_t)rows * frames;
+  if (int rc = iva_disjoint(me, {{mask_dev, (size_t)nsig * J * cells * 4}, {y_dev, y_dev ? (size_t)nsig * J * C * cells * 8 : 0}, {status_dev, (size_t)nsig * 4},
+                                 {work_dev, need}, {f_dev, cluster_bytes_f(nsig, D, rows, frames)}, {x_dev, x_dev ? (size_t)nsig * C * cells * 8 : 0},
+                                 {pi_dev, (size_t)nsig * J * 8}, {mu_dev, (size_t)nsig * J * D * 8}, {sigma_dev, cluster_bytes_state(nsig, D, J)},
+                                 {origin_dev, (size_t)nsig * D * 8}, {total_dev, (size_t)nsig * 8}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({f_dev, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, x_dev, mask_dev, y_dev, status_dev, work_dev}, &dev, "cluster_posteriors")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = cluster_launch_prepare(nsig, D, J, pi_dev, mu_dev, sigma_dev, origin_dev, total_dev, status_dev, (double*)work_dev, st)) return rc;
+  const int blocks = (int)((cells + THREADS - 1) / THREADS);
+  const dim3 grid((unsigned)((int64_t)nsig * blocks));
+  switch (D) {
+#define GLOWK_CASE(d)                                                                                                                                       \
+  case d:                                                                                                                                                   \
+    hipLaunchKernelGGL(k_cluster_posteriors<d>, grid, dim3(THREADS), 0, st, f_dev, (int64_t)cells, blocks, J, (const double*)work_dev, (const float2*)x_dev, C, \
+                       mask_dev, (float2*)y_dev);                                                                                                           \
+    break;
+    GLOWK_CLUSTER_EACH_D(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_cluster_posteriors");
+  return 0;
+}
+
+int glowk_cluster_spatial_features(const float* x_dev, int nsig, int rows, int frames, int delay, double max_delay, double p, float* feat_dev, float* w_dev,
+                                   void* stream) {
+  using namespace glowk_cluster;
+  const std::string me("cluster_spatial_features");
+  if (int rc = cluster_sizes(me, nsig, 2, 1, rows, frames)) return rc;
+  if (delay != 0 && delay != 1) return fail(me + ": delay must be 0 or 1");
+  if (!(max_delay > 0.0) || !std::isfinite(max_delay)) return fail(me + ": max_delay must be finite and positive");
+  if (!(p > 0.0) || !std::isfinite(p)) return fail(me + ": p must be finite and positive");
+  if (nsig == 0) return 0;
+  if (!x_dev || !feat_dev || !w_dev) return fail("null tensor");
+  if (int rc = cluster_aligned(me, {x_dev}, {feat_dev, w_dev})) return rc;
+  const size_t cells = (size_t)rows * frames;
+  if (int rc = iva_disjoint(me, {{feat_dev, (size_t)nsig * (1 + delay) * cells * 4}, {w_dev, (size_t)nsig * cells * 4}, {x_dev, (size_t)nsig * 2 * cells * 8}}, 2)) return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, feat_dev, w_dev}, &dev, "cluster_spatial_features")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t total = (int64_t)cells * nsig;
+  hipLaunchKernelGGL(k_cluster_spatial, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, (const float2*)x_dev, total, rows,
+                     frames, delay, max_delay, p, feat_dev, w_dev);
+  LAUNCHCHK("k_cluster_spatial");
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 555
+#define GLOWK_VERSION 556
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -1042,6 +1042,94 @@ int glowk_projet_divergence(const float* x_dev, const double* p_dev, int nsig, i
 /* y [nsig][J][2][rows][frames] complex64.  One launch. */
 int glowk_projet_separate(const float* x_dev, const double* p_dev, int nsig, int rows, int frames, const double* u_dev, const double* up_dev, const double* g_dev,
                           int M, int J, float* y_dev, void* stream);
+
+/* --- Clustering: a weighted Gaussian mixture over time-frequency cells (nussl's PrimitiveClustering, Seetharaman et al. 2019, and ----- */
+/* --- SpatialClustering; glowk_cluster.h) ---------------------------------------------------------------------------------------------- */
+/* f [nsig][D][rows][frames] float32 features (planes, frames fastest; cell c = r frames + t), w [nsig][rows][frames] float32 weights,
+ * non-negative and finite.  nsig in [0, 65535] (0: a successful no-op), rows in [1, 4096], frames in [1, 32768], D in [1, 8] features,
+ * J in [1, 8] clusters, nsig max(D, J) rows frames <= 2^31 - 1, reg_covar finite and >= 2^-40, tol finite and >= 0, n_iter in [0, 100000].
+ * Only full covariances.  A batch is independent signals.  Everything after the float32 loads is fp64 without contraction (the
+ * matrix-core instruction is the one fused operation); every sum has an order that the shapes alone fix, never nsig or the data; no
+ * atomics, no spin waits, no allocation, no host synchronisation: bitwise reproducible, and a batch gives what its signals give alone.
+ * Conventions as in the PROJET section: handle-free, device memory on one device, enqueued on `stream`, GLOWK_ERR with a
+ * glowk_last_error message before anything is launched; tensors a call writes must not overlap its other tensors; float64 tensors and
+ * workspaces 8-byte aligned, the others 4.  audiosourcesep_amd/cluster.py drives the calls.  Since version 556.
+ *
+ * State (float64): pi [nsig][J], mu [nsig][J][D], sigma [nsig][J][D][D], origin o [nsig][D], total W [nsig].
+ * Pass 0: W = sum w, o = sum w x / W.  All later moments are of u = x - o, so that B / N - (a / N)(a / N)^T does not cancel against the
+ * features' offset.
+ * Per cluster: Cholesky sigma_j = L L^T (row by row, the sums in ascending order), Linv = L^-1 by forward substitution, k_j = (log pi_j
+ * - sum_d log L[d][d]) - D log(2 pi) / 2.
+ * Per cell: y = Linv (x - mu_j) (columns ascending), l_j = k_j - |y|^2 / 2, m = max_j l_j, e_j = exp(l_j - m), s = sum_j e_j in ascending
+ * j, lse = m + log s, r_j = e_j / s.
+ * Statistics: N_j = sum w r_j, a_j = sum w r_j u, B_j = sum w r_j u u^T (the upper triangle; the update mirrors it, so sigma is bitwise
+ * symmetric), LL = sum w lse.  stats [nsig][J (1 + D + D (D + 1) / 2) + 1]: per cluster N, a [D], B[a][b] for a <= b (a ascending, then
+ * b); then LL.  They are R^T Phi with R [cells][J] = w r_j (and a row of w for LL) and Phi [cells][P] = (1, u, u u^T upper, lse),
+ * accumulated by v_mfma_f64_16x16x4_f64.  A signal's cells are cut into G = ceil(cells / chunk) chunks, chunk = ceil(ceil(cells /
+ * min(1024, ceil(cells / 256))) / 256) 256 cells, a workgroup each; a wave adds 64 consecutive cells with 16 instructions of four
+ * cells, step after step of 256 cells; the workgroup adds its four waves in ascending order; the per-signal kernel adds the G partials
+ * in ascending order from 0.0.  Longest chain of additions: chain = 64 chunk / 256 + 4 + G.
+ * Update: pi_j = N_j / W, mu_j = o + a_j / N_j, sigma_j = B_j / N_j - (a_j / N_j)(a_j / N_j)^T + reg_covar I.  A cluster with N_j <
+ * 2^-40 W is dead: its mu and sigma stay, its pi is 0, so its r_j is an exact 0 from then on.  A non-positive (or NaN) Cholesky pivot in
+ * any cluster leaves the signal's whole state as it was and, in a fit, freezes the signal.  W == 0 leaves the state alone.
+ * Status bits (int32 per signal): 1, all weights are zero (posteriors 1 / J); 2, a cluster is dead; 4, a Cholesky factorisation failed
+ * (in glowk_cluster_stats and glowk_cluster_posteriors, of the state as given: posteriors 1 / J).
+ * Stop: ll_k = LL / W is the likelihood of the state before update k = 0, 1, ..  With tol > 0 a signal stops after update k >= 1 when
+ * ll_k - ll_{k-1} <= tol |ll_k|; update k is applied, then the signal is frozen: iters = k + 1, and ll of later k is NaN.  tol == 0
+ * runs all n_iter.
+ * Start (z_dev [J], the standard-normal quantiles of (j + 1/2) / J: the library takes tables, not formulas): Sigma0 = B / W - (a / W)(a
+ * / W)^T + reg_covar I from a second pass about o; v = 64 power-iteration steps on Sigma0 from all ones, divided by its Euclidean norm
+ * each step, the sign such that the earliest component of largest magnitude is positive; lambda = v^T Sigma0 v; mu_j = (o + a / W) +
+ * (z_j sqrt(lambda)) v, sigma_j = Sigma0, pi_j = 1 / J.  W == 0: pi = 1 / J, mu = 0, sigma = I.
+ * Posteriors: mask [nsig][J][rows][frames] float32 = r_j rounded; with x [nsig][C][rows][frames] complex64, C in {1, 2}, also y
+ * [nsig][J][C][rows][frames] = mask_j x, each component one float32 product.
+ * Spatial features of x [nsig][2][rows][frames] complex64: pan = atan2(|X2|, |X1|) - pi / 4; with delay, delta = -arg(X2 conj X1) /
+ * omega_r clipped to +-max_delay (omega_r = 2 pi r / (2 (rows - 1)); 0 in row 0 and where a channel is exactly 0); w = (|X1|^2 +
+ * |X2|^2)^(p / 2) (sqrt for p 1, itself for p 2, else pow), 0 in row 0 and where both channels are exactly 0.  fp64, rounded to float32;
+ * feat [nsig][1 + delay][rows][frames].
+ *
+ * Error bound of the statistics against exact arithmetic on the same float32 inputs and float64 constants, with eps = 2^-53.  The
+ * quadratic form q_j = |Linv (x - mu_j)|^2 is D (D + 1) / 2 products and as many additions of terms whose absolute values sum to at
+ * most q~_j = | |Linv| |x - mu_j| |^2; each y_a carries at most (D + 1) eps relative to its absolute sum and the squares and their sum
+ * another D + 1, so |dq_j| <= 2 (D + 2) eps q~_j (1 + O(eps)); l_j = k_j - q_j / 2 adds one rounding of |l_j| <= |k_j| + q~_j / 2.  exp and
+ * log are within 1 ulp (2 eps): |dl_j| <= eps e_j with e_j = 4 (D + 2)^2 (q~_j + |k_j| + 1) is a generous cover of all of it.  With
+ * r_j = exp(l_j) / sum_i exp(l_i): |dr_j| / r_j <= |dl_j| + sum_i r_i |dl_i| + 4 eps (two exp, the sum's ratio, the division), so |dr_j|
+ * <= eps r_j (e_j + sum_i r_i e_i + 4).  A statistic sum_c w r_j phi then differs by at most
+ *   eps [ chain sum_c w r_j |phi| + sum_c w |phi| r_j (e_j + sum_i r_i e_i + 4) ]
+ * (the first term is the summation in the order above, the products w r_j and u_a u_b included in the 4), and LL by at most
+ *   eps [ chain sum_c w |lse| + sum_c w (|lse| + max_j e_j) ].
+ * Update: Cholesky and the triangular solves are backward stable; every element of the new state is within eps 64 D^2 (1 + cond(sigma_j))
+ * of the exact update of the same statistics, relative to the element's scale (max |sigma_j| for sigma, max(|mu_j|, sqrt(max |sigma_j|))
+ * for mu, 1 for pi). */
+/* work_dev: 8 (nsig G (J (P - 1) + 1) + nsig (J (P - 1) + 1) + nsig (D + J (1 + D + D D)) + 2 nsig) bytes, P = 2 + D + D (D + 1) / 2.  0
+ * for arguments out of range. */
+size_t glowk_cluster_work_bytes(int nsig, int D, int J, int rows, int frames);
+/* Pass 0 and the start.  status is written.  Four launches. */
+int glowk_cluster_init(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* z_dev, double reg_covar, double* pi_dev,
+                       double* mu_dev, double* sigma_dev, double* origin_dev, double* total_dev, int32_t* status_dev, void* work_dev, size_t work_bytes,
+                       void* stream);
+/* The statistics of the state as given.  status is written (bits 1 and 4).  Three launches. */
+int glowk_cluster_stats(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* pi_dev, const double* mu_dev,
+                        const double* sigma_dev, const double* origin_dev, const double* total_dev, double* stats_dev, int32_t* status_dev, void* work_dev,
+                        size_t work_bytes, void* stream);
+/* The update from statistics, in place on pi, mu, sigma; ll [nsig] = LL / W (NaN for W == 0); bits are ORed into status.  work_dev: 8
+ * nsig (D + J (1 + D + D D)) bytes.  One launch. */
+int glowk_cluster_update(const double* stats_dev, int nsig, int D, int J, double reg_covar, double* pi_dev, double* mu_dev, double* sigma_dev,
+                         const double* origin_dev, const double* total_dev, double* ll_dev, int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream);
+/* The whole loop: pass 0 (origin, total), the start (z_dev) or, with z_dev null, the state as given in pi, mu, sigma; then n_iter times
+ * the statistics pass and the per-signal kernel.  ll [nsig][n_iter], iters and status [nsig] int32.  Four or five launches and two per
+ * iteration.  Bit for bit glowk_cluster_init, then n_iter times glowk_cluster_stats, glowk_cluster_update. */
+int glowk_cluster_fit(const float* f_dev, const float* w_dev, int nsig, int D, int J, int rows, int frames, const double* z_dev, double reg_covar, int n_iter,
+                      double tol, double* pi_dev, double* mu_dev, double* sigma_dev, double* origin_dev, double* total_dev, double* ll_dev, int32_t* iters_dev,
+                      int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream);
+/* The masks and, with x_dev (then y_dev too), the masked spectra.  status is written (bits 1 and 4).  work_dev as for the update.  Two
+ * launches. */
+int glowk_cluster_posteriors(const float* f_dev, int nsig, int D, int J, int rows, int frames, const double* pi_dev, const double* mu_dev, const double* sigma_dev,
+                             const double* origin_dev, const double* total_dev, const float* x_dev, int C, float* mask_dev, float* y_dev, int32_t* status_dev,
+                             void* work_dev, size_t work_bytes, void* stream);
+/* One launch. */
+int glowk_cluster_spatial_features(const float* x_dev, int nsig, int rows, int frames, int delay, double max_delay, double p, float* feat_dev, float* w_dev,
+                                   void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
