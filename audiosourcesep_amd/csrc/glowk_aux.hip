@@ -1122,6 +1122,8 @@ int nn_ranges(const char* what, int nsig, int rows, int frames, int k) {
 }
 // the workspace: the norms [nsig][frames], then the frame-major copy [nsig][frames][rows]
 size_t nn_work_floats(int nsig, int rows, int frames) { return (size_t)nsig * frames * ((size_t)rows + 1); }
+// in bytes, rounded up to 8 as every other size query is: a caller that allocates its workspaces in 8-byte words gets all of it
+size_t nn_work_bytes(int nsig, int rows, int frames) { return (nn_work_floats(nsig, rows, frames) * sizeof(float) + 7) / 8 * 8; }
 bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
   return p < q + nb && q < p + na;
@@ -1130,7 +1132,7 @@ bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
 
 size_t glowk_nn_workspace_bytes(int nsig, int rows, int frames, int k) {
   if (nn_ranges("nn_workspace_bytes", nsig, rows, frames, k)) return 0;
-  return nn_work_floats(nsig, rows, frames) * sizeof(float);
+  return nn_work_bytes(nsig, rows, frames);
 }
 
 int glowk_nn_neighbors(const float* s_dev, int nsig, int rows, int frames, int k, int width, int32_t* idx_dev, float* sim_dev,
@@ -1140,7 +1142,7 @@ int glowk_nn_neighbors(const float* s_dev, int nsig, int rows, int frames, int k
   if (width < 1 || width > MAX_WIDTH) return fail("nn_neighbors: width must be in [1, 2^20]");
   if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
   if (!s_dev || !idx_dev || !work_dev) return fail("null tensor");
-  const size_t need = nn_work_floats(nsig, rows, frames) * sizeof(float);
+  const size_t need = nn_work_bytes(nsig, rows, frames);
   if (work_bytes < need) return fail("nn_neighbors: work_bytes is smaller than glowk_nn_workspace_bytes says");
   const size_t n = (size_t)nsig * rows * frames * 4, nk = (size_t)nsig * frames * k * 4;
   if (bytes_overlap(s_dev, n, idx_dev, nk) || (sim_dev && bytes_overlap(s_dev, n, sim_dev, nk)) || (sim_dev && bytes_overlap(idx_dev, nk, sim_dev, nk)))
@@ -1172,7 +1174,7 @@ int glowk_nn_median(const float* s_dev, const int32_t* idx_dev, int nsig, int ro
   if (int rc = nn_ranges("nn_median", nsig, rows, frames, k)) return rc;
   if (nsig == 0) return 0;
   if (!s_dev || !idx_dev || !out_dev || !work_dev) return fail("null tensor");
-  const size_t need = nn_work_floats(nsig, rows, frames) * sizeof(float);
+  const size_t need = nn_work_bytes(nsig, rows, frames);
   if (work_bytes < need) return fail("nn_median: work_bytes is smaller than glowk_nn_workspace_bytes says");
   const size_t n = (size_t)nsig * rows * frames * 4, nk = (size_t)nsig * frames * k * 4;
   if (bytes_overlap(s_dev, n, out_dev, n)) return fail("nn_median: out_dev must not be s_dev (the filter does not run in place)");

@@ -613,7 +613,8 @@ int glowk_hpss_mask(const float* harm_dev, const float* perc_dev, const float* s
  * frames and nsig * frames * k at most 2^31 - 1.  audiosourcesep_amd/repet.py drives the calls; the two masks of REPET-SIM are
  * glowk_hpss_mask(harm = min(s, filt), perc = s - min(s, filt)).  Since version 520. */
 /* The bytes of work_dev that glowk_nn_neighbors and glowk_nn_median need for these shapes: the frame norms and a frame-major copy
- * of s, 4 nsig frames (rows + 1) -- linear in frames; there is no frames x frames matrix anywhere.  0 for arguments out of range. */
+ * of s, 4 nsig frames (rows + 1) rounded up to a multiple of 8 (as every size query here is) -- linear in frames; there is no
+ * frames x frames matrix anywhere.  0 for arguments out of range. */
 size_t glowk_nn_workspace_bytes(int nsig, int rows, int frames, int k);
 /* The neighbours of every frame.  sim(i, j) = <s[:, i], s[:, j]> / max(|s[:, i]| |s[:, j]|, FLT_MIN), so a silent frame has
  * similarity 0 to everything; the dot product is an fp32 fma chain over the rows in row order on the fp32 matrix cores, the same

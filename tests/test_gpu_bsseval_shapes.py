@@ -34,6 +34,7 @@ import torch
 
 from audiosourcesep_amd import _lib, bsseval
 from tests import bsseval_ref as R
+from tests.footprint import Guarded
 from tests.test_bsseval_cpu import assert_metrics
 from tests.test_gpu_bsseval import TOL_SYNTH_DB, synthetic
 
@@ -136,25 +137,6 @@ def test_one_long_window():
 
 
 # ---- the C entry points on descriptors outside the tensors ---------------------------------------------------------------------
-CANARY, GUARD = -7.25, 64
-
-
-class Guarded:
-    """A device buffer with GUARD canary words on each side of the part a call may write."""
-
-    def __init__(self, shape, dtype, fill, canary=CANARY):
-        self.n, self.canary = int(np.prod(shape)), canary
-        self.buf = torch.full((self.n + 2 * GUARD,), canary, dtype=dtype, device="cuda")
-        self.t = self.buf[GUARD:GUARD + self.n].view(shape)
-        self.t.fill_(fill)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.t.data_ptr())
-
-    def intact(self):
-        return bool((self.buf[:GUARD] == self.canary).all()) and bool((self.buf[GUARD + self.n:] == self.canary).all())
-
-
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 

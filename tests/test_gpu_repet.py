@@ -7,6 +7,7 @@ leaves no doubt (one row: every cosine is 1 or 0; the planted input: the gap is 
 is a selection, and at an even count one fp32 (a + b) * 0.5.  Masks: 1e-6 absolute against the fp64 restatement fed the device's
 own filter output, the bar of tests/test_gpu_hpss.py, whose kernel this is.  Audio: 1e-5 of the mixture's peak over every sample,
 the bar of the HPSS stems, whose inversion this is."""
+import ctypes
 import functools
 import wave
 
@@ -14,9 +15,10 @@ import numpy as np
 import pytest
 import torch
 
-from audiosourcesep_amd import audio, repet
+from audiosourcesep_amd import _lib, audio, repet
 from tests import audio_ref as A
 from tests import repet_ref as R
+from tests.footprint import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +148,27 @@ def test_nn_filter_defaults_and_empty_batches():
 
 
 # ---- repet_sim -----------------------------------------------------------------------------------------------------------------------
+def test_the_workspace_query_is_whole_words_and_both_calls_stay_inside_it():
+    """(1, 2, 31): 31 norms and 62 copied values are 93 floats, an odd count; glowk_nn_workspace_bytes rounds them up to 8-byte words, as
+    every other size query does.  Through the C ABI with canaries around the workspace and the outputs: nothing outside is written and the
+    results are the wrapper's."""
+    nsig, rows, F, k, width = 1, 2, 31, 16, 1
+    lib = _lib.load()
+    nbytes = lib.glowk_nn_workspace_bytes(nsig, rows, F, k)
+    assert nbytes == 376 and nbytes % 8 == 0
+    S = torch.from_numpy(spectra((nsig, rows, F, k, width))).cuda()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    work = Guarded((nbytes // 4,), torch.float32, float("nan"))
+    idx, sim = Guarded((nsig, F, k), torch.int32, -9, canary=77), Guarded((nsig, F, k), torch.float32, float("nan"))
+    out = Guarded((nsig, rows, F), torch.float32, float("nan"))
+    assert lib.glowk_nn_neighbors(p(S), nsig, rows, F, k, width, idx.ptr(), sim.ptr(), work.ptr(), nbytes, None) == 0
+    assert lib.glowk_nn_median(p(S), idx.ptr(), nsig, rows, F, k, out.ptr(), work.ptr(), nbytes, None) == 0
+    torch.cuda.synchronize()
+    assert work.intact() and idx.intact() and sim.intact() and out.intact()
+    want_out, want_idx = repet.nn_filter(S, k, width, return_neighbors=True)
+    assert torch.equal(idx.t, want_idx) and torch.equal(out.t, want_out) and not bool(torch.isnan(sim.t).any())
+
+
 POWERS = [1.0, 2.0, float("inf")]
 MARGINS = [(1.0, 1.0), (2.0, 10.0)]
 

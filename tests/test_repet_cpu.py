@@ -181,8 +181,11 @@ def _err(lib):
 
 
 def test_the_workspace_is_positive_and_linear_in_the_frames(lib):
-    for nsig, rows, F, k in [(1, 1, 1, 1), (1, 1025, 5626, 150), (3, 33, 129, 8), (1, 4096, 66, 6), (1, 5, 600, 512), (2, 96, 16384, 512)]:
+    for nsig, rows, F, k in [(1, 1, 1, 1), (1, 1025, 5626, 150), (3, 33, 129, 8), (1, 4096, 66, 6), (1, 5, 600, 512), (2, 96, 16384, 512),
+                             (1, 2, 31, 16), (3, 33, 95, 3)]:
         one, two = lib.glowk_nn_workspace_bytes(nsig, rows, F, k), lib.glowk_nn_workspace_bytes(nsig, rows, 2 * F, k)
+        assert one == (4 * nsig * F * (rows + 1) + 7) // 8 * 8                       # the norms and the frame-major copy, in 8-byte words:
+        assert one % 8 == 0                                                         # 93 and 9690 floats (the last two) are odd counts
         assert one > 0 and two <= 2 * one + 65536, (nsig, rows, F, k)
         assert one <= 4 * nsig * F * (rows + k) + 65536                            # like nsig frames (rows + k), never frames^2
     for args in [(-1, 12, 30, 4), (65536, 12, 30, 4), (1, 0, 30, 4), (1, 4097, 30, 4), (1, 12, 0, 4), (1, 12, 32769, 4), (1, 12, 30, 0),
