@@ -218,6 +218,10 @@ SYMBOLS = {
     "glowk_cluster_fit": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_cluster_posteriors": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_cluster_spatial_features": (_i, [_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
+    "glowk_kam_median": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "glowk_kam_backfit": (_i, [_vp, _vp, _i, _i, ctypes.c_size_t, ctypes.c_float, _vp, _vp, _vp]),
+    "glowk_kam_work_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _vp]),
+    "glowk_kam_fit": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -28,6 +28,7 @@
 #include "glowk_rpca.h"
 #include "glowk_projet.h"
 #include "glowk_cluster.h"
+#include "glowk_kam.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -3250,6 +3251,171 @@ int glowk_cluster_spatial_features(const float* x_dev, int nsig, int rows, int f
   hipLaunchKernelGGL(k_cluster_spatial, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, (const float2*)x_dev, total, rows,
                      frames, delay, max_delay, p, feat_dev, w_dev);
   LAUNCHCHK("k_cluster_spatial");
+  return 0;
+}
+
+// ---- kernel additive modelling: sparse-kernel medians with back-fitting (glowk_kam.h) ------------------------------------------------------
+namespace {
+int kam_sizes(const std::string& w, int nsig, int rows, int frames, int J) {
+  using namespace glowk_kam;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (J < 1 || J > MAX_J) return fail(w + ": J must be in [1, 8]");
+  if (!sizes_ok(nsig, rows, frames, J)) return fail(w + ": nsig * J * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int kam_offsets(const std::string& w, const int32_t* offsets, int n) {
+  using namespace glowk_kam;
+  if (n < 1 || n > MAX_N) return fail(w + ": n, the number of offsets, must be in [1, 127]");
+  if (!offsets) return fail(w + ": the offset table is null");
+  if (!offsets_ok(offsets, n)) return fail(w + ": every offset needs |d_row| <= 4095 and |d_frame| <= 32767");
+  return 0;
+}
+int kam_power(const std::string& w, float power) {
+  if (!(power > 0.0f) || !std::isfinite(power)) return fail(w + ": power must be finite and > 0");
+  return 0;
+}
+// one filter over an offset table; signals s_stride / out_stride floats apart
+int kam_launch_median(const float* s, int64_t s_stride, int nsig, int rows, int frames, const int32_t* offsets, int n, float* out, int64_t out_stride,
+                      hipStream_t st) {
+  using namespace glowk_kam;
+  const dim3 grid((unsigned)blocks(nsig, rows, frames, n)), block(waves(n) * 64);
+  if (candidates(n) == 8)
+    hipLaunchKernelGGL(k_kam_median<8>, grid, block, lds_bytes(n), st, s, s_stride, rows, frames, units(nsig, rows, frames), pack(offsets, n), n, out, out_stride);
+  else
+    hipLaunchKernelGGL(k_kam_median<4>, grid, block, lds_bytes(n), st, s, s_stride, rows, frames, units(nsig, rows, frames), pack(offsets, n), n, out, out_stride);
+  LAUNCHCHK("k_kam_median");
+  return 0;
+}
+int kam_launch_backfit(const float* v, const float* a, int nsig, int J, int64_t n, float power, float* p, float* mask, hipStream_t st) {
+  using namespace glowk_kam;
+  const int64_t total = (int64_t)nsig * n;
+  switch (J) {
+#define GLOWK_CASE(j) case j: hipLaunchKernelGGL(k_kam_backfit<j>, dim3(stride_grid(total)), dim3(256), 0, st, v, a, total, n, power, p, mask); break;
+    GLOWK_KAM_EACH_J(GLOWK_CASE)
+#undef GLOWK_CASE
+  }
+  LAUNCHCHK("k_kam_backfit");
+  return 0;
+}
+// the models of glowk_kam_fit: 0 or an error; has_idx: a source has a frame-neighbour model
+int kam_models(const std::string& w, int nsig, int frames, int J, const int32_t* model_n, const int32_t* offsets, const int32_t* model_k, bool* has_idx) {
+  *has_idx = false;
+  if (!model_n || !model_k) return fail(w + ": model_n and model_k are null");
+  size_t at = 0;
+  for (int j = 0; j < J; ++j) {
+    if ((model_n[j] != 0) == (model_k[j] != 0)) return fail(w + ": every source needs exactly one of model_n (an offset table) and model_k (a frame-neighbour tensor)");
+    if (model_n[j]) {
+      if (int rc = kam_offsets(w, offsets ? offsets + 2 * at : nullptr, model_n[j])) return rc;
+      at += (size_t)model_n[j];
+    } else {
+      if (int rc = nn_ranges(w.c_str(), nsig, 1, frames, model_k[j])) return rc;
+      *has_idx = true;
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+int glowk_kam_median(const float* s_dev, int nsig, int rows, int frames, const int32_t* offsets, int n, float* out_dev, void* stream) {
+  const std::string me("kam_median");
+  if (int rc = kam_sizes(me, nsig, rows, frames, 1)) return rc;
+  if (int rc = kam_offsets(me, offsets, n)) return rc;
+  if (nsig == 0) return 0;                     // nothing to read or write: an empty tensor has no storage, its pointer may be null
+  if (!s_dev || !out_dev) return fail("null tensor");
+  const size_t cells = (size_t)nsig * rows * frames;
+  if (floats_overlap(s_dev, cells, out_dev, cells)) return fail(me + ": out_dev must not be s_dev (the filter does not run in place)");
+  int dev;
+  if (int rc = audio_device({s_dev, out_dev}, &dev, "kam_median")) return rc;
+  DeviceGuard dg(dev);
+  const int64_t plane = (int64_t)rows * frames;
+  return kam_launch_median(s_dev, plane, nsig, rows, frames, offsets, n, out_dev, plane, (hipStream_t)stream);
+}
+
+int glowk_kam_backfit(const float* v_dev, const float* a_dev, int nsig, int J, size_t n, float power, float* p_dev, float* mask_dev, void* stream) {
+  using namespace glowk_kam;
+  const std::string me("kam_backfit");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (J < 1 || J > MAX_J) return fail(me + ": J must be in [1, 8]");
+  if (n > (size_t)MAX_ELEMENTS || (uint64_t)nsig * J * n > (uint64_t)MAX_ELEMENTS) return fail(me + ": nsig * J * n must be at most 2^31 - 1");
+  if (int rc = kam_power(me, power)) return rc;
+  if (nsig == 0 || n == 0) return 0;
+  if (!v_dev || !a_dev || !p_dev) return fail("null tensor");
+  const size_t all = (size_t)nsig * J * n * 4;
+  if (int rc = iva_disjoint(me, {{p_dev, all}, {mask_dev, mask_dev ? all : 0}, {a_dev, all}, {v_dev, (size_t)nsig * n * 4}}, 2)) return rc;
+  int dev;
+  if (int rc = audio_device({v_dev, a_dev, p_dev, mask_dev}, &dev, "kam_backfit")) return rc;
+  DeviceGuard dg(dev);
+  return kam_launch_backfit(v_dev, a_dev, nsig, J, (int64_t)n, power, p_dev, mask_dev, (hipStream_t)stream);
+}
+
+size_t glowk_kam_work_bytes(int nsig, int rows, int frames, int J, const int32_t* model_k) {
+  using namespace glowk_kam;
+  if (nsig < 1 || !sizes_ok(nsig, rows, frames, J) || !model_k) return 0;
+  bool has_idx = false;
+  for (int j = 0; j < J; ++j) {
+    if (model_k[j] < 0 || model_k[j] > glowk_repet::MAX_K) return 0;
+    has_idx = has_idx || model_k[j] > 0;
+  }
+  return work_bytes(nsig, rows, frames, J, has_idx ? nn_work_bytes(1, rows, frames) : 0);
+}
+
+int glowk_kam_fit(const float* v_dev, int nsig, int rows, int frames, int J, const int32_t* model_n, const int32_t* offsets, const int32_t* model_k,
+                  const int32_t* const* idx_dev, int n_iter, float power, float* p_dev, float* mask_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_kam;
+  const std::string me("kam_fit");
+  if (int rc = kam_sizes(me, nsig, rows, frames, J)) return rc;
+  bool has_idx;
+  if (int rc = kam_models(me, nsig, frames, J, model_n, offsets, model_k, &has_idx)) return rc;
+  if (n_iter < 1 || n_iter > MAX_ITER) return fail(me + ": n_iter must be in [1, 100]");
+  if (int rc = kam_power(me, power)) return rc;
+  if (nsig == 0) return 0;
+  if (!v_dev || !p_dev || !work_dev) return fail("null tensor");
+  if (has_idx && !idx_dev) return fail(me + ": idx_dev is null");
+  const size_t nn_bytes = has_idx ? nn_work_bytes(1, rows, frames) : 0, need = glowk_kam::work_bytes(nsig, rows, frames, J, nn_bytes);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_kam_work_bytes says");
+  const size_t cells = (size_t)rows * frames, all = (size_t)nsig * J * cells * 4;
+  if (int rc = iva_disjoint(me, {{p_dev, all}, {mask_dev, mask_dev ? all : 0}, {work_dev, need}, {v_dev, (size_t)nsig * cells * 4}}, 3)) return rc;
+  for (int j = 0; j < J; ++j)
+    if (model_k[j]) {
+      if (!idx_dev[j]) return fail(me + ": a frame-neighbour model's tensor is null");
+      const size_t nk = (size_t)nsig * frames * model_k[j] * 4;
+      if (bytes_overlap(idx_dev[j], nk, p_dev, all) || bytes_overlap(idx_dev[j], nk, work_dev, need) || (mask_dev && bytes_overlap(idx_dev[j], nk, mask_dev, all)))
+        return fail(me + ": a tensor the call writes overlaps another of its tensors");
+    }
+  int dev;
+  if (int rc = audio_device({v_dev, p_dev, mask_dev, work_dev}, &dev, "kam_fit")) return rc;
+  for (int j = 0; j < J; ++j) {
+    int dj;
+    if (!model_k[j]) continue;
+    if (int rc = audio_device({idx_dev[j]}, &dj, "kam_fit")) return rc;
+    if (dj != dev) return fail(me + ": the tensors are on different devices");
+  }
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  float* a = (float*)work_dev;
+  void* nn_work = (char*)work_dev + work_a_bytes(nsig, rows, frames, J);
+  const int64_t plane = (int64_t)cells, group = (int64_t)J * plane;
+  for (int it = 0; it < n_iter; ++it) {
+    // iteration 0 filters the mixture itself (P_j = V for every j), later ones source j of p_dev; A_j goes to source j of the workspace
+    const float* src = it == 0 ? v_dev : p_dev;
+    const int64_t src_stride = it == 0 ? plane : group;
+    size_t at = 0;
+    for (int j = 0; j < J; ++j) {
+      const int64_t src_off = it == 0 ? 0 : j * plane;
+      if (model_n[j]) {
+        if (int rc = kam_launch_median(src + src_off, src_stride, nsig, rows, frames, offsets + 2 * at, model_n[j], a + j * plane, group, st)) return rc;
+        at += (size_t)model_n[j];
+      } else {
+        for (int sg = 0; sg < nsig; ++sg)      // glowk_nn_median wants contiguous signals: one signal at a time
+          if (int rc = glowk_nn_median(src + src_off + sg * src_stride, idx_dev[j] + (size_t)sg * frames * model_k[j], 1, rows, frames, model_k[j],
+                                       a + sg * group + j * plane, nn_work, nn_bytes, stream))
+            return rc;
+      }
+    }
+    if (int rc = kam_launch_backfit(v_dev, a, nsig, J, plane, power, p_dev, it == n_iter - 1 ? mask_dev : nullptr, st)) return rc;
+  }
   return 0;
 }
 

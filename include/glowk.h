@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 556
+#define GLOWK_VERSION 557
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -1131,6 +1131,50 @@ int glowk_cluster_posteriors(const float* f_dev, int nsig, int D, int J, int row
 /* One launch. */
 int glowk_cluster_spatial_features(const float* x_dev, int nsig, int rows, int frames, int delay, double max_delay, double p, float* feat_dev, float* w_dev,
                                    void* stream);
+
+/* --- Kernel additive modelling: sparse-kernel medians with back-fitting (Liutkus, FitzGerald, Rafii, Pardo & Daudet 2014; KAML 2015; ---- */
+/* --- glowk_kam.h) ---------------------------------------------------------------------------------------------------------------------- */
+/* Every source j has a proximity kernel, the set of time-frequency neighbours it is locally constant over; the sources are estimated
+ * together by back-fitting: median-filter each source's estimate over its own kernel, share the mixture out by the ratio of the results,
+ * repeat.  With J = 2, a horizontal and a vertical kernel and one iteration that is HPSS; with a periodic kernel, the adaptive REPET.
+ * s, v [nsig][rows][frames] float32, frames contiguous.  nsig in [0, 65535] (0: a successful no-op of valid arguments), rows in [1, 4096],
+ * frames in [1, 32768], J in [1, 8] sources, nsig J rows frames <= 2^31 - 1.  Conventions as in the sections above: handle-free, every
+ * tensor device memory on one device, enqueued on `stream`, no atomics, no allocation, no host synchronisation, a launch count that the
+ * shapes and models alone fix, GLOWK_ERR with a glowk_last_error message before anything is launched; tensors a call writes must not
+ * overlap its other tensors; bitwise reproducible, and a batch gives what its signals give alone.  Inputs are finite.
+ * audiosourcesep_amd/kam.py drives the calls.  Since version 557.
+ *
+ * The median over a sparse kernel.  `offsets` is a HOST table of n pairs (d_row, d_frame), int32 [n][2]: a parameter like a filter's
+ * size, checked on the host and passed to the kernel by value in its launch arguments (as int16 pairs).  1 <= n <= 127, |d_row| <= 4095,
+ * |d_frame| <= 32767; duplicates are allowed and count twice; (0, 0) need not be present.  The neighbours of cell (r, t) are the cells
+ * (r + d_row, t + d_frame) that lie inside the plane; the others are skipped and never read (no reflection).  With m of them: m odd, the
+ * middle element -- a selection by compares, the bits a sort gives; m even, (a + b) * 0.5f of the two middle elements in fp32, the only
+ * arithmetic on the values; m = 0, the cell itself (glowk_nn_median's rules).  Of elements that compare equal (they differ in bits only
+ * as -0 and +0 do) the first in table order is taken (glowk_median_filter's rule).  out_dev must not overlap s_dev.  One launch: a wave
+ * owns 64 consecutive frames of one row; a workgroup is four waves for n <= 64 and one above, a function of n alone. */
+int glowk_kam_median(const float* s_dev, int nsig, int rows, int frames, const int32_t* offsets, int n, float* out_dev, void* stream);
+/* The back-fitting step, elementwise in fp32 over n cells per signal: a [nsig][J][n] (the filtered estimates, >= 0), v [nsig][n] (the
+ * mixture magnitude), p and mask [nsig][J][n]; mask_dev may be null.  glowk_hpss_mask's arithmetic (both margins 1) from 2 to J sources:
+ *   Z = max_j a_j, bad = Z < FLT_MIN (1.17549435e-38), Z = 1 where bad; r_j = (a_j / Z)^power (powers 1 and 2 without powf);
+ *   mask_j = r_j / (r_0 + r_1 + .. + r_{J-1}), the sum in ascending j, and 1 / J where bad; p_j = v mask_j.
+ * Every operation rounds once (no contraction).  power finite and > 0; nsig J n <= 2^31 - 1 (n = 0 is a no-op).  One launch. */
+int glowk_kam_backfit(const float* v_dev, const float* a_dev, int nsig, int J, size_t n, float power, float* p_dev, float* mask_dev, void* stream);
+/* The bytes of work_dev that glowk_kam_fit needs: the filtered estimates, 4 nsig J rows frames rounded up to a multiple of 8 (as every
+ * size query here is), plus, when some model_k[j] > 0, glowk_nn_workspace_bytes(1, rows, frames, k).  model_k: host [J], as below.  0 for
+ * arguments out of range (and for nsig = 0). */
+size_t glowk_kam_work_bytes(int nsig, int rows, int frames, int J, const int32_t* model_k);
+/* The loop.  The model of source j is one of two kinds, told by two HOST arrays [J] of which exactly one is non-zero at j:
+ *   model_n[j] = n_j >= 1: an offset table of n_j pairs, filtered as glowk_kam_median does; the tables of these sources follow each other
+ *     in `offsets` (host, int32 [sum n_j][2]) in source order;
+ *   model_k[j] = k_j >= 1: a frame-neighbour tensor idx_dev[j] (idx_dev: a host array [J] of device pointers, null entries for the other
+ *     kind) int32 [nsig][frames][k_j], what glowk_nn_neighbors and glowk_period_neighbors write, filtered by glowk_nn_median, one signal
+ *     at a time.
+ * P_j = V for every j; each of the n_iter iterations (1 <= n_iter <= 100) computes A_j = filter_j(P_j) for every j, then P, mask =
+ * backfit(V, A).  p [nsig][J][rows][frames]; mask_dev (nullable) receives the last iteration's masks.  Bit for bit n_iter staged rounds of
+ * glowk_kam_median / glowk_nn_median and glowk_kam_backfit.  Per iteration one launch per offset model, 2 nsig per frame-neighbour model,
+ * and one for the back-fit.  work_bytes at least glowk_kam_work_bytes; work_dev 8-byte aligned is enough. */
+int glowk_kam_fit(const float* v_dev, int nsig, int rows, int frames, int J, const int32_t* model_n, const int32_t* offsets, const int32_t* model_k,
+                  const int32_t* const* idx_dev, int n_iter, float power, float* p_dev, float* mask_dev, void* work_dev, size_t work_bytes, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
