@@ -222,6 +222,10 @@ SYMBOLS = {
     "glowk_kam_backfit": (_i, [_vp, _vp, _i, _i, ctypes.c_size_t, ctypes.c_float, _vp, _vp, _vp]),
     "glowk_kam_work_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _vp]),
     "glowk_kam_fit": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmfd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_nmfd_fit": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmfd_divergence": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
+    "glowk_nmfd_masks": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -50,7 +50,7 @@ HOP = MEL_FRONTEND["hop_length"]
 NBIN = MEL_FRONTEND["n_fft"] // 2 + 1
 NMEL = MEL_FRONTEND["n_mels"]
 EXTRACT = int(SR * MEL_FRONTEND["length_sec"])          # 32 640 samples (datasets/preprocessing.py:9-26)
-GRIFFINLIM_STREAM = 13      # device RNG stream of init='random' (stream ids are 0..15; 0-3 serve the flows, 14 / 15 separate_audio)
+GRIFFINLIM_STREAM = 13      # device RNG stream of init='random' (stream ids are 0..15; 0-3 serve the flows, 11 nmfd, 12 nmf, 14 / 15 separate_audio)
 GRIFFINLIM_MAX_FRAMES = 1 << 20                          # glowk_griffinlim's cap: 9.3 h of 16 kHz audio in one signal
 MWF_EM_MAX_ITER = 1000                                   # glowk_mwf_em's cap on its EM iterations
 MIN_RATE, MAX_RATE = 1000, 768000                        # glowk_resample's sampling rates, at most a factor 64 apart

@@ -8,6 +8,7 @@
 // DUET: the attenuation-delay histogram, its peaks and the assignment of a two-channel STFT (glowk_duet.h)
 // NMF: fused multiplicative updates, the beta divergence and masks of component ranges (glowk_nmf.h)
 // AuxIVA and ILRMA: frame norms, weighted covariances with the iterative projection, demixing and images (glowk_iva.h)
+// convolutive NMF: NMF on K Tw stacked components whose activations are tied shifts of each other (glowk_nmfd.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -29,6 +30,7 @@
 #include "glowk_projet.h"
 #include "glowk_cluster.h"
 #include "glowk_kam.h"
+#include "glowk_nmfd.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -3416,6 +3418,160 @@ int glowk_kam_fit(const float* v_dev, int nsig, int rows, int frames, int J, con
     }
     if (int rc = kam_launch_backfit(v_dev, a, nsig, J, plane, power, p_dev, it == n_iter - 1 ? mask_dev : nullptr, st)) return rc;
   }
+  return 0;
+}
+
+// ---- convolutive NMF: K patches of Tw spectra, NMF on K Tw stacked components with tied shifts (glowk_nmfd.h) ------------------------------
+namespace {
+// the ranges every glowk_nmfd_* call shares; 0 or an error.  The stacked problem (rows, frames, K Tw) is held to the NMF ranges.
+int nmfd_ranges(const std::string& w, int nsig, int rows, int frames, int K, int Tw) {
+  using namespace glowk_nmfd;
+  if (K < 1 || K > glowk_nmf::MAX_K) return fail(w + ": K must be in [1, 128]");
+  if (Tw < 1 || Tw > MAX_TW) return fail(w + ": Tw must be in [1, 32]");
+  if (K * Tw > MAX_STACK) return fail(w + ": K * Tw must be at most 128");
+  return nmf_ranges(w, nsig, rows, frames, K * Tw);
+}
+}  // namespace
+
+size_t glowk_nmfd_workspace_bytes(int nsig, int rows, int frames, int K, int Tw) {
+  if (nmfd_ranges("nmfd_workspace_bytes", nsig, rows, frames, K, Tw)) return 0;
+  return glowk_nmfd::nmfd_work_bytes(nsig, rows, frames, K, Tw);
+}
+
+int glowk_nmfd_fit(const float* v_dev, int nsig, int rows, int frames, float* w_dev, int nw, float* h_dev, int K, int Tw, int beta, int n_iter, int update_w,
+                   void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_nmfd;
+  const std::string me("nmfd_fit");
+  if (int rc = nmfd_ranges(me, nsig, rows, frames, K, Tw)) return rc;
+  if (int rc = nmf_model(me, nsig, nw, beta)) return rc;
+  if (n_iter < 0 || n_iter > glowk_nmf::MAX_ITER) return fail(me + ": n_iter must be in [0, 100000]");
+  if (update_w < 0 || update_w > 2) return fail(me + ": update_w must be 0 (H alone), 1 (W, then H) or 2 (W alone)");
+  if (update_w && nw != nsig) return fail(me + ": a dictionary shared by several signals cannot be updated (nw = 1 needs update_w = 0)");
+  if (nsig == 0 || n_iter == 0) return 0;
+  if (!v_dev || !w_dev || !h_dev || !work_dev) return fail("null tensor");
+  const int KS = K * Tw;
+  const NmfPlan p = nmf_plan(rows, frames, KS);
+  const size_t need_w = update_w ? (size_t)nmf_w_part_floats(p, rows, KS) * 4 : 0, need_h = update_w != 2 ? (size_t)nmfd_plane_floats(KS, frames) * 4 : 0;
+  const size_t need = (size_t)nsig * (need_w > need_h ? need_w : need_h);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_nmfd_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8) return fail(me + ": work_dev must be aligned to 8 bytes");
+  const size_t nv = (size_t)nsig * rows * frames * 4, nww = (size_t)nw * rows * KS * 4, nh = (size_t)nsig * K * frames * 4;
+  if (bytes_overlap(v_dev, nv, w_dev, nww) || bytes_overlap(v_dev, nv, h_dev, nh) || bytes_overlap(w_dev, nww, h_dev, nh))
+    return fail(me + ": V, W and H must not overlap");
+  if (bytes_overlap(work_dev, need, v_dev, nv) || bytes_overlap(work_dev, need, w_dev, nww) || bytes_overlap(work_dev, need, h_dev, nh))
+    return fail(me + ": work_dev must not overlap the tensors");
+  int dev;
+  if (int rc = audio_device({v_dev, w_dev, h_dev, work_dev}, &dev, "nmfd_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)work_dev;
+  const int64_t wstride = nw == 1 ? 0 : (int64_t)rows * KS, per_sig = (int64_t)rows * KS, total = (int64_t)nsig * per_sig, htotal = (int64_t)nsig * K * frames;
+  const dim3 gw((unsigned)((int64_t)nsig * p.rtiles * p.nch)), gh((unsigned)((int64_t)nsig * p.ftiles)), gf((unsigned)((total + 255) / 256)),
+      ghf((unsigned)((htotal + 255) / 256));
+  for (int it = 0; it < n_iter; ++it) {
+    if (update_w) {
+      switch (p.kt) {
+#define GLOWK_CASE(n) \
+  case n: hipLaunchKernelGGL(k_nmfd_update_w<n>, gw, dim3(256), 0, st, v_dev, (const float*)w_dev, (const float*)h_dev, rows, frames, K, Tw, p, beta, part); break;
+        GLOWK_NMF_EACH_KT(GLOWK_CASE)
+#undef GLOWK_CASE
+      }
+      LAUNCHCHK("k_nmfd_update_w");
+      hipLaunchKernelGGL(glowk_nmf::k_nmf_w_finish, gf, dim3(256), 0, st, (const float*)part, total, per_sig, nmf_w_part_floats(p, rows, KS), p.nch, beta, w_dev);
+      LAUNCHCHK("k_nmf_w_finish");
+    }
+    if (update_w != 2) {
+      switch (p.kt) {
+#define GLOWK_CASE(n) \
+  case n: hipLaunchKernelGGL(k_nmfd_update_h<n>, gh, dim3(256), 0, st, v_dev, (const float*)w_dev, wstride, (const float*)h_dev, part, rows, frames, K, Tw, p.ftiles, beta); break;
+        GLOWK_NMF_EACH_KT(GLOWK_CASE)
+#undef GLOWK_CASE
+      }
+      LAUNCHCHK("k_nmfd_update_h");
+      hipLaunchKernelGGL(k_nmfd_h_finish, ghf, dim3(256), 0, st, (const float*)part, htotal, K, Tw, frames, beta, h_dev);
+      LAUNCHCHK("k_nmfd_h_finish");
+    }
+  }
+  return 0;
+}
+
+int glowk_nmfd_divergence(const float* v_dev, int nsig, int rows, int frames, const float* w_dev, int nw, const float* h_dev, int K, int Tw, int beta,
+                          double* out_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_nmfd;
+  const std::string me("nmfd_divergence");
+  if (int rc = nmfd_ranges(me, nsig, rows, frames, K, Tw)) return rc;
+  if (int rc = nmf_model(me, nsig, nw, beta)) return rc;
+  if (nsig == 0) return 0;
+  if (!v_dev || !w_dev || !h_dev || !out_dev || !work_dev) return fail("null tensor");
+  const int KS = K * Tw;
+  const NmfPlan p = nmf_plan(rows, frames, KS);
+  const size_t need = (size_t)nsig * (size_t)glowk_nmf::nmf_div_parts(p) * 8;
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_nmfd_workspace_bytes says");
+  if ((uintptr_t)work_dev % 8 || (uintptr_t)out_dev % 8) return fail(me + ": work_dev and out_dev must be aligned to 8 bytes");
+  const size_t nv = (size_t)nsig * rows * frames * 4, nww = (size_t)nw * rows * KS * 4, nh = (size_t)nsig * K * frames * 4, no = (size_t)nsig * 8;
+  const void* ins[3] = {v_dev, w_dev, h_dev};
+  const size_t in_sizes[3] = {nv, nww, nh};
+  for (int i = 0; i < 3; ++i)
+    if (bytes_overlap(ins[i], in_sizes[i], out_dev, no) || bytes_overlap(ins[i], in_sizes[i], work_dev, need))
+      return fail(me + ": out_dev and work_dev must not overlap the inputs");
+  if (bytes_overlap(out_dev, no, work_dev, need)) return fail(me + ": out_dev and work_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({v_dev, w_dev, h_dev, out_dev, work_dev}, &dev, "nmfd_divergence")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_nmfd_divergence, dim3((unsigned)((int64_t)nsig * p.rtiles * p.nch)), dim3(256), 0, st, v_dev, w_dev,
+                     nw == 1 ? (int64_t)0 : (int64_t)rows * KS, h_dev, rows, frames, K, Tw, p, beta, (double*)work_dev);
+  LAUNCHCHK("k_nmfd_divergence");
+  hipLaunchKernelGGL(glowk_nmf::k_nmf_div_reduce, dim3((unsigned)nsig), dim3(64), 0, st, (const double*)work_dev, glowk_nmf::nmf_div_parts(p), out_dev);
+  LAUNCHCHK("k_nmf_div_reduce");
+  return 0;
+}
+
+int glowk_nmfd_masks(const float* w_dev, int nw, const float* h_dev, int nsig, int rows, int frames, int K, int Tw, const int32_t* bounds_host,
+                     int num_sources, int power, const float* x_dev, int channels, float* mask_dev, float* spec_dev, void* stream) {
+  using namespace glowk_nmfd;
+  const std::string me("nmfd_masks");
+  if (int rc = nmfd_ranges(me, nsig, rows, frames, K, Tw)) return rc;
+  if (nw != 1 && nw != nsig) return fail(me + ": nw must be 1 (one shared dictionary) or nsig");
+  if (num_sources < 1 || num_sources > glowk_nmf::MAX_SRC) return fail(me + ": the number of sources must be in [1, 16]");
+  if (power != 1 && power != 2) return fail(me + ": power must be 1 or 2");
+  if (!bounds_host) return fail(me + ": bounds_host is null");
+  const int KS = K * Tw;
+  int bc[glowk_nmf::MAX_SRC + 1];                                // in components, as the caller gives them
+  for (int s = 0; s <= glowk_nmf::MAX_SRC; ++s) bc[s] = s <= num_sources ? bounds_host[s] : K;
+  if (bc[0] != 0 || bc[num_sources] != K) return fail(me + ": bounds must start at 0 and end at K");
+  for (int s = 0; s < num_sources; ++s)
+    if (bc[s] >= bc[s + 1]) return fail(me + ": bounds must increase strictly (every source owns at least one component)");
+  glowk_nmf::NmfBounds bd;                                       // in stacked components: k-major, so a range stays a range
+  for (int s = 0; s <= glowk_nmf::MAX_SRC; ++s) bd.b[s] = bc[s] * Tw;
+  if ((x_dev == nullptr) != (spec_dev == nullptr)) return fail(me + ": x_dev and spec_dev are given together or not at all");
+  if (x_dev && channels != 1 && channels != 2) return fail(me + ": the channel count must be 1 or 2");
+  const int C = x_dev ? channels : 0;
+  const int64_t cells = (int64_t)nsig * rows * frames;
+  if (cells * num_sources * (C ? C : 1) > (int64_t)INT32_MAX) return fail(me + ": nsig * S * C * rows * frames must be at most 2^31 - 1");
+  if (nsig == 0) return 0;
+  if (!w_dev || !h_dev || !mask_dev) return fail("null tensor");
+  if ((uintptr_t)x_dev % 8 || (uintptr_t)spec_dev % 8) return fail(me + ": x_dev and spec_dev must be aligned to 8 bytes");
+  const size_t nww = (size_t)nw * rows * KS * 4, nh = (size_t)nsig * K * frames * 4, nx = (size_t)cells * C * 8,
+               nm = (size_t)cells * num_sources * 4, ns = (size_t)cells * num_sources * C * 8;
+  const void* ins[3] = {w_dev, h_dev, x_dev};
+  const size_t in_sizes[3] = {nww, nh, nx};
+  for (int i = 0; i < 3; ++i) {
+    if (!ins[i]) continue;
+    if (bytes_overlap(ins[i], in_sizes[i], mask_dev, nm) || (spec_dev && bytes_overlap(ins[i], in_sizes[i], spec_dev, ns)))
+      return fail(me + ": mask_dev and spec_dev must not overlap the inputs");
+  }
+  if (spec_dev && bytes_overlap(mask_dev, nm, spec_dev, ns)) return fail(me + ": mask_dev and spec_dev must not overlap");
+  int dev;
+  if (int rc = audio_device({w_dev, h_dev, x_dev, mask_dev, spec_dev}, &dev, "nmfd_masks")) return rc;
+  DeviceGuard dg(dev);
+  const NmfPlan p = nmf_plan(rows, frames, KS);
+  const int fgroups = (p.ftiles + glowk_nmf::WAVES - 1) / glowk_nmf::WAVES;
+  if ((int64_t)nsig * p.rtiles * fgroups > (int64_t)INT32_MAX) return fail(me + ": the workgroup count must be at most 2^31 - 1");
+  hipLaunchKernelGGL(k_nmfd_masks, dim3((unsigned)((int64_t)nsig * p.rtiles * fgroups)), dim3(256), 0, (hipStream_t)stream, w_dev,
+                     nw == 1 ? (int64_t)0 : (int64_t)rows * KS, h_dev, rows, frames, K, Tw, p.rtiles, fgroups, bd, num_sources, power, (const float2*)x_dev, C, mask_dev,
+                     (float2*)spec_dev);
+  LAUNCHCHK("k_nmfd_masks");
   return 0;
 }
 

@@ -29,7 +29,7 @@ from .audio import _p, _s
 from .repet import MAX_ELEMENTS, MAX_FRAMES, MAX_ROWS, MAX_SIGNALS, _check_flag, _check_range_int
 
 MAX_COMPONENTS, MAX_SOURCES, MAX_ITER = 128, 16, 100000
-NMF_STREAM = 12             # device RNG stream of ``init`` (0-3 serve the flows, 13 griffinlim, 14 / 15 separate_audio)
+NMF_STREAM = 12             # device RNG stream of ``init`` (0-3 serve the flows, 11 nmfd, 13 griffinlim, 14 / 15 separate_audio)
 
 
 def _check_beta(beta):

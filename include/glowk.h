@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 557
+#define GLOWK_VERSION 558
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -1175,6 +1175,53 @@ size_t glowk_kam_work_bytes(int nsig, int rows, int frames, int J, const int32_t
  * and one for the back-fit.  work_bytes at least glowk_kam_work_bytes; work_dev 8-byte aligned is enough. */
 int glowk_kam_fit(const float* v_dev, int nsig, int rows, int frames, int J, const int32_t* model_n, const int32_t* offsets, const int32_t* model_k,
                   const int32_t* const* idx_dev, int n_iter, float power, float* p_dev, float* mask_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* --- Convolutive NMF (NMFD): time-varying templates (Smaragdis 2004; Schmidt & Morup 2006; Smaragdis 2007; glowk_nmfd.h) --------------- */
+/* Every component is a patch of Tw spectra instead of one spectrum; the activations say where the patches start.
+ * V [nsig][rows][frames] float32, finite and >= 0, frames contiguous; W [nw][rows][K][Tw], Tw contiguous, nw = nsig or 1 (one
+ * dictionary shared by every signal, allowed only where W is not updated); H [nsig][K][frames]; W and H float32, finite and >= 0.
+ * FLOOR = 2^-40, beta = 0, 1 or 2 and g as in the NMF section.
+ * The stacked view, s = k Tw + tau (k-major): Ws [rows][K Tw] is W's own memory read as an NMF dictionary; Hs[s][t] = H[k][t - tau],
+ * and an exact 0 for t < tau.  L = Ws Hs, an fp32 fma chain over s (padded with exact zeros) on v_mfma_f32_32x32x2_f32; Le, Q, P and g
+ * exactly as in the NMF section.  Hs is never in memory: the shift is applied where H is loaded.
+ *   W update: W' = W g(Q Hs^T / max(P Hs^T, FLOOR)): the NMF W update on (V, Ws, Hs), bit for bit what glowk_nmf_fit (update_w 2)
+ *     gives on a materialised Hs (the same chain order over s, the same chunk plan at K Tw components).
+ *   H update, the joint one (the majorise-minimise argument holds for it: no update increases D):
+ *     N[k][t] = sum_tau sum_f W[f][k][tau] Q[f][t + tau] over t + tau < frames, D the same sum with P, H' = H g(N / max(D, FLOOR)).
+ *     The sums over f are the NMF H update's chains Ws^T Q and Ws^T P; the Tw shifted rows are then added in ascending tau in fp32.
+ *     At Tw = 1 this is glowk_nmf_fit's H update bit for bit.
+ * One iteration is the W update with the old H, then the H update with the new W.  frames < Tw is allowed: the slices tau >= frames
+ * meet no data, and a W update makes them exact zeros.  A source that owns the components [k0, k1) owns the stacked range
+ * [k0 Tw, k1 Tw).  Every term is non-negative, so the error of one update is relative per element: at most (3 K Tw + 2 rows Tw + 16)
+ * 2^-24 of the value for H, (3 K Tw + 2 frames + 16) 2^-24 for W, and an exact 0 where the exact result is 0.  L, Q and P exist in
+ * registers alone.  Conventions as in the NMF section: handle-free, every tensor device memory on one device, launches on `stream`
+ * with no atomics, no allocation and no host synchronisation, a launch count that depends on the shapes and n_iter alone, bitwise
+ * reproducible results, a batch gives what its signals give alone.  K in [1, 128], Tw in [1, 32], K Tw <= 128 (more needs several
+ * passes over the accumulators); nsig, rows, frames and the element counts as in the NMF section with K Tw for K; anything else is
+ * GLOWK_ERR with a glowk_last_error message before anything is launched.  audiosourcesep_amd/nmfd.py drives the calls.
+ * Since version 558. */
+/* The bytes of work_dev that glowk_nmfd_fit and glowk_nmfd_divergence need: with nch and rtiles of glowk_nmf_workspace_bytes at K Tw
+ * components, nsig max(8 nch rows K Tw, 8 rtiles nch, 8 K Tw frames) -- the W update's partial sums, the divergence's, and the H
+ * update's stacked numerators and denominators.  0 for arguments out of range (and for nsig = 0). */
+size_t glowk_nmfd_workspace_bytes(int nsig, int rows, int frames, int K, int Tw);
+/* n_iter iterations in place; update_w = 1: W, then H; 0: H alone (W may be shared, nw = 1); 2: W alone, as in glowk_nmf_fit.  The W
+ * update is two launches as there.  The H update is two launches: the stacked numerators and denominators [2][K Tw][frames] go to
+ * work_dev (a workgroup owns 32 frames of them), and a second launch adds the shifts and takes the step, so work_dev is needed in
+ * every mode.  4 n_iter launches with update_w = 1, 2 n_iter with 0 or 2.  V, W, H and work must not overlap; work_dev aligned to 8
+ * bytes. */
+int glowk_nmfd_fit(const float* v_dev, int nsig, int rows, int frames, float* w_dev, int nw, float* h_dev, int K, int Tw, int beta, int n_iter,
+                   int update_w, void* work_dev, size_t work_bytes, void* stream);
+/* out[sig] = D_beta(V | Ws Hs), float64: glowk_nmf_divergence on (V, Ws, Hs), bit for bit.  At most (K Tw + 4) 2^-24 sum(w) from the
+ * exact value.  Two launches. */
+int glowk_nmfd_divergence(const float* v_dev, int nsig, int rows, int frames, const float* w_dev, int nw, const float* h_dev, int K, int Tw, int beta,
+                          double* out_dev /* [nsig] */, void* work_dev, size_t work_bytes, void* stream);
+/* Ratio masks of num_sources <= 16 sources that own the component ranges [bounds[s], bounds[s + 1]), bounds_host[0] = 0 < .. <
+ * bounds_host[num_sources] = K, in components: glowk_nmf_masks on (Ws, Hs) with the bounds scaled by Tw, bit for bit; power, x_dev,
+ * channels, mask_dev and spec_dev as there.  One launch. */
+int glowk_nmfd_masks(const float* w_dev, int nw, const float* h_dev, int nsig, int rows, int frames, int K, int Tw, const int32_t* bounds_host,
+                     int num_sources, int power, const float* x_dev /* [nsig][C][rows][frames] complex64, or null */, int channels,
+                     float* mask_dev /* [nsig][S][rows][frames] */, float* spec_dev /* [nsig][S][C][rows][frames] complex64, or null */,
+                     void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
