@@ -226,6 +226,12 @@ SYMBOLS = {
     "glowk_nmfd_fit": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "glowk_nmfd_divergence": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, ctypes.c_size_t, _vp]),
     "glowk_nmfd_masks": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "glowk_wpe_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "glowk_wpe_power": (_i, [_vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "glowk_wpe_correlations": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "glowk_wpe_solve": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "glowk_wpe_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "glowk_wpe_fit": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 // NMF: fused multiplicative updates, the beta divergence and masks of component ranges (glowk_nmf.h)
 // AuxIVA and ILRMA: frame norms, weighted covariances with the iterative projection, demixing and images (glowk_iva.h)
 // convolutive NMF: NMF on K Tw stacked components whose activations are tied shifts of each other (glowk_nmfd.h)
+// WPE dereverberation: the inverse power, the weighted correlations of the stacked past, the Cholesky solve and the filter (glowk_wpe.h)
 #include "glowk_engine.h"
 #include "glowk_basis.h"
 #include "glowk_audio.h"
@@ -31,6 +32,7 @@
 #include "glowk_cluster.h"
 #include "glowk_kam.h"
 #include "glowk_nmfd.h"
+#include "glowk_wpe.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -3572,6 +3574,172 @@ int glowk_nmfd_masks(const float* w_dev, int nw, const float* h_dev, int nsig, i
                      nw == 1 ? (int64_t)0 : (int64_t)rows * KS, h_dev, rows, frames, K, Tw, p.rtiles, fgroups, bd, num_sources, power, (const float2*)x_dev, C, mask_dev,
                      (float2*)spec_dev);
   LAUNCHCHK("k_nmfd_masks");
+  return 0;
+}
+
+// ---- WPE dereverberation: delayed linear prediction, the correlations on the fp64 matrix cores (glowk_wpe.h) ---------------------------------
+namespace {
+int wpe_sizes(const std::string& w, int nsig, int M, int rows, int frames) {
+  using namespace glowk_wpe;
+  if (nsig < 0 || nsig > MAX_SIG) return fail(w + ": nsig must be in [0, 65535]");
+  if (M < 1 || M > MAX_M) return fail(w + ": the channel count M must be in [1, 4]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(w + ": rows must be in [1, 4096]");
+  if (frames < 1 || frames > MAX_FRAMES) return fail(w + ": frames must be in [1, 32768]");
+  if (!sizes_ok(nsig, M, rows, frames)) return fail(w + ": nsig * M * rows * frames must be at most 2^31 - 1");
+  return 0;
+}
+int wpe_model(const std::string& w, int M, int K, int delay) {
+  using namespace glowk_wpe;
+  if (K < 1 || K > MAX_K) return fail(w + ": the tap count K must be in [1, 32]");
+  if (M * K > MAX_D) return fail(w + ": M * K must be at most 64");
+  if (delay < 1 || delay > MAX_DELAY) return fail(w + ": delay must be in [1, 16]");
+  return 0;
+}
+int wpe_power_args(const std::string& w, int context, double eps) {
+  if (context < 0 || context > glowk_wpe::MAX_CONTEXT) return fail(w + ": context must be in [0, 8]");
+  if (!(eps > 0.0 && eps <= 1.0)) return fail(w + ": eps must be in (0, 1]");
+  return 0;
+}
+int wpe_loading(const std::string& w, double loading) {
+  if (!(loading >= 0.0 && loading <= 1.0)) return fail(w + ": loading must be in [0, 1]");
+  return 0;
+}
+int wpe_launch_power(const float* y, int nsig, int M, int rows, int frames, int context, double eps, double* w, double* pmax, hipStream_t st) {
+  using namespace glowk_wpe;
+  hipLaunchKernelGGL(k_wpe_power, dim3((unsigned)row_grid(nsig, rows)), dim3(THREADS), 0, st, (const float2*)y, M, rows, frames, context, eps, w, pmax);
+  LAUNCHCHK("k_wpe_power");
+  return 0;
+}
+int wpe_launch_corr(const float* x, const double* w, int nsig, int M, int rows, int frames, int K, int delay, double* r, double* p, hipStream_t st) {
+  using namespace glowk_wpe;
+  hipLaunchKernelGGL(k_wpe_corr, dim3((unsigned)row_grid(nsig, rows)), dim3(THREADS), 0, st, (const float2*)x, w, M, K, delay, rows, frames, (double2*)r, (double2*)p);
+  LAUNCHCHK("k_wpe_corr");
+  return 0;
+}
+int wpe_launch_solve(const double* r, const double* p, int nsig, int rows, int D, int M, double loading, double* g, int* status, hipStream_t st) {
+  using namespace glowk_wpe;
+  hipLaunchKernelGGL(k_wpe_solve, dim3((unsigned)row_grid(nsig, rows)), dim3(SOLVE_THREADS), 0, st, (const double2*)r, (const double2*)p, D, M, loading, (double2*)g,
+                     status);
+  LAUNCHCHK("k_wpe_solve");
+  return 0;
+}
+int wpe_launch_filter(const float* x, const double* g, int nsig, int M, int rows, int frames, int K, int delay, float* y, hipStream_t st) {
+  using namespace glowk_wpe;
+  hipLaunchKernelGGL(k_wpe_filter, dim3((unsigned)filter_grid(nsig, rows, frames)), dim3(THREADS), 0, st, (const float2*)x, (const double2*)g, M, K, delay, rows, frames,
+                     (float2*)y);
+  LAUNCHCHK("k_wpe_filter");
+  return 0;
+}
+}  // namespace
+
+size_t glowk_wpe_workspace_bytes(int nsig, int M, int K, int rows, int frames) {
+  if (wpe_sizes("wpe_workspace_bytes", nsig, M, rows, frames) || K < 1 || K > glowk_wpe::MAX_K || M * K > glowk_wpe::MAX_D) return 0;
+  return glowk_wpe::work_bytes(nsig, M, K, rows, frames);
+}
+
+int glowk_wpe_power(const float* y_dev, int nsig, int M, int rows, int frames, int context, double eps, double* w_dev, double* max_dev, void* stream) {
+  using namespace glowk_wpe;
+  const std::string me("wpe_power");
+  if (int rc = wpe_sizes(me, nsig, M, rows, frames)) return rc;
+  if (int rc = wpe_power_args(me, context, eps)) return rc;
+  if (nsig == 0) return 0;
+  if (!y_dev || !w_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {y_dev, w_dev, max_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{w_dev, w_bytes(nsig, rows, frames)}, {max_dev, (size_t)nsig * rows * 8}, {y_dev, x_bytes(nsig, M, rows, frames)}}, 2)) return rc;
+  int dev;
+  if (int rc = audio_device({y_dev, w_dev, max_dev}, &dev, "wpe_power")) return rc;
+  DeviceGuard dg(dev);
+  return wpe_launch_power(y_dev, nsig, M, rows, frames, context, eps, w_dev, max_dev, (hipStream_t)stream);
+}
+
+int glowk_wpe_correlations(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, int K, int delay, double* r_dev, double* p_dev,
+                           void* stream) {
+  using namespace glowk_wpe;
+  const std::string me("wpe_correlations");
+  if (int rc = wpe_sizes(me, nsig, M, rows, frames)) return rc;
+  if (int rc = wpe_model(me, M, K, delay)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !w_dev || !r_dev || !p_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, w_dev, r_dev, p_dev})) return rc;
+  const int D = stacked(M, K);
+  if (int rc = iva_disjoint(me, {{r_dev, r_bytes(nsig, rows, D)}, {p_dev, p_bytes(nsig, rows, D, M)}, {x_dev, x_bytes(nsig, M, rows, frames)},
+                                 {w_dev, w_bytes(nsig, rows, frames)}}, 2))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, w_dev, r_dev, p_dev}, &dev, "wpe_correlations")) return rc;
+  DeviceGuard dg(dev);
+  return wpe_launch_corr(x_dev, w_dev, nsig, M, rows, frames, K, delay, r_dev, p_dev, (hipStream_t)stream);
+}
+
+int glowk_wpe_solve(const double* r_dev, const double* p_dev, int nsig, int rows, int D, int M, double loading, double* g_dev, int32_t* status_dev, void* stream) {
+  using namespace glowk_wpe;
+  const std::string me("wpe_solve");
+  if (nsig < 0 || nsig > MAX_SIG) return fail(me + ": nsig must be in [0, 65535]");
+  if (rows < 1 || rows > MAX_ROWS) return fail(me + ": rows must be in [1, 4096]");
+  if (M < 1 || M > MAX_M) return fail(me + ": the channel count M must be in [1, 4]");
+  if (D < 1 || D > MAX_D) return fail(me + ": the system size D must be in [1, 64]");
+  if (int rc = wpe_loading(me, loading)) return rc;
+  if (nsig == 0) return 0;
+  if (!r_dev || !p_dev || !g_dev || !status_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {r_dev, p_dev, g_dev})) return rc;
+  if ((uintptr_t)status_dev % 4) return fail(me + ": status_dev must be aligned to 4 bytes");
+  if (int rc = iva_disjoint(me, {{g_dev, p_bytes(nsig, rows, D, M)}, {status_dev, (size_t)nsig * rows * 4}, {r_dev, r_bytes(nsig, rows, D)},
+                                 {p_dev, p_bytes(nsig, rows, D, M)}}, 2))
+    return rc;
+  int dev;
+  if (int rc = audio_device({r_dev, p_dev, g_dev, status_dev}, &dev, "wpe_solve")) return rc;
+  DeviceGuard dg(dev);
+  return wpe_launch_solve(r_dev, p_dev, nsig, rows, D, M, loading, g_dev, status_dev, (hipStream_t)stream);
+}
+
+int glowk_wpe_filter(const float* x_dev, const double* g_dev, int nsig, int M, int rows, int frames, int K, int delay, float* y_dev, void* stream) {
+  using namespace glowk_wpe;
+  const std::string me("wpe_filter");
+  if (int rc = wpe_sizes(me, nsig, M, rows, frames)) return rc;
+  if (int rc = wpe_model(me, M, K, delay)) return rc;
+  if (nsig == 0) return 0;
+  if (!x_dev || !g_dev || !y_dev) return fail("null tensor");
+  if (int rc = iva_aligned(me, {x_dev, g_dev, y_dev})) return rc;
+  if (int rc = iva_disjoint(me, {{y_dev, x_bytes(nsig, M, rows, frames)}, {x_dev, x_bytes(nsig, M, rows, frames)}, {g_dev, p_bytes(nsig, rows, stacked(M, K), M)}}, 1))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, g_dev, y_dev}, &dev, "wpe_filter")) return rc;
+  DeviceGuard dg(dev);
+  return wpe_launch_filter(x_dev, g_dev, nsig, M, rows, frames, K, delay, y_dev, (hipStream_t)stream);
+}
+
+int glowk_wpe_fit(const float* x_dev, int nsig, int M, int rows, int frames, int K, int delay, int iterations, int context, double eps, double loading,
+                  float* y_dev, double* g_dev, int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream) {
+  using namespace glowk_wpe;
+  const std::string me("wpe_fit");
+  if (int rc = wpe_sizes(me, nsig, M, rows, frames)) return rc;
+  if (int rc = wpe_model(me, M, K, delay)) return rc;
+  if (int rc = wpe_power_args(me, context, eps)) return rc;
+  if (int rc = wpe_loading(me, loading)) return rc;
+  if (iterations < 0 || iterations > MAX_ITER) return fail(me + ": iterations must be in [0, 1000]");
+  if (nsig == 0 || iterations == 0) return 0;
+  if (!x_dev || !y_dev || !g_dev || !status_dev || !work_dev) return fail("null tensor");
+  const size_t need = glowk_wpe::work_bytes(nsig, M, K, rows, frames);
+  if (work_bytes < need) return fail(me + ": work_bytes is smaller than glowk_wpe_workspace_bytes says");
+  if (int rc = iva_aligned(me, {x_dev, y_dev, g_dev, work_dev})) return rc;
+  if ((uintptr_t)status_dev % 4) return fail(me + ": status_dev must be aligned to 4 bytes");
+  const int D = stacked(M, K);
+  if (int rc = iva_disjoint(me, {{y_dev, x_bytes(nsig, M, rows, frames)}, {g_dev, p_bytes(nsig, rows, D, M)}, {status_dev, (size_t)nsig * rows * 4}, {work_dev, need},
+                                 {x_dev, x_bytes(nsig, M, rows, frames)}}, 4))
+    return rc;
+  int dev;
+  if (int rc = audio_device({x_dev, y_dev, g_dev, status_dev, work_dev}, &dev, "wpe_fit")) return rc;
+  DeviceGuard dg(dev);
+  hipStream_t st = (hipStream_t)stream;
+  double* w = (double*)work_dev;
+  double* r = w + (size_t)nsig * rows * frames;
+  double* p = r + (size_t)nsig * rows * D * D * 2;
+  for (int it = 0; it < iterations; ++it) {
+    if (int rc = wpe_launch_power(it ? y_dev : x_dev, nsig, M, rows, frames, context, eps, w, nullptr, st)) return rc;
+    if (int rc = wpe_launch_corr(x_dev, w, nsig, M, rows, frames, K, delay, r, p, st)) return rc;
+    if (int rc = wpe_launch_solve(r, p, nsig, rows, D, M, loading, g_dev, status_dev, st)) return rc;
+    if (int rc = wpe_launch_filter(x_dev, g_dev, nsig, M, rows, frames, K, delay, y_dev, st)) return rc;
+  }
   return 0;
 }
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GLOWK_VERSION 558
+#define GLOWK_VERSION 559
 
 /* Arguments of build_glow (flow_builder.py:60-61) + SpecPreprocessing kwargs (flow_tfp_bijectors.py:365). */
 typedef struct glowk_config {
@@ -1222,6 +1222,63 @@ int glowk_nmfd_masks(const float* w_dev, int nw, const float* h_dev, int nsig, i
                      int num_sources, int power, const float* x_dev /* [nsig][C][rows][frames] complex64, or null */, int channels,
                      float* mask_dev /* [nsig][S][rows][frames] */, float* spec_dev /* [nsig][S][C][rows][frames] complex64, or null */,
                      void* stream);
+
+/* --- WPE dereverberation: delayed linear prediction (Nakatani et al. 2010; Yoshioka & Nakatani 2012; nara_wpe; glowk_wpe.h) ----------- */
+/* Per signal and frequency row, independently.  X [nsig][M][rows][frames] complex64, K taps, delay, D = M K.  The stacked past
+ * x~(t) in C^D has x~[k M + m](t) = x_m(t - delay - k), zero where t - delay - k < 0.  One iteration:
+ *   power         q(t) = (sum_m |y_m(t)|^2) / M (m ascending); p(t) = q(t), or with context c > 0 the sum of q over the frames of
+ *                 [t - c, t + c] that exist (ascending) divided by their count; w(t) = 1 / max(p(t), eps max_t p(t)).  A row whose
+ *                 maximum is zero or not finite gets w = 0 everywhere: its correlations are zero, its solve fails its first pivot, so
+ *                 it is flagged, G = 0, and the filter passes it through.
+ *   correlations  R = sum_t w(t) x~ x~^H [D][D] (both triangles, R[j][i] the bitwise conjugate of R[i][j], the diagonal's imaginary
+ *                 part exactly 0) and P = sum_t w(t) x~ x^H [D][M], on v_mfma_f64_16x16x4_f64: with x~ = a + i b an element is
+ *                 (Gaa + Gbb) + i (Gba - Gab) with the four real Gram sums Gpq[i][j] = sum_t (w p_i) q_j, frames ascending, four to an
+ *                 instruction, each in its own accumulator from 0.0 and combined once at the end.
+ *   solve         tr = sum_i Re R[i][i] (ascending); R[i][i] += loading (tr / D); R = L L^H by columns; a pivot that is not finite
+ *                 or not > 0 gives G = 0 and status GLOWK_WPE_PIVOT (1); else status 0 and G = R^-1 P [D][M] by the two triangular
+ *                 solves.
+ *   filter        y_m(t) = x_m(t) - sum_e conj(G[e][m]) x~_e(t), e ascending, each component rounded once to float32.  A row whose G
+ *                 is all zeros is copied.
+ * From the second iteration on the power is taken from the complex64 y the previous iteration stored, so glowk_wpe_fit gives the bits
+ * of the four staged calls iterated by hand.  Error bounds, with u = 2^-53 and T = frames:
+ *   w             relative (M + 2 c + 6) u per element; the row maximum is exact where the q are.
+ *   R, P          with the stacked real vector v = [a; b], a real Gram sum is within (T + 8) u sum_t w |v_i| |v_j| of its exact value;
+ *                 so |Re error[i][j]| <= (T + 8) u sum_t w (|a_i| |a_j| + |b_i| |b_j|) and |Im error[i][j]| <= (T + 8) u sum_t w
+ *                 (|b_i| |a_j| + |a_i| |b_j|).
+ *   G             backward: (R' + E) G = P with R' the loaded matrix as stored in fp64 and |E| <= 12 (D + 1) u |L| |L^H|
+ *                 elementwise (Cholesky plus two triangular solves, 3 D + 1 roundings of complex arithmetic at 2 sqrt 2 u each), so
+ *                 |R' G - P| <= 12 (D + 1) u |L| |L^H| |G|.
+ *   y             one float32 rounding of the fp64 value, whose error is at most (4 D + 2) u (|x_m| + sum_e |G[e][m]| |x~_e|_1).
+ *   one iteration given its weights: the bound of y plus 2 cond(R') ((T + 8) + 12 (D + 1)) u ||G||_F ||x~(t)||_2, normwise: the
+ *                 operation counts of the correlations and of the solve are part of the bound, not u cond alone.  Over several
+ *                 iterations it holds as long as the complex64 estimates between them round alike; in practice the float32
+ *                 rounding term dominates.
+ * Everything after the float32 load is fp64 without contraction; every order is fixed by the shapes; results are bitwise
+ * reproducible and a batch gives what its signals give alone.  Handle-free, every tensor device memory on one device, launches on
+ * `stream`, no atomics, no allocation, no host synchronisation.  M in [1, 4], K in [1, 32], M K <= 64, delay in [1, 16], context in
+ * [0, 8], eps in (0, 1], loading in [0, 1], iterations in [0, 1000], nsig in [0, 65535], rows in [1, 4096], frames in [1, 32768], nsig M
+ * rows frames <= 2^31 - 1; anything else is GLOWK_ERR with a glowk_last_error message before anything is launched.  Tensors aligned
+ * to 8 bytes (status 4); a tensor a call writes must not overlap another of its tensors.  audiosourcesep_amd/wpe.py drives the
+ * calls.  Since version 559. */
+#define GLOWK_WPE_OK 0
+#define GLOWK_WPE_PIVOT 1
+/* The bytes of glowk_wpe_fit's work_dev: w [nsig][rows][frames] float64, R [nsig][rows][D][D] and P [nsig][rows][D][M] complex128.
+ * 0 for arguments out of range (and for nsig = 0). */
+size_t glowk_wpe_workspace_bytes(int nsig, int M, int K, int rows, int frames);
+/* w [nsig][rows][frames] float64 from y [nsig][M][rows][frames] complex64; max_dev [nsig][rows] float64, or null, receives max_t p.
+ * One launch, one workgroup per (signal, row). */
+int glowk_wpe_power(const float* y_dev, int nsig, int M, int rows, int frames, int context, double eps, double* w_dev, double* max_dev, void* stream);
+/* r_dev [nsig][rows][D][D] and p_dev [nsig][rows][D][M] complex128.  One launch, one workgroup per (signal, row). */
+int glowk_wpe_correlations(const float* x_dev, const double* w_dev, int nsig, int M, int rows, int frames, int K, int delay, double* r_dev, double* p_dev,
+                           void* stream);
+/* g_dev [nsig][rows][D][M] complex128 and status_dev [nsig][rows] int32 for any D in [1, 64].  One launch, one wave per (signal, row). */
+int glowk_wpe_solve(const double* r_dev, const double* p_dev, int nsig, int rows, int D, int M, double loading, double* g_dev, int32_t* status_dev, void* stream);
+/* y_dev like x_dev.  One launch, one workgroup per (signal, row, 256 frames). */
+int glowk_wpe_filter(const float* x_dev, const double* g_dev, int nsig, int M, int rows, int frames, int K, int delay, float* y_dev, void* stream);
+/* `iterations` iterations (power of x, then of y; correlations; solve; filter): 4 launches each, all in one call.  y_dev, g_dev and
+ * status_dev receive the last iteration's; with iterations = 0 nothing is written. */
+int glowk_wpe_fit(const float* x_dev, int nsig, int M, int rows, int frames, int K, int delay, int iterations, int context, double eps, double loading,
+                  float* y_dev, double* g_dev, int32_t* status_dev, void* work_dev, size_t work_bytes, void* stream);
 
 /* --- host utility ----------------------------------------------------------------------------------------------------------- */
 /* CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord frames (datasets/preprocessing.py:197-271) and of TensorFlow
